@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- slides/sec of the RRTEncoder forward on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the headline line (metric, value, unit, ms_per_step, dtype, ...).
+Everything else this file measures -- the spread repeats, the rooflines and the kernel table, the raw C-ABI loop, the
+module-call / other-config / fresh-input / bf16 / f32x3 / H2D / training records and the CPU baseline -- runs only with
+--full (--no-extras / --no-cpu-baseline then leave out parts of it).
+--dump-outputs DIR: after the timed steps, what the last timed step handed its caller, as DIR/<name>.npy (a fixed
+sample of rows of every output where all of them would exceed DUMP_BYTES; see dump_outputs).  The inputs are the same on
+every run with the same arguments, so two builds can be compared output for output.
 
 With --gpus N > 1 and no torch.distributed environment, bench.py re-executes itself under
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`` (one rank per
@@ -22,7 +30,7 @@ In configs 0-3 a step = one batch of `--streams` (default 4; 3 for bf16 bags of 
 bags per GPU: `--streams` bags in flight, each an ordinary forward on its own HIP stream with its own workspace (bags are
 independent units), and every rank owns its own bags ("scaling": "weak").  No data-path collective anywhere: RCCL carries the barrier and a MAX of the elapsed time.
 
-Besides the contract fields the JSON line carries
+With --full, besides the contract fields the JSON line carries
   roofline     -- the dominant kernel (the fused R-MSA kernel): algorithmic FLOPs per launch / its average
                   duration, measured live with HIP events that librrt_hip records on the launch stream inside
                   the timed region (config 2: in an untimed pass of the same encoder; the one-call classifier
@@ -40,7 +48,7 @@ Besides the contract fields the JSON line carries
                   (oracle/rrt_oracle.py::forward_eager) timed on this box's host cores over a bounded sample
                   of the same workload (rank 0, N=1 only).
 --dtype overrides a config's arithmetic (f32 | bf16 | f16 | f32x3 = fp32 in / out with the big products emulated on the bf16
-matrix cores, RRT_COMPUTE_F32X3); the default run also reports bf16 and f32x3 as extra records (`amp_bf16`, `f32x3`).
+matrix cores, RRT_COMPUTE_F32X3); a --full run also reports bf16 and f32x3 as extra records (`amp_bf16`, `f32x3`).
 --stub-cpu replaces the GPU workload by a tiny CPU one over gloo: the rank logic (spawn, sharding, barrier,
 MAX over ranks, the JSON line) then runs without a GPU -- tests/test_multiproc_cpu.py drives it.
 """
@@ -70,6 +78,9 @@ DIM = 512
 PEAK_TFLOPS = {"f32": 157.3, "bf16": 2500.0}   # MI355X_MICROARCH.md: dense MFMA peaks (f32 in / bf16 in)
 PEAK_HBM_GBS = 8000.0                          # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec; ~6.3 TB/s achievable)
 FRESH_BYTES = 512 << 20                        # --fresh-inputs: distinct input bytes in rotation (2 x the 256 MiB Infinity Cache)
+DUMP_BYTES = 48 << 20                          # --dump-outputs: bytes of array data over all files and ranks (< 64 MB)
+
+
 def _newest(stem):
     """profiles/rNN_<stem> of the latest round that has one (the files are written by tools/, never typed in)"""
     for rnd in ("r06", "r05", "r04", "r03"):
@@ -299,7 +310,10 @@ def cpu_baseline(n_tokens, enc_cfg, budget_s=22.0):
     st = {k: torch.from_numpy(v) for k, v in state.items()}
     x = torch.from_numpy(synth.bag(n_tokens, DIM))
     ncpu = os.cpu_count() or torch.get_num_threads()
-    cands = sorted({c for c in (ncpu, ncpu // 2, ncpu // 4, 32, 16, 8) if 1 <= c <= ncpu}, reverse=True)
+    # the probe stays within the CPUs this process is given (its affinity mask, and OMP_NUM_THREADS where the host sets one):
+    # on a shared host the whole machine's count is not this process's to use
+    avail = min(len(os.sched_getaffinity(0)), int(os.environ.get("OMP_NUM_THREADS") or ncpu))
+    cands = sorted({c for c in (avail, avail // 2, avail // 4, 32, 16, 8) if 1 <= c <= avail}, reverse=True)
     probe = {}
     for c in cands:
         torch.set_num_threads(c)
@@ -369,12 +383,18 @@ class StubWorkload:
         return dict(region_num=e["region_num"], epeg_k=e["epeg_k"], crmsa_k=e["crmsa_k"])
 
     def step(self, i, timed):
+        self.sums = []
         for b in self.mine:
             x = self.torch.full((max(1, self.sizes[b] // 1000), 64), 1.0 / 64)
-            self.acc += float((x @ self.w).sum())
+            self.sums.append(float((x @ self.w).sum()))
+        self.acc += sum(self.sums)
 
     def sync(self):
         pass
+
+    def outputs(self, budget, i):
+        import numpy as np
+        return {"bag_sums": np.array(self.sums, dtype=np.float64)} if self.mine else {}
 
     def finish(self, args, world, rank, elapsed):
         return {}
@@ -557,6 +577,20 @@ class EncoderWorkload:
     def sync(self):
         self.torch.cuda.synchronize()
 
+    def outputs(self, budget, i):
+        """What step i handed its caller: the classifier's logits of the last bag on every stream; the encoder's outputs of
+        the step's bags (forward_bags: one per bag of the call; raw loop: the buffers the step wrote), sampled to `budget`."""
+        if self.mil is not None:
+            return {"logits": self.torch.stack(self.outs).cpu().numpy()}
+        if self.via == "forward_bags":
+            outs = self.call_outs
+        elif self.fresh:
+            bis = [((i * self.Rr + r_) * self.S + s_) % len(self.bags) for r_ in range(self.Rr) for s_ in range(self.S)]
+            outs = [self.outs_raw[b] for b in dict.fromkeys(bis)]
+        else:
+            outs = self.outs_raw
+        return {"y": sample_rows(outs, budget)}
+
     def isolated_fused_ms(self, reps=10):
         """the dominant kernel alone on the chip (one bag in flight), untimed pass"""
         import numpy as np
@@ -687,7 +721,7 @@ class EncoderWorkload:
         torch = self.torch
         for o in (self.call_outs if self.via == "forward_bags" else self.outs):
             assert torch.isfinite(o).all()
-        if rank != 0:
+        if rank != 0 or not args.full:
             return {}
         rec = {}
         raw_elapsed = elapsed
@@ -842,10 +876,14 @@ class MixWorkload:
     def sync(self):
         self.torch.cuda.synchronize()
 
+    def outputs(self, budget, i):
+        """What a step handed its caller: the output of every bag of this rank, sampled to `budget`."""
+        return {"y": sample_rows(self.outs, budget)} if self.bags else {}
+
     def finish(self, args, world, rank, elapsed):
         for o in self.outs:
             assert self.torch.isfinite(o).all()
-        if rank != 0 or not self.bags:
+        if rank != 0 or not self.bags or not args.full:
             return {}
         # the R-MSA core kernel of every bag of this rank, one bag in flight, untimed: sum of the algorithmic FLOPs over the
         # sum of the launches' durations (HIP events recorded by the library around the kernel)
@@ -894,6 +932,38 @@ class MixWorkload:
                                      "avg_launch_ms and traffic are means per launch"}}
 
 
+# ------------------------------------------------------------------------------------ --dump-outputs
+def sample_index(n, m):
+    """m increasing row indices of a bag of n >= m rows: the k-th from the k-th of m equal slices, at a fixed seeded offset
+    inside it -- every part of the bag is covered, the same rows on every run (all n rows when m == n)."""
+    import numpy as np
+    u = np.random.RandomState(2021).random_sample(m)
+    k = np.arange(m)
+    lo, hi = k * n // m, (k + 1) * n // m
+    return lo + (u * (hi - lo)).astype(np.int64)
+
+
+def sample_rows(outs, budget):
+    """[len(outs), m, D] float32 on the host: rows sample_index(n, m) of every [n, D] output, m as large as `budget` bytes
+    allow (all rows when they fit)."""
+    import torch
+    D = outs[0].shape[-1]
+    m = max(1, min(min(o.shape[0] for o in outs), budget // (len(outs) * D * 4)))
+    rows = [o[torch.from_numpy(sample_index(o.shape[0], m)).to(o.device)] for o in outs]
+    return torch.stack(rows).float().cpu().numpy()
+
+
+def dump_outputs(wl, out_dir, last_step, rank, world):
+    """--dump-outputs: the arrays the last timed step handed its caller, as out_dir/<name>.npy (<name>_rank<r>.npy with
+    several ranks), float32 / float64, at most DUMP_BYTES of array data over all files and ranks."""
+    import numpy as np
+    budget = DUMP_BYTES // world
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in wl.outputs(budget, last_step).items():
+        assert a.dtype in (np.float32, np.float64) and a.nbytes <= budget, (name, a.dtype, a.nbytes)
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------ the rank program
 def stabilise(wl, steps_hint, max_s=3.0, min_s=0.4):
     """Untimed: run probes of a few steps until three consecutive probe rates agree within 3 % (clock ramp,
@@ -928,8 +998,15 @@ def main():
     ap.add_argument("--dtype", choices=("f32", "bf16", "f16", "f32x3"), default=None,
                     help="override the config's arithmetic (f32x3: the two big projections emulated in fp32 on the bf16 "
                          "matrix cores, RRT_COMPUTE_F32X3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the informational extra records of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else this file measures: spread repeats, rooflines, kernel table, "
+                         "extra records (config 1: other precisions and configs, module call, fresh inputs, H2D, training) "
+                         "and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, a fixed sample of rows when "
+                         "the outputs exceed 48 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the informational extra records")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("RRT_BENCH_STREAMS", "0")),
                     help="bags in flight per GPU (one HIP stream + workspace each); a step = this many bags.  Default: 4 "
                          "(3 for bf16 / fp16 bags of > 12 k tokens and the configs[4] mix: measured optima, see main())")
@@ -944,7 +1021,7 @@ def main():
                          "rounds 1-5) instead of RRTEncoder.forward_bags")
     ap.add_argument("--stub-cpu", action="store_true", help="rank logic only: CPU stand-in workload over gloo (tests)")
     ap.add_argument("--module-call-only", action="store_true",
-                    help="print only the `module_call` record of this config (the default run spawns this as a child process)")
+                    help="print only the `module_call` record of this config (a --full run spawns this as a child process)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1025,11 +1102,13 @@ def main():
     wl.sync()
     elapsed = time.perf_counter() - t0
     elapsed = sharding.max_over_ranks(elapsed, device=None if args.stub_cpu else dev)   # whole-job time = slowest rank
+    if args.dump_outputs:
+        dump_outputs(wl, args.dump_outputs, args.steps - 1, rank, world)
 
     # run-to-run spread: three more repeats of the same K steps, same bracketing, after the contract's timed region
     # (rank-local clocks, informational: `value` is the first region, the only one bracketed by the barriers' MAX)
     spread = []
-    if not args.stub_cpu:
+    if not args.stub_cpu and args.full:
         for _ in range(3):
             wl.sync()
             ts = time.perf_counter()
@@ -1091,19 +1170,20 @@ def main():
         rec.update(rec_extra)
         if whole_path is not None:
             rec["whole_path"] = whole_path
-        if not args.stub_cpu and world == 1 and cfg["kind"] == "encoder" and not args.no_extras:
+        full = args.full and not args.stub_cpu and world == 1
+        if full and cfg["kind"] == "encoder" and not args.no_extras:
             rec["module_call"] = module_call_record(args)
             if args.config == 1 and not args.dtype:      # the headline config also through the module in bf16 (the --amp path)
                 import copy
                 a16 = copy.copy(args)
                 a16.dtype = "bf16"
                 rec["module_call_bf16"] = module_call_record(a16)
-        if not args.stub_cpu and args.config == 1 and world == 1 and not args.no_extras:
+        if full and args.config == 1 and not args.no_extras:
             rec.update(extras(wl, dev))
             for c in (0, 2, 3, 4):
                 rec[f"config{c}"] = config_record(c)
             rec["fresh_inputs"] = fresh_inputs_record(rec)
-        if not args.stub_cpu and world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             n_cpu = cfg["n"] or 9000          # config 4: the typical bag of the mix
             rec["cpu_baseline"] = cpu_baseline(n_cpu, enc_cfg)
         print(json.dumps(rec), flush=True)
@@ -1285,7 +1365,7 @@ def module_call_record(args):
 
 
 def config_record(c):
-    """A bounded single-GPU record of BASELINE configs[c] inside the default run (rank 0, after the timed region):
+    """A bounded single-GPU record of BASELINE configs[c] inside a --full run (rank 0, after the timed region):
     `bench.py --config c` with a short timed region, run as a CHILD PROCESS while this one idles -- HIP maps streams to
     hardware queues in creation order, and a process that has already created this run's streams (four bags in flight, the
     feeder's copy stream, the executor's own) no longer gives a new workload the queues a fresh process gets (measured:
@@ -1294,7 +1374,7 @@ def config_record(c):
     steps = {0: 100, 2: 30, 3: 12, 4: 12}[c]        # (configs 0-3: a step = streams x 4 bags)
     t0 = time.perf_counter()
     cmd = [sys.executable, os.path.abspath(__file__), "--config", str(c), "--steps", str(steps), "--warmup", "5",
-           "--no-extras", "--no-cpu-baseline"]
+           "--full", "--no-extras", "--no-cpu-baseline"]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
         r = json.loads(out.stdout.strip().splitlines()[-1])
@@ -1351,7 +1431,7 @@ def fresh_inputs_record(rec):
 
 
 def extras(wl, dev):
-    """Informational records of the default run (rank 0, after the timed region; none is the headline value)."""
+    """Informational records of a --full run (rank 0, after the timed region; none is the headline value)."""
     import torch
     from rrt_mil_amd import RRTEncoder, RRTMIL, _lib, synth
     out = {}

@@ -1,6 +1,6 @@
 """CPU: the C-ABI library loads and exports every symbol include/rrt_hip.h declares;
 host-only entry points (geometry, workspace size, error strings) behave; the Python
-boundary mirrors the reference's constructor / state_dict surface.  No GPU compute."""
+boundary mirrors the reference's constructor / state_dict surface.  No GPU compute, on a machine with a GPU too."""
 import ctypes as C
 import inspect
 import os
@@ -156,34 +156,58 @@ def test_weight_fingerprint_covers_every_parameter(n_layers):
     assert enc._weights().crmsa.qkv_w == enc.cr_msa.attn.attn.qkv.weight.data_ptr()
 
 
+# The body of test_workspace_queries_cover_what_the_forwards_check, run in a child process that sees no GPU: its forward calls
+# take HOST pointers, and on a machine with a GPU a call that passes validation would launch kernels on them.  HIP drops every
+# HIP_VISIBLE_DEVICES index from the first invalid one on, so "-1" hides all devices; the child asks the HIP runtime the
+# library is bound to and stops before its first call if that runtime reports a device anyway.
+_WORKSPACE_CHILD = r"""
+import ctypes as C, json, sys
+sys.path.insert(0, sys.argv[1])
+import torch
+from rrt_mil_amd import RRTEncoder, _lib
+lib = _lib.load()
+n_dev = C.c_int(-1)
+C.CDLL(_lib.LIB_PATH).hipGetDeviceCount(C.byref(n_dev))
+if n_dev.value != 0 or torch.cuda.device_count() != 0:
+    sys.exit(f"a GPU is visible ({n_dev.value} devices): the host-pointer forward calls must not run")
+enc = RRTEncoder(mlp_dim=512, **json.loads(sys.argv[2]))
+d, w = enc._desc, enc._weights()
+n = 700
+x, y = torch.zeros(2, n, 512), torch.zeros(2, n, 512)
+for mode in (_lib.COMPUTE_F32, _lib.COMPUTE_BF16, _lib.COMPUTE_F32X3):
+    d.compute = mode
+    need = C.c_size_t()
+    assert lib.rrt_encoder_workspace_size(C.byref(d), n, C.byref(need)) == 0
+    buf = (C.c_char * need.value)()
+    rc = lib.rrt_encoder_forward_f32(C.byref(d), C.byref(w), x.data_ptr(), y.data_ptr(), n, C.addressof(buf), need.value, None)
+    assert rc > 0 or rc == 0, (mode, rc)
+    assert lib.rrt_encoder_forward_f32(C.byref(d), C.byref(w), x.data_ptr(), y.data_ptr(), n, C.addressof(buf),
+                                       need.value - 1, None) == -3
+    assert lib.rrt_encoder_batch_workspace_size(C.byref(d), 2, n, C.byref(need)) == 0
+    buf = (C.c_char * need.value)()
+    rc = lib.rrt_encoder_forward_batch_f32(C.byref(d), C.byref(w), x.data_ptr(), y.data_ptr(), 2, n, C.addressof(buf),
+                                           need.value, None)
+    assert rc > 0 or rc == 0, (mode, rc)
+    assert lib.rrt_encoder_forward_batch_f32(C.byref(d), C.byref(w), x.data_ptr(), y.data_ptr(), 2, n, C.addressof(buf),
+                                             need.value - 1, None) == -3
+print("workspace checks ok")
+"""
+
+
 @pytest.mark.parametrize("kw", [dict(), dict(ffn=True), dict(ffn=True, crmsa_mlp=True), dict(n_layers=1), dict(n_layers=3),
                                 dict(pos="ppeg", pos_pos=-1), dict(cr_msa=False), dict(epeg_2d=True), dict(epeg_type="value_bf")])
-def test_workspace_queries_cover_what_the_forwards_check(kw):
+def test_workspace_queries_cover_what_the_forwards_check(lib, kw):
     """The size a workspace query returns is the size the forward checks its workspace against -- for the single-bag entry
     point and the batch one (round 4: with ffn = 1 the batch carve handed the inner forward the REAL size of the single-bag
-    carve, which is smaller than the queried one it checks).  No GPU here: a call that passes validation fails at its first
-    launch with a HIP error (> 0); a sizing bug shows up as RRT_E_WORKSPACE (-3) before anything is launched."""
-    lib = _lib.load()
-    enc = RRTEncoder(mlp_dim=512, **kw)
-    d, w = enc._desc, enc._weights()
-    n = 700
-    x, y = torch.zeros(2, n, 512), torch.zeros(2, n, 512)
-    for mode in (_lib.COMPUTE_F32, _lib.COMPUTE_BF16, _lib.COMPUTE_F32X3):
-        d.compute = mode
-        need = C.c_size_t()
-        assert lib.rrt_encoder_workspace_size(C.byref(d), n, C.byref(need)) == 0
-        buf = (C.c_char * need.value)()
-        rc = lib.rrt_encoder_forward_f32(C.byref(d), C.byref(w), x.data_ptr(), y.data_ptr(), n, C.addressof(buf), need.value, None)
-        assert rc > 0 or rc == 0, (mode, rc)
-        assert lib.rrt_encoder_forward_f32(C.byref(d), C.byref(w), x.data_ptr(), y.data_ptr(), n, C.addressof(buf),
-                                           need.value - 1, None) == -3
-        assert lib.rrt_encoder_batch_workspace_size(C.byref(d), 2, n, C.byref(need)) == 0
-        buf = (C.c_char * need.value)()
-        rc = lib.rrt_encoder_forward_batch_f32(C.byref(d), C.byref(w), x.data_ptr(), y.data_ptr(), 2, n, C.addressof(buf),
-                                               need.value, None)
-        assert rc > 0 or rc == 0, (mode, rc)
-        assert lib.rrt_encoder_forward_batch_f32(C.byref(d), C.byref(w), x.data_ptr(), y.data_ptr(), 2, n, C.addressof(buf),
-                                                 need.value - 1, None) == -3
+    carve, which is smaller than the queried one it checks).  No GPU in the child that makes the calls (_WORKSPACE_CHILD):
+    a call that passes validation fails at its first launch with a HIP error (> 0); a sizing bug shows up as
+    RRT_E_WORKSPACE (-3) before anything is launched."""
+    import json
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, "-c", _WORKSPACE_CHILD, ROOT, json.dumps(kw)], capture_output=True, text=True,
+                         timeout=300, env=dict(os.environ, HIP_VISIBLE_DEVICES="-1"))
+    assert out.returncode == 0 and "workspace checks ok" in out.stdout, out.stderr[-3000:]
 
 
 def test_executor_argument_checks_need_no_gpu():

@@ -6,7 +6,7 @@ R=$PWD
 OUT=$R/gpurun_out
 mkdir -p $OUT
 export RRT_HIP_LIB=$R/tools/_abl/librrt_tune.so
-X="--no-cpu-baseline --no-extras"
+X="--full --no-cpu-baseline --no-extras"
 : > $OUT/${TAG}_proj.txt
 for rep in 1 2; do
   for S in 1 2 4; do

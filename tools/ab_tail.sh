@@ -14,7 +14,7 @@ for v in $VARIANTS; do
   name=${v%%:*}; envs=${v#*:}
   rm -rf /tmp/prof_$name
   ( for e in ${envs//,/ }; do export $e; done
-    timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o p -- python $R/bench.py $ARGS --no-cpu-baseline --no-extras > /tmp/p_$name.json 2>/tmp/p_$name.err )
+    timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o p -- python $R/bench.py $ARGS --full --no-cpu-baseline --no-extras > /tmp/p_$name.json 2>/tmp/p_$name.err )
   python $R/tools/rocprof_summary.py /tmp/prof_$name/p_results.db > $OUT/${TAG}_${name}.kernel_stats.txt
   echo "== $name ($envs)"
   head -10 $OUT/${TAG}_${name}.kernel_stats.txt | cut -c1-60,96-150

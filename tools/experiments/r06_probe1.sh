@@ -2,7 +2,7 @@
 # round 6, first probe on the GPU box: (1) fresh vs cycled inputs through the raw C-ABI loop, (2) forward_bags by caller stream /
 # outputs, (3) the all-no-packed-fp32 build, (4) the training step's kernel table.   -> gpurun_out/r06_probe1.txt
 R=$PWD; OUT=$R/gpurun_out/r06_probe1.txt; : > $OUT
-X="--no-cpu-baseline --no-extras"
+X="--full --no-cpu-baseline --no-extras"
 line() { python -c "import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', r['value'], r['ms_per_step'], (r.get('value_spread') or {}).get('values'), (r.get('one_bag_in_flight') or {}).get('ms_per_bag'), r['config'].get('fresh_inputs'))" >> $OUT; }
 for dt in f32 bf16; do
   timeout 200 python bench.py --dtype $dt $X 2>/dev/null | line "raw $dt cycled"

@@ -5,7 +5,7 @@ export RRT_HIP_LIB=$R/tools/_abl/librrt_tune.so
 run() {  # label, env assignments...
   lbl=$1; shift
   ( for kv in "$@"; do export "$kv"; done
-    timeout 300 python bench.py --dtype bf16 --streams 4 --steps 12 --warmup 3 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+    timeout 300 python bench.py --dtype bf16 --streams 4 --steps 12 --warmup 3 --full --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lbl', r['value'], r['value_spread']['values'])" )
 }
 : > $OUT/r06_p13_ab.txt

@@ -6,7 +6,7 @@ run() {  # label, args, env...
   lbl=$1; a=$2; shift 2
   ( for kv in "$@"; do export "$kv"; done
     export RRT_HIP_LIB=$R/tools/_abl/librrt_tune.so
-    timeout 300 python bench.py $a --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+    timeout 300 python bench.py $a --full --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lbl', r['value'], r['value_spread']['values'], (r.get('one_bag_in_flight') or {}).get('ms_per_bag'))" )
 }
 : > $OUT/r06_p16_ab.txt
@@ -21,6 +21,6 @@ done
 cat $OUT/r06_p16_ab.txt
 cd /tmp; export TMPDIR=/tmp
 for v in gpr old; do
-  rm -rf /tmp/prof_x; ( [ $v = old ] && export RRT_NO_REGION4_GPR=1; RRT_HIP_LIB=$R/tools/_abl/librrt_tune.so timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_x -o p -- python $R/bench.py --dtype bf16 --streams 1 --steps 40 --no-cpu-baseline --no-extras > /tmp/p.log 2>&1 )
+  rm -rf /tmp/prof_x; ( [ $v = old ] && export RRT_NO_REGION4_GPR=1; RRT_HIP_LIB=$R/tools/_abl/librrt_tune.so timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_x -o p -- python $R/bench.py --dtype bf16 --streams 1 --steps 40 --full --no-cpu-baseline --no-extras > /tmp/p.log 2>&1 )
   python $R/tools/rocprof_summary.py /tmp/prof_x/p_results.db | grep "crmsa_region4" | cut -c1-60,96-140 | sed "s/^/$v /"
 done

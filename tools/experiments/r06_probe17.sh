@@ -5,7 +5,7 @@ run() {  # label, args, env...
   lbl=$1; a=$2; shift 2
   ( for kv in "$@"; do export "$kv"; done
     export RRT_HIP_LIB=$R/tools/_abl/librrt_tune.so
-    timeout 300 python bench.py $a --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+    timeout 300 python bench.py $a --full --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lbl', r['value'], r['value_spread']['values'], (r.get('one_bag_in_flight') or {}).get('ms_per_bag'))" )
 }
 : > $OUT/r06_p17_ab.txt

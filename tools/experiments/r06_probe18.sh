@@ -6,7 +6,7 @@ run() {  # label, args, env...
   lbl=$1; a=$2; shift 2
   ( for kv in "$@"; do export "$kv"; done
     export RRT_HIP_LIB=$R/tools/_abl/librrt_tune.so
-    timeout 300 python bench.py $a --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+    timeout 300 python bench.py $a --full --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lbl', r['value'], r['value_spread']['values'], (r.get('one_bag_in_flight') or {}).get('ms_per_bag'))" )
 }
 : > $OUT/r06_p18_ab.txt
@@ -19,5 +19,5 @@ for rep in 1 2 3; do
 done
 cat $OUT/r06_p18_ab.txt
 cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/prof_x
-RRT_HIP_LIB=$R/tools/_abl/librrt_tune.so timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_x -o p -- python $R/bench.py --dtype f32 --streams 2 --steps 6 --warmup 2 --no-cpu-baseline --no-extras > /tmp/p.log 2>&1
+RRT_HIP_LIB=$R/tools/_abl/librrt_tune.so timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_x -o p -- python $R/bench.py --dtype f32 --streams 2 --steps 6 --warmup 2 --full --no-cpu-baseline --no-extras > /tmp/p.log 2>&1
 python $R/tools/rocprof_summary.py /tmp/prof_x/p_results.db | grep "crmsa_" | cut -c1-60,96-140

@@ -9,6 +9,6 @@ bash tools/experiments/ab_lib.sh "base lean3" --config 2 --steps 100 --warmup 5 
 cat $OUT/r06_p21_ab.txt
 cd /tmp; export TMPDIR=/tmp
 for lib in base lean3; do
-  rm -rf /tmp/prof_x; RRT_HIP_LIB=$R/tools/_abl/librrt_$lib.so timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_x -o p -- python $R/bench.py --dtype bf16 --streams 1 --steps 40 --no-cpu-baseline --no-extras > /tmp/p.log 2>&1
+  rm -rf /tmp/prof_x; RRT_HIP_LIB=$R/tools/_abl/librrt_$lib.so timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_x -o p -- python $R/bench.py --dtype bf16 --streams 1 --steps 40 --full --no-cpu-baseline --no-extras > /tmp/p.log 2>&1
   python $R/tools/rocprof_summary.py /tmp/prof_x/p_results.db | grep "rmsa_pair16" | cut -c1-60,96-140 | sed "s/^/$lib /"
 done

@@ -3,7 +3,7 @@
 # qkv projection, O16 into the out-projection): same-box A/B of four builds, bags in flight (bf16 N = 9000, configs 2-4)
 R=$PWD; OUT=$R/gpurun_out; mkdir -p $OUT
 run() { lbl=$1; lib=$2; a=$3; ( [ -n "$lib" ] && export RRT_HIP_LIB=$R/tools/_abl/librrt_$lib.so
-    timeout 300 python bench.py $a --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+    timeout 300 python bench.py $a --full --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lbl', r['value'], r['value_spread']['values'])" ); }
 : > $OUT/r06_p24_ab.txt
 for rep in 1 2 3; do

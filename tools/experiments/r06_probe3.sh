@@ -2,7 +2,7 @@
 # round 6, third probe: the streaming CR-MSA pair for large regions (crmsa_logits512 / crmsa_combine512): tests, A/B, kernel table
 R=$PWD; OUT=$R/gpurun_out; mkdir -p $OUT
 timeout 900 python -m pytest tests -m gpu -x -q -k "crmsa or logits or combine or golden or config4 or G4 or G16 or G19" 2>&1 | tail -4 > $OUT/r06_p3_tests.txt; cat $OUT/r06_p3_tests.txt
-X="--no-cpu-baseline --no-extras"
+X="--full --no-cpu-baseline --no-extras"
 line() { python -c "import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', r['value'], r['ms_per_step'], (r.get('value_spread') or {}).get('values'), (r.get('one_bag_in_flight') or {}).get('ms_per_bag'))" >> $OUT/r06_p3_lines.txt; }
 for rep in 1 2; do
   for old in 0 1; do

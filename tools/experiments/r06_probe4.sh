@@ -1,7 +1,7 @@
 #!/bin/bash
 R=$PWD; OUT=$R/gpurun_out; mkdir -p $OUT; rm -f $OUT/r06_p4_lines.txt
 timeout 900 python -m pytest tests -m gpu -x -q -k "crmsa or logits or combine or feeder or config4 or forward_bags" 2>&1 | tail -8 > $OUT/r06_p4_tests.txt; cat $OUT/r06_p4_tests.txt
-X="--no-cpu-baseline --no-extras"
+X="--full --no-cpu-baseline --no-extras"
 line() { python -c "import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', r['value'], r['ms_per_step'], (r.get('value_spread') or {}).get('values'), (r.get('one_bag_in_flight') or {}).get('ms_per_bag'))" >> $OUT/r06_p4_lines.txt; }
 for rep in 1 2; do
   for old in 0 1; do

@@ -3,7 +3,7 @@
 # against RRT_NO_CRMSA_STREAM4=1 (tuning switch: needs a tuning build -> here the A/B is new build vs the numbers of r06a), kernel table
 R=$PWD; OUT=$R/gpurun_out; mkdir -p $OUT
 timeout 1200 python -m pytest tests -m gpu -x -q -k "pair16 or fused16 or crmsa or golden or config4 or autocast or bags_in_flight" 2>&1 | tail -6 > $OUT/r06_p5_tests.txt; cat $OUT/r06_p5_tests.txt
-X="--no-cpu-baseline --no-extras"
+X="--full --no-cpu-baseline --no-extras"
 line() { python -c "import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', r['value'], r['ms_per_step'], (r.get('value_spread') or {}).get('values'), (r.get('one_bag_in_flight') or {}).get('ms_per_bag'), json.dumps(r.get('whole_path'))[:400])"; }
 cd /tmp; export TMPDIR=/tmp
 for rep in 1 2; do

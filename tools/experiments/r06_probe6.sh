@@ -2,7 +2,7 @@
 # round 6, probe 6: the merged 16-bit launch (rmsa_pair16 PROJ): bit-identity tests, config 3 lines, kernel table
 R=$PWD; OUT=$R/gpurun_out; mkdir -p $OUT
 timeout 1200 python -m pytest tests -m gpu -x -q -k "${1:-pair16}" 2>&1 | tail -6 > $OUT/r06_p6_tests.txt; cat $OUT/r06_p6_tests.txt
-X="--no-cpu-baseline --no-extras"
+X="--full --no-cpu-baseline --no-extras"
 line() { python -c "import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', r['value'], r['ms_per_step'], (r.get('value_spread') or {}).get('values'), (r.get('one_bag_in_flight') or {}).get('ms_per_bag'))"; }
 cd /tmp; export TMPDIR=/tmp
 : > $OUT/r06_p6_lines.txt

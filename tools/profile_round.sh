@@ -12,7 +12,7 @@ OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_* /tmp/pmc_*
-X="--no-cpu-baseline --no-extras"
+X="--full --no-cpu-baseline --no-extras"
 rm -f $OUT/${TAG}_traffic.json
 for spec in "c1_f32:--config 1 --dtype f32" "c1_bf16:--config 1 --dtype bf16" "c1_f32x3:--config 1 --dtype f32x3" \
             "c2_bf16:--config 2" "c3_bf16:--config 3" "c4_bf16:--config 4"; do
@@ -48,13 +48,13 @@ for dt in f32 bf16; do
     fi
   done
 done
-timeout 900 python $R/bench.py > $OUT/${TAG}_bench_default.bench.json 2> /tmp/bench.err || tail -5 /tmp/bench.err
+timeout 900 python $R/bench.py --full > $OUT/${TAG}_bench_default.bench.json 2> /tmp/bench.err || tail -5 /tmp/bench.err
 timeout 600 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench_driver_cmd.bench.json 2>/dev/null
-for c in 2 3 4; do timeout 300 python $R/bench.py --config $c --no-cpu-baseline --steps 100 > $OUT/${TAG}_bench_config$c.bench.json 2>/dev/null; done
-timeout 300 python $R/bench.py --dtype bf16 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_config1_bf16.bench.json 2>/dev/null
-timeout 300 python $R/bench.py --dtype f32x3 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_config1_f32x3.bench.json 2>/dev/null
-timeout 300 python $R/bench.py --streams 1 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_1stream.bench.json 2>/dev/null
-timeout 300 python $R/bench.py --streams 2 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_2streams.bench.json 2>/dev/null
+for c in 2 3 4; do timeout 300 python $R/bench.py --config $c --full --no-cpu-baseline --steps 100 > $OUT/${TAG}_bench_config$c.bench.json 2>/dev/null; done
+timeout 300 python $R/bench.py --dtype bf16 --full --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_config1_bf16.bench.json 2>/dev/null
+timeout 300 python $R/bench.py --dtype f32x3 --full --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_config1_f32x3.bench.json 2>/dev/null
+timeout 300 python $R/bench.py --streams 1 --full --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_1stream.bench.json 2>/dev/null
+timeout 300 python $R/bench.py --streams 2 --full --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_2streams.bench.json 2>/dev/null
 : > $OUT/${TAG}_streams_sweep.txt
 for S in 1 2 3 4 5 6 8; do
   timeout 200 python $R/bench.py --streams $S $X 2>/dev/null | python -c "import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('fp32 N=9000 streams=$S', r['value'], 'slides/s', r['ms_per_step'], 'ms/step', (r.get('value_spread') or {}).get('values'))" >> $OUT/${TAG}_streams_sweep.txt

@@ -13,7 +13,7 @@ else
 fi
 cat $OUT/${TAG}_tests.txt
 cd /tmp && export TMPDIR=/tmp
-X="--no-cpu-baseline --no-extras"
+X="--full --no-cpu-baseline --no-extras"
 for spec in "f32:--dtype f32" "bf16:--dtype bf16" "c3:--config 3 --steps 60" "c4:--config 4 --steps 30" "c2:--config 2 --steps 100"; do
   name=${spec%%:*}; args=${spec#*:}
   timeout 300 python $R/bench.py $args $X > $OUT/${TAG}_bench_$name.json 2>/tmp/err_$name.log || tail -3 /tmp/err_$name.log

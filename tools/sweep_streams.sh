@@ -5,7 +5,7 @@ DT=${2:-f32}
 R=$PWD
 OUT=$R/gpurun_out
 mkdir -p $OUT
-X="--no-cpu-baseline --no-extras"
+X="--full --no-cpu-baseline --no-extras"
 : > $OUT/${TAG}_streams_sweep.txt
 for S in 1 2 3 4 5 6 8; do
   for gate in 0 1; do

@@ -506,7 +506,9 @@ int rrt_executor_destroy(rrt_executor *ex);
 /* Region attention backward (rmsa.py:103-122): qkv [n_regions*P, 3*dim] as the forward stage wrote it (q scaled),
  * o = the forward output, d_o its gradient  ->  d_qkv (gradient w.r.t. the qkv linear's raw output, same layout)
  * and d_pe_w [heads, epeg_k] (NULL allowed; the conv bias gradient is exactly zero).  Head dim 64: any P (<= 208: one resident kernel; larger: a streaming four-kernel variant);
- * other head dims: no EPEG and P <= 128.  workspace: rrt_region_attention_backward_workspace_size bytes. */
+ * other multiples of 16 up to 256: any P and epeg_k <= 63 (the streaming variant at that head dim; without EPEG on P <= 128 the
+ * VALU kernel below); any other multiple of 4: no EPEG and P <= 128 (a VALU kernel).  workspace:
+ * rrt_region_attention_backward_workspace_size bytes. */
 int rrt_region_attention_backward_workspace_size(int32_t n_regions, int32_t P, int32_t dim, int32_t heads,
                                                  int32_t epeg_k, size_t *bytes);
 int rrt_region_attention_backward_f32(const float *qkv, const float *pe_w, const float *o, const float *d_o,
@@ -535,8 +537,9 @@ int rrt_linear_backward_f32(const float *dY, const float *X, const float *W, flo
 
 /* ---- row f2: training.  Forward that stashes what the backward needs, and the backward itself ----
  * Supported: the default path (1-D 'attn' EPEG R-MSA layers, CR-MSA with the phi matrix or the MLP phi,
- * all_shortcut), head dim 64 in R-MSA (any multiple of 4 in CR-MSA's inner attention), bags of any size, dim <= 1024,
- * F32 compute.  Anything else: RRT_E_UNSUPPORTED.
+ * all_shortcut), an R-MSA head dim that is a multiple of 16 up to 256 (any other multiple of 4 without EPEG on regions of
+ * <= 128 tokens; any multiple of 4 in CR-MSA's inner attention), bags of any size, dim <= 1024, F32 compute.  Anything
+ * else: RRT_E_UNSUPPORTED.
  * drop_p / drop_seed: the train-mode proj_drop of every InnerAttention (rmsa.py:70,132; p = drop_out): a stateless
  * mask, element kept iff hash(seed, layer, index) >= p * 2^32, kept values scaled by 1/(1-p); the backward call
  * must receive the same (drop_p, drop_seed) as its forward.  drop_p = 0: no dropout.

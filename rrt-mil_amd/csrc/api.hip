@@ -1795,7 +1795,8 @@ int rrt_region_attention_backward_f32(const float* qkv, const float* pe_w, const
   const int ek = pe_w ? epeg_k : 0;
   if (ek > 0 && ek % 2 == 0) return unsupported("epeg_k must be odd");
   if (!attn_bwd_supported(P, dim, heads, ek))
-    return unsupported("attention backward: needs head dim 64 with P <= 208, or (no EPEG, P <= 128, head dim % 4 == 0)");
+    return unsupported("attention backward: needs a head dim that is a multiple of 16 up to 256 with epeg_k <= 63 (any P), "
+                       "or no EPEG, P <= 128 and a head dim that is a multiple of 4");
   if (!workspace || workspace_bytes < attn_bwd_workspace(n_regions, P, dim, heads, ek)) return RRT_E_WORKSPACE;
   return (int)launch_attention_backward(qkv, pe_w, o, d_o, d_qkv, d_pe_w, (float*)workspace, n_regions, P, dim,
                                         heads, ek, (hipStream_t)stream);
@@ -2025,7 +2026,7 @@ int check_train(const rrt_encoder_desc* d, int64_t N, rrt_grid* g, rrt_grid* g8)
     const bool e2d = d->epeg && d->epeg_2d && d->epeg_type == RRT_EPEG_ATTN, evalue = d->epeg && d->epeg_type != RRT_EPEG_ATTN;
     // (the 2-D 'attn' EPEG has its own backward kernel, any head dim; the value variants run the plain attention backward)
     if (!e2d && !attn_bwd_supported(g->s * g->s, d->dim, d->n_heads, (d->epeg && !evalue) ? d->epeg_k : 0))
-      return unsupported("training: the R-MSA attention backward needs head dim 64 (any region size, epeg_k <= 63); other head dims only without EPEG on regions of <= 128 tokens, or with epeg_2d");
+      return unsupported("training: the R-MSA attention backward needs a head dim that is a multiple of 16 up to 256 (any region size, epeg_k <= 63); other head dims (not a multiple of 16, or above 256) only without EPEG on regions of <= 128 tokens, or with epeg_2d");
   }
   rc = rrt_region_grid(N, 8, 0, 0, 0.f, g8);
   if (rc) return rc;

@@ -719,15 +719,16 @@ hipError_t launch_bwd_mt(const float* qkv, const float* pe_w, const float* O, co
 //   adjoint:  dq = scale (I + T_w)^T dQ~ and the tap gradients, block = (region, head).
 constexpr int CK = 128, CT = CK / 16;     // chunk rows / row tiles per chunk
 
+template <int HDT>
 __global__ __launch_bounds__(256) void attn_stencil_kernel(const float* __restrict__ qkv, const float* __restrict__ pe_w,
                                                            float* __restrict__ qt, int P, int D, int heads,
                                                            int epeg_k, long n_rows) {
-  // thread = (row, 16-byte slot of one head): qt[row, head*64 + 4s ..] ; rows stay inside their region
+  // thread = (row, 16-byte slot of one head): qt[row, head*HDT + 4s ..] ; rows stay inside their region
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   const int slots = D / 4;
   if (idx >= n_rows * slots) return;
   const long row = idx / slots;
-  const int c = (int)(idx - row * slots) * 4, head = c / HD;
+  const int c = (int)(idx - row * slots) * 4, head = c / HDT;
   const int i = (int)(row % P);
   const int half = epeg_k >> 1;
   const float* w = pe_w + head * epeg_k;
@@ -945,23 +946,27 @@ __global__ __launch_bounds__(384) void attn_bwd_kv_kernel(const float* __restric
 }
 
 // dq = scale (I + T_w)^T dQ~ (dQ~ parked in the dq columns; staged through `tmp` so the in-place update never reads
-// a row it has already overwritten) and the tap-gradient partials.  Block = (region, head).
-__global__ __launch_bounds__(256) void attn_adjoint_kernel(const float* __restrict__ qkv, const float* __restrict__ pe_w,
+// a row it has already overwritten) and the tap-gradient partials.  Block = (region, head); thread = (row of a group of
+// RP rows, 16-byte slot of the head), threads past RP x SL idle (head dims 48, 96, ...).  NT threads: 256 at head dim <= 64,
+// 1024 above (one block per (region, head) holds a CU alone at P = 144: with four waves, 120 us at head dim 128).
+template <int HDT, int NT = (HDT <= 64 ? 256 : 1024)>
+__global__ __launch_bounds__(NT) void attn_adjoint_kernel(const float* __restrict__ qkv, const float* __restrict__ pe_w,
                                                            float* __restrict__ dqkv, float* __restrict__ tmp,
                                                            float* __restrict__ dpe_part, int P, int D, int heads,
                                                            int epeg_k, float q_scale) {
-  __shared__ float wred[4 * 64];
+  constexpr int SL = HDT / 4, RP = NT / SL;
+  __shared__ float wred[NT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int head = blockIdx.x, reg = blockIdx.y;
   const size_t row0 = (size_t)reg * P;
   const int ld = 3 * D, half = epeg_k >> 1;
   const float* w = pe_w + head * epeg_k;
-  const int s = tid & 15;
+  const int s = tid % SL, i_first = (RP * SL == NT || tid < RP * SL) ? tid / SL : P;
   // copy dQ~ rows of this (region, head) to tmp [rows, D] (head columns)
-  for (int i = tid >> 4; i < P; i += 16)
-    *(float4*)(tmp + (row0 + i) * D + head * HD + 4 * s) = *(const float4*)(dqkv + (row0 + i) * ld + head * HD + 4 * s);
+  for (int i = i_first; i < P; i += RP)
+    *(float4*)(tmp + (row0 + i) * D + head * HDT + 4 * s) = *(const float4*)(dqkv + (row0 + i) * ld + head * HDT + 4 * s);
   __syncthreads();
-  for (int i = tid >> 4; i < P; i += 16) {
+  for (int i = i_first; i < P; i += RP) {
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int t0 = -half; t0 <= half; t0 += 8) {    // dq_i = sum_j wt[i - j + half] dQ~_j ,  j = i + t ; 8 loads in flight
       float4 v[8];
@@ -971,14 +976,14 @@ __global__ __launch_bounds__(256) void attn_adjoint_kernel(const float* __restri
         const int t = t0 + u, j = i + t;
         const bool ok = t <= half && j >= 0 && j < P;
         wt[u] = ok ? ((epeg_k > 0 ? w[half - t] : 0.f) + (t == 0 ? 1.0f : 0.f)) : 0.f;
-        v[u] = ok ? *(const float4*)(tmp + (row0 + j) * D + head * HD + 4 * s) : make_float4(0.f, 0.f, 0.f, 0.f);
+        v[u] = ok ? *(const float4*)(tmp + (row0 + j) * D + head * HDT + 4 * s) : make_float4(0.f, 0.f, 0.f, 0.f);
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         acc.x += wt[u] * v[u].x; acc.y += wt[u] * v[u].y; acc.z += wt[u] * v[u].z; acc.w += wt[u] * v[u].w;
       }
     }
-    *(float4*)(dqkv + (row0 + i) * ld + head * HD + 4 * s) =
+    *(float4*)(dqkv + (row0 + i) * ld + head * HDT + 4 * s) =
         make_float4(acc.x * q_scale, acc.y * q_scale, acc.z * q_scale, acc.w * q_scale);
   }
   if (epeg_k > 0) {
@@ -987,14 +992,14 @@ __global__ __launch_bounds__(256) void attn_adjoint_kernel(const float* __restri
     float tacc[64];
 #pragma unroll
     for (int t = 0; t < 64; ++t) tacc[t] = 0.f;
-    for (int i = tid >> 4; i < P; i += 16) {
-      const float4 g4 = *(const float4*)(tmp + (row0 + i) * D + head * HD + 4 * s);
+    for (int i = i_first; i < P; i += RP) {
+      const float4 g4 = *(const float4*)(tmp + (row0 + i) * D + head * HDT + 4 * s);
 #pragma unroll
       for (int t = 0; t < 64; ++t) {
         if (t < epeg_k) {
           const int j = i + t - half;
           if (j >= 0 && j < P) {
-            const float4 q4 = *(const float4*)(qkv + (row0 + j) * ld + head * HD + 4 * s);
+            const float4 q4 = *(const float4*)(qkv + (row0 + j) * ld + head * HDT + 4 * s);
             tacc[t] += (g4.x * q4.x + g4.y * q4.y) + (g4.z * q4.z + g4.w * q4.w);
           }
         }
@@ -1008,9 +1013,13 @@ __global__ __launch_bounds__(256) void attn_adjoint_kernel(const float* __restri
       }
     }
     __syncthreads();
-    if (tid < epeg_k)
-      dpe_part[((size_t)reg * heads + head) * epeg_k + tid] =
-          (wred[tid] + wred[64 + tid]) + (wred[128 + tid] + wred[192 + tid]);
+    if (tid < epeg_k) {
+      float a = (wred[tid] + wred[64 + tid]) + (wred[128 + tid] + wred[192 + tid]);
+#pragma unroll
+      for (int wv = 4; wv < NT / 64; wv += 4)       // (NT = 1024) the further groups of four waves, in order
+        a += (wred[wv * 64 + tid] + wred[(wv + 1) * 64 + tid]) + (wred[(wv + 2) * 64 + tid] + wred[(wv + 3) * 64 + tid]);
+      dpe_part[((size_t)reg * heads + head) * epeg_k + tid] = a;
+    }
   }
 }
 
@@ -1126,6 +1135,327 @@ __global__ __launch_bounds__(512) void attn_adjoint_lds_kernel(const float* __re
   }
 }
 
+// ---- the streaming variant at the other head dims (16 .. 256, multiple of 16, not 64): the same four steps, the fragment
+// counts a template parameter.  Score side (S = Q~ K^T, dA = dO V^T): a lane holds NF = HD/16 float4 fragments of its row,
+// 16-byte slots 4c + lg, as above.  Apply side (dQ~, dK, dV): NF accumulators, lane lr owns columns NF lr .. NF lr + NF - 1
+// (read and written as float4 / float2 / float pieces).  LDS rows are padded to HD + 4 floats instead of XOR-swizzled (the
+// 16-slot swizzle does not cover 48 / 96 / ... columns): 16 rows at one slot land on 16 distinct 16-byte bank groups for
+// every head dim here.  Chunks of CT row tiles keep a chunk pair near 64 KB of LDS (two blocks per CU); the adjoint is the
+// global-buffer kernel above (the LDS form's two [256, HD] tiles do not fit past head dim 64).
+template <int HDT>
+struct StreamCfg {
+  static constexpr int NF = HDT / 16;
+  static constexpr int LDR = HDT + 4;
+  static constexpr int CT = 512 / HDT > 8 ? 8 : 512 / HDT < 2 ? 2 : 512 / HDT;
+  static constexpr int CK = 16 * CT;
+  static constexpr int NW = HDT >= 192 ? 4 : 6;                 // query / key tiles (waves) per block
+  static constexpr int VW = NF % 4 == 0 ? 4 : NF % 2 == 0 ? 2 : 1;   // apply-side piece width
+  static_assert(HDT % 16 == 0 && HDT >= 16 && HDT <= 256, "head dim");
+};
+
+template <int HDT, int N>
+__device__ __forceinline__ void hd_run_scores(const float* X, const float4 (&f)[HDT / 16], int lr, int lg, int t0,
+                                              f32x4 (&s)[N]) {
+  constexpr int LDR = StreamCfg<HDT>::LDR;
+#pragma unroll
+  for (int u = 0; u < N; ++u) s[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int c = 0; c < HDT / 16; ++c) {
+    float4 a[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) a[u] = *(const float4*)(X + ((t0 + u) * 16 + lr) * LDR + 4 * (4 * c + lg));
+#pragma unroll
+    for (int u = 0; u < N; ++u) s[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].x, f[c].x, s[u], 0, 0, 0);
+#pragma unroll
+    for (int u = 0; u < N; ++u) s[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].y, f[c].y, s[u], 0, 0, 0);
+#pragma unroll
+    for (int u = 0; u < N; ++u) s[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].z, f[c].z, s[u], 0, 0, 0);
+#pragma unroll
+    for (int u = 0; u < N; ++u) s[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].w, f[c].w, s[u], 0, 0, 0);
+  }
+}
+
+// o[c][r] += sum_{u, rows} p[u][r'] * X[16 (t0 + u) + 4 lg + r'][NF lr + c]
+template <int HDT, int N>
+__device__ __forceinline__ void hd_run_apply(const float* X, const f32x4 (&p)[N], int lr, int lg, int t0,
+                                             f32x4 (&o)[HDT / 16]) {
+  constexpr int NF = HDT / 16, LDR = StreamCfg<HDT>::LDR, VW = StreamCfg<HDT>::VW;
+#pragma unroll
+  for (int u = 0; u < N; ++u)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float* src = X + ((t0 + u) * 16 + 4 * lg + r) * LDR + NF * lr;
+      const float w = p[u][r];
+#pragma unroll
+      for (int c = 0; c < NF; c += VW) {
+        if constexpr (VW == 4) {
+          const float4 v = *(const float4*)(src + c);
+          o[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, v.x, o[c], 0, 0, 0);
+          o[c + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, v.y, o[c + 1], 0, 0, 0);
+          o[c + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, v.z, o[c + 2], 0, 0, 0);
+          o[c + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, v.w, o[c + 3], 0, 0, 0);
+        } else if constexpr (VW == 2) {
+          const float2 v = *(const float2*)(src + c);
+          o[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, v.x, o[c], 0, 0, 0);
+          o[c + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, v.y, o[c + 1], 0, 0, 0);
+        } else {
+          o[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, src[c], o[c], 0, 0, 0);
+        }
+      }
+    }
+}
+
+// row 4 lg + r of the apply-side accumulators (columns NF lr ..) -> dst[NF lr ..], scaled
+template <int HDT>
+__device__ __forceinline__ void hd_store_row(float* dst, const f32x4 (&o)[HDT / 16], int r, int lr, float scale) {
+  constexpr int NF = HDT / 16, VW = StreamCfg<HDT>::VW;
+  dst += NF * lr;
+#pragma unroll
+  for (int c = 0; c < NF; c += VW) {
+    if constexpr (VW == 4) *(float4*)(dst + c) = make_float4(o[c][r] * scale, o[c + 1][r] * scale, o[c + 2][r] * scale, o[c + 3][r] * scale);
+    else if constexpr (VW == 2) *(float2*)(dst + c) = make_float2(o[c][r] * scale, o[c + 1][r] * scale);
+    else dst[c] = o[c][r] * scale;
+  }
+}
+
+// rows [r0, r0 + CK) of a [.., stride]-strided tensor (head columns) -> padded LDS chunk; rows >= P: zeros
+template <int HDT>
+__device__ __forceinline__ void hd_load_chunk(float* dst, const float* src, size_t stride, size_t row0, int r0, int P,
+                                              int tid) {
+  using C = StreamCfg<HDT>;
+  constexpr int SL = HDT / 4;
+  for (int idx = tid; idx < C::CK * SL; idx += C::NW * 64) {
+    const int m = idx / SL, s = idx - m * SL;
+    const float4 v = (r0 + m < P) ? *(const float4*)(src + (row0 + r0 + m) * stride + 4 * s) : make_float4(0.f, 0.f, 0.f, 0.f);
+    *(float4*)(dst + m * C::LDR + 4 * s) = v;
+  }
+}
+
+// the score side's own fragments of row m (zeros past the region)
+template <int HDT>
+__device__ __forceinline__ void hd_row_frags(const float* base, size_t stride, int m, int P, int lg, float4 (&f)[HDT / 16]) {
+#pragma unroll
+  for (int c = 0; c < HDT / 16; ++c)
+    f[c] = m < P ? *(const float4*)(base + (size_t)m * stride + 4 * (4 * c + lg)) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// q pass: block = (head, region, NW query tiles)
+template <int HDT>
+__global__ __launch_bounds__(StreamCfg<HDT>::NW * 64) void attn_bwd_q_hd_kernel(
+    const float* __restrict__ qkv, const float* __restrict__ qt, const float* __restrict__ O, const float* __restrict__ dO,
+    float* __restrict__ dqkv, float* __restrict__ lse_g, float* __restrict__ dd_g, int P, int D, int heads) {
+  using C = StreamCfg<HDT>;
+  constexpr int NF = C::NF, CT = C::CT, CK = C::CK;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* Ks = (float*)smem;
+  float* Vs = Ks + CK * C::LDR;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, lg = lane >> 4;
+  const int head = blockIdx.x, reg = blockIdx.y;
+  const size_t row0 = (size_t)reg * P;
+  const int ld = 3 * D;
+  const int i0 = (blockIdx.z * C::NW + wave) * 16;
+  const bool active = i0 < P;
+  const int m = i0 + lr;
+  float4 fq[NF], fg[NF];
+  hd_row_frags<HDT>(qt + row0 * D + head * HDT, (size_t)D, m, P, lg, fq);
+  hd_row_frags<HDT>(dO + row0 * D + head * HDT, (size_t)D, m, P, lg, fg);
+  float dsum = 0.f;
+  if (m < P) {
+#pragma unroll
+    for (int c = 0; c < NF; ++c) {
+      const float4 o4 = *(const float4*)(O + (row0 + m) * D + head * HDT + 4 * (4 * c + lg));
+      dsum += (fg[c].x * o4.x + fg[c].y * o4.y) + (fg[c].z * o4.z + fg[c].w * o4.w);
+    }
+  }
+  dsum = sum_xor32(sum_xor16(dsum));
+  // sweep 1: online row max / sum over the key chunks
+  float mrun = NEG_BIG, lrun = 0.f;
+  for (int r0 = 0; r0 < P; r0 += CK) {
+    __syncthreads();
+    hd_load_chunk<HDT>(Ks, qkv + D + head * HDT, (size_t)ld, row0, r0, P, tid);
+    __syncthreads();
+    if (active) {
+      // the chunk's key tiles in runs of three; runs wholly past the region are skipped (block-uniform)
+      auto srun = [&](auto nc, const int t0) {
+        constexpr int N = decltype(nc)::value;
+        if (r0 + t0 * 16 >= P) return;
+        f32x4 s[N];
+        hd_run_scores<HDT, N>(Ks, fq, lr, lg, t0, s);
+        float cmax = NEG_BIG;
+#pragma unroll
+        for (int u = 0; u < N; ++u)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            if (r0 + (t0 + u) * 16 + 4 * lg + r >= P) s[u][r] = NEG_BIG;
+            cmax = fmaxf(cmax, s[u][r]);
+          }
+        cmax = max_xor32(max_xor16(cmax));
+        const float mnew = fmaxf(mrun, cmax);
+        float psum = 0.f;
+#pragma unroll
+        for (int u = 0; u < N; ++u)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) psum += __builtin_amdgcn_exp2f(s[u][r] - mnew);
+        psum = sum_xor32(sum_xor16(psum));
+        lrun = lrun * __builtin_amdgcn_exp2f(mrun - mnew) + psum;
+        mrun = mnew;
+      };
+#pragma unroll
+      for (int t0 = 0; t0 + 3 <= CT; t0 += 3) srun(std::integral_constant<int, 3>{}, t0);
+      if constexpr (CT % 3 == 1) srun(std::integral_constant<int, 1>{}, CT - 1);
+      if constexpr (CT % 3 == 2) srun(std::integral_constant<int, 2>{}, CT - 2);
+    }
+  }
+  const float lse = mrun + __builtin_amdgcn_logf(lrun);
+  // sweep 2: A, dA, dS, dQ~ += dS K
+  f32x4 dqt[NF];
+#pragma unroll
+  for (int c = 0; c < NF; ++c) dqt[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int r0 = 0; r0 < P; r0 += CK) {
+    __syncthreads();
+    hd_load_chunk<HDT>(Ks, qkv + D + head * HDT, (size_t)ld, row0, r0, P, tid);
+    hd_load_chunk<HDT>(Vs, qkv + 2 * D + head * HDT, (size_t)ld, row0, r0, P, tid);
+    __syncthreads();
+    if (active) {
+      auto krun = [&](auto nc, const int t0) {
+        constexpr int N = decltype(nc)::value;
+        if (r0 + t0 * 16 >= P) return;
+        f32x4 sc[N], da[N];
+        hd_run_scores<HDT, N>(Ks, fq, lr, lg, t0, sc);
+        hd_run_scores<HDT, N>(Vs, fg, lr, lg, t0, da);
+#pragma unroll
+        for (int u = 0; u < N; ++u)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const bool ok = r0 + (t0 + u) * 16 + 4 * lg + r < P;
+            const float p = ok ? __builtin_amdgcn_exp2f(sc[u][r] - lse) : 0.f;
+            sc[u][r] = p * (da[u][r] - dsum);
+          }
+        hd_run_apply<HDT, N>(Ks, sc, lr, lg, t0, dqt);
+      };
+#pragma unroll
+      for (int t0 = 0; t0 + 3 <= CT; t0 += 3) krun(std::integral_constant<int, 3>{}, t0);
+      if constexpr (CT % 3 == 1) krun(std::integral_constant<int, 1>{}, CT - 1);
+      if constexpr (CT % 3 == 2) krun(std::integral_constant<int, 2>{}, CT - 2);
+    }
+  }
+  if (active) {
+    if (lg == 0 && m < P) {
+      lse_g[(row0 + m) * heads + head] = lse;
+      dd_g[(row0 + m) * heads + head] = dsum;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = i0 + 4 * lg + r;
+      if (i < P) hd_store_row<HDT>(dqkv + (row0 + i) * ld + head * HDT, dqt, r, lr, 1.0f);
+    }
+  }
+}
+
+// kv pass: block = (head, region, NW key tiles); one sweep over the query chunks (Q~, dO, lse, D in LDS)
+template <int HDT>
+__global__ __launch_bounds__(StreamCfg<HDT>::NW * 64) void attn_bwd_kv_hd_kernel(
+    const float* __restrict__ qkv, const float* __restrict__ qt, const float* __restrict__ dO, const float* __restrict__ lse_g,
+    const float* __restrict__ dd_g, float* __restrict__ dqkv, int P, int D, int heads) {
+  using C = StreamCfg<HDT>;
+  constexpr int NF = C::NF, CT = C::CT, CK = C::CK;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* Qs = (float*)smem;
+  float* Gs = Qs + CK * C::LDR;
+  float* lse = Gs + CK * C::LDR;        // [CK]
+  float* dd = lse + CK;                 // [CK]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, lg = lane >> 4;
+  const int head = blockIdx.x, reg = blockIdx.y;
+  const size_t row0 = (size_t)reg * P;
+  const int ld = 3 * D;
+  const int j0 = (blockIdx.z * C::NW + wave) * 16;
+  const bool active = j0 < P;
+  const int m = j0 + lr;
+  float4 fk[NF], fv[NF];
+  hd_row_frags<HDT>(qkv + row0 * ld + D + head * HDT, (size_t)ld, m, P, lg, fk);
+  hd_row_frags<HDT>(qkv + row0 * ld + 2 * D + head * HDT, (size_t)ld, m, P, lg, fv);
+  f32x4 dv[NF], dk[NF];
+#pragma unroll
+  for (int c = 0; c < NF; ++c) dv[c] = dk[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int r0 = 0; r0 < P; r0 += CK) {
+    __syncthreads();
+    hd_load_chunk<HDT>(Qs, qt + head * HDT, (size_t)D, row0, r0, P, tid);
+    hd_load_chunk<HDT>(Gs, dO + head * HDT, (size_t)D, row0, r0, P, tid);
+    if (tid < CK) {
+      const bool ok = r0 + tid < P;
+      lse[tid] = ok ? lse_g[(row0 + r0 + tid) * heads + head] : 0.f;
+      dd[tid] = ok ? dd_g[(row0 + r0 + tid) * heads + head] : 0.f;
+    }
+    __syncthreads();
+    if (active) {
+      auto qrun = [&](auto nc, const int t0) {
+        constexpr int N = decltype(nc)::value;
+        if (r0 + t0 * 16 >= P) return;
+        f32x4 a[N], ds[N];
+        hd_run_scores<HDT, N>(Qs, fk, lr, lg, t0, a);
+        hd_run_scores<HDT, N>(Gs, fv, lr, lg, t0, ds);
+#pragma unroll
+        for (int u = 0; u < N; ++u)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int q = (t0 + u) * 16 + 4 * lg + r;
+            const bool ok = r0 + q < P;
+            const float p = ok ? __builtin_amdgcn_exp2f(a[u][r] - lse[q]) : 0.f;
+            a[u][r] = p;
+            ds[u][r] = ok ? p * (ds[u][r] - dd[q]) : 0.f;
+          }
+        hd_run_apply<HDT, N>(Gs, a, lr, lg, t0, dv);
+        hd_run_apply<HDT, N>(Qs, ds, lr, lg, t0, dk);
+      };
+#pragma unroll
+      for (int t0 = 0; t0 + 3 <= CT; t0 += 3) qrun(std::integral_constant<int, 3>{}, t0);
+      if constexpr (CT % 3 == 1) qrun(std::integral_constant<int, 1>{}, CT - 1);
+      if constexpr (CT % 3 == 2) qrun(std::integral_constant<int, 2>{}, CT - 2);
+    }
+  }
+  if (active) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int key = j0 + 4 * lg + r;
+      if (key < P) {
+        float* dst = dqkv + (row0 + key) * ld + head * HDT;
+        hd_store_row<HDT>(dst + D, dk, r, lr, LN2);
+        hd_store_row<HDT>(dst + 2 * D, dv, r, lr, 1.0f);
+      }
+    }
+  }
+}
+
+// stencil, q pass, kv pass, global-buffer adjoint at head dim HDT; buffers as the head-dim-64 streaming variant's
+template <int HDT>
+hipError_t launch_stream_hd(const float* qkv, const float* pe_w, const float* O, const float* dO, float* dqkv,
+                            float* dpe_part, float* qt, float* tmp, float* lse_g, float* dd_g, int n_regions, int P,
+                            int D, int heads, int epeg_k, hipStream_t st) {
+  using C = StreamCfg<HDT>;
+  const size_t rows = (size_t)n_regions * P;
+  const long n4 = (long)rows * (D / 4);
+  attn_stencil_kernel<HDT><<<dim3((unsigned)((n4 + 255) / 256)), 256, 0, st>>>(qkv, pe_w, qt, P, D, heads, epeg_k, (long)rows);
+  const int groups = (P + 16 * C::NW - 1) / (16 * C::NW);
+  constexpr size_t lq = (size_t)2 * C::CK * C::LDR * sizeof(float), lkv = lq + 2 * C::CK * sizeof(float);
+  static_assert(lkv <= 80 * 1024, "two blocks per CU");
+  static OncePerDevice once;
+  if (once.first()) {
+    (void)hipFuncSetAttribute((const void*)attn_bwd_q_hd_kernel<HDT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lq);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_kv_hd_kernel<HDT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lkv);
+  }
+  attn_bwd_q_hd_kernel<HDT><<<dim3(heads, n_regions, groups), C::NW * 64, lq, st>>>(qkv, qt, O, dO, dqkv, lse_g, dd_g, P, D,
+                                                                                   heads);
+  attn_bwd_kv_hd_kernel<HDT><<<dim3(heads, n_regions, groups), C::NW * 64, lkv, st>>>(qkv, qt, dO, lse_g, dd_g, dqkv, P, D,
+                                                                                     heads);
+  attn_adjoint_kernel<HDT><<<dim3(heads, n_regions), HDT <= 64 ? 256 : 1024, 0, st>>>(qkv, pe_w, dqkv, tmp, dpe_part, P, D, heads, epeg_k,
+                                                                   1.0f / sqrtf((float)HDT));
+  return hipGetLastError();
+}
+
 // ---- any head dim (crmsa_heads = 1 -> head dim = dim), no EPEG, short sequences: CR-MSA's inner attention over
 // the k x 64 representatives.  VALU only: one block per (sequence, head), a wave per query / key row, the head dim
 // across the lanes; A and dS [P, P] in LDS.  (Published TCGA-BRCA-R50 / NSCLC-PLIP configs: 3 x 64 rows.)
@@ -1228,19 +1558,30 @@ __global__ __launch_bounds__(256) void attn_bwd_generic_kernel(const float* __re
 RRT_TRACE_DEFINE_READER(rrt_debug_trace_attn_bwd)
 #endif
 
-// MFMA path: head dim 64, P <= 208.  Generic path: any head dim that is a multiple of 4, no EPEG, P <= 128.
+namespace {
+// the VALU kernel's cases (kept there: moving them to the MFMA kernels would change their bits)
+bool generic_case(int P, int hd, int epeg_k) { return epeg_k == 0 && P <= 128 && hd % 4 == 0; }
+// the streaming variant at the other head dims: a multiple of 16 up to 256, any P, epeg_k <= 63, what the VALU kernel does not take
+bool stream_hd_case(int P, int hd, int epeg_k) {
+  return hd != HD && hd % 16 == 0 && hd >= 16 && hd <= 256 && epeg_k >= 0 && epeg_k <= 63 && !generic_case(P, hd, epeg_k);
+}
+}  // namespace
+
+// MFMA path: head dim 64 (P <= 208 resident, larger streaming), or a multiple of 16 up to 256 (streaming, any P).  Generic
+// VALU path: any head dim that is a multiple of 4, no EPEG, P <= 128.
 bool attn_bwd_supported(int P, int D, int heads, int epeg_k) {
   if (heads <= 0 || P <= 0 || D % heads) return false;
   const int hd = D / heads;
   if (hd == HD) return epeg_k >= 0 && epeg_k <= 63;            // P <= 208 resident kernel, larger: streaming
-  return epeg_k == 0 && P <= 128 && hd % 4 == 0;
+  return generic_case(P, hd, epeg_k) || stream_hd_case(P, hd, epeg_k);
 }
 
-// tap partials [n_regions, heads, k]; streaming variant (P > 208, head dim 64): + q~ [rows, D], tmp [rows, D],
-// lse and D [rows, heads]
+// tap partials [n_regions, heads, k]; streaming variant (P > 208 at head dim 64, every case of the other head dims'
+// MFMA path): + q~ [rows, D], tmp [rows, D], lse and D [rows, heads]
 size_t attn_bwd_workspace(int n_regions, int P, int D, int heads, int epeg_k) {
   size_t b = ((size_t)n_regions * heads * (epeg_k > 0 ? epeg_k : 1) * sizeof(float) + 255) / 256 * 256;
-  if (D == heads * HD && P > 48) {    // (streaming buffers also when the tuning hook forces that variant)
+  if ((D == heads * HD && P > 48) ||    // (streaming buffers also when the tuning hook forces that variant)
+      (heads > 0 && D % heads == 0 && stream_hd_case(P, D / heads, epeg_k))) {
     const size_t rows = (size_t)n_regions * P;
     b += (2 * rows * D + 2 * rows * heads) * sizeof(float) + 1024;
   }
@@ -1256,6 +1597,25 @@ hipError_t launch_attention_backward(const float* qkv, const float* pe_w, const 
   float* const ws_base = dpe_part;                          // the streaming variant's buffers sit behind the partials' slot
   if (defer && defer_part) dpe_part = defer_part;           // partials that must outlive this call (summed at the end)
   else defer = nullptr;
+  if (D / heads != HD && stream_hd_case(P, D / heads, epeg_k)) {
+    const size_t rows = (size_t)n_regions * P;
+    char* base = (char*)ws_base + ((size_t)n_regions * heads * (epeg_k > 0 ? epeg_k : 1) * sizeof(float) + 255) / 256 * 256;
+    float* qt = (float*)base;
+    float* tmp = qt + rows * D;
+    float* lse_g = tmp + rows * D;
+    float* dd_g = lse_g + rows * heads;
+    switch (D / heads) {
+#define RRT_STREAM_HD(H) \
+      case H: e = launch_stream_hd<H>(qkv, pe_w, O, dO, dqkv, dpe_part, qt, tmp, lse_g, dd_g, n_regions, P, D, heads, epeg_k, st); break;
+      RRT_STREAM_HD(16) RRT_STREAM_HD(32) RRT_STREAM_HD(48) RRT_STREAM_HD(80) RRT_STREAM_HD(96) RRT_STREAM_HD(112)
+      RRT_STREAM_HD(128) RRT_STREAM_HD(144) RRT_STREAM_HD(160) RRT_STREAM_HD(176) RRT_STREAM_HD(192) RRT_STREAM_HD(208)
+      RRT_STREAM_HD(224) RRT_STREAM_HD(240) RRT_STREAM_HD(256)
+#undef RRT_STREAM_HD
+      default: return hipErrorInvalidValue;
+    }
+    if (e != hipSuccess || epeg_k == 0 || dpe == nullptr) return e;
+    return reduce_or_defer(defer, dpe_part, dpe, n_regions, (size_t)heads * epeg_k, st);
+  }
   if (D / heads != HD) {
     const size_t lds = (size_t)2 * P * P * sizeof(float);
     if (lds > 64 * 1024)
@@ -1274,7 +1634,7 @@ hipError_t launch_attention_backward(const float* qkv, const float* pe_w, const 
     float* dd_g = lse_g + rows * heads;
     const float q_scale = 1.0f / sqrtf((float)HD);
     const long n4 = (long)rows * (D / 4);
-    attn_stencil_kernel<<<dim3((unsigned)((n4 + 255) / 256)), 256, 0, st>>>(qkv, pe_w, qt, P, D, heads, epeg_k, (long)rows);
+    attn_stencil_kernel<HD><<<dim3((unsigned)((n4 + 255) / 256)), 256, 0, st>>>(qkv, pe_w, qt, P, D, heads, epeg_k, (long)rows);
     const int groups = (P + 95) / 96;
     const size_t lq = (size_t)2 * CK * HD * sizeof(float), lkv = lq + 2 * CK * sizeof(float);
     static OncePerDevice once;
@@ -1291,7 +1651,7 @@ hipError_t launch_attention_backward(const float* qkv, const float* pe_w, const 
         (void)hipFuncSetAttribute((const void*)attn_adjoint_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LADJ);
       attn_adjoint_lds_kernel<<<dim3(heads, n_regions), 512, LADJ, st>>>(qkv, pe_w, dqkv, dpe_part, P, D, heads, epeg_k, q_scale);
     } else {
-      attn_adjoint_kernel<<<dim3(heads, n_regions), 256, 0, st>>>(qkv, pe_w, dqkv, tmp, dpe_part, P, D, heads, epeg_k,
+      attn_adjoint_kernel<HD><<<dim3(heads, n_regions), 256, 0, st>>>(qkv, pe_w, dqkv, tmp, dpe_part, P, D, heads, epeg_k,
                                                                    q_scale);
     }
     e = hipGetLastError();

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define RRT_ABI_VERSION 27
+#define RRT_ABI_VERSION 28
 #define RRT_MAX_RMSA_LAYERS 8
 #define RRT_MAX_CRMSA_K 8
 
@@ -166,6 +166,8 @@ int rrt_encoder_workspace_size(const rrt_encoder_desc *desc, int64_t n_tokens, s
 #define RRT_PLAN_FUSED_X3   8   /* the split-bf16 fused kernel (RRT_COMPUTE_F32X3) */
 #define RRT_PLAN_CRMSA_PARTS 16 /* the last layer's merged launch also leaves CR-MSA's row records (LayerNorm 2 statistics +
                                    logit dot products); CR-MSA's first pass is rrt_crmsa_combine_parts_f32 */
+#define RRT_PLAN_ATTN_HD    32  /* qkv linear + the MFMA attention forward at a head dim other than 64 (set alone; see
+                                   rrt_region_attention_hd_supported) */
 int rrt_encoder_plan(const rrt_encoder_desc *desc, int64_t n_tokens, int32_t *flags);
 
 /* Whole path: RRTEncoder.forward, modules/rrt.py:165-202 (eval mode, one bag).
@@ -239,10 +241,22 @@ int rrt_linear_unpartition_residual_f32(const float *A, const float *B, const fl
 
 /* Region attention core (rmsa.py:103-122): qkv [n_regions*P, 3*dim] (q already scaled),
  * EPEG taps pe_w [heads, epeg_k] (NULL/0 = none; pe bias is softmax-invariant and not needed)
- * -> o [n_regions*P, dim] (heads merged). */
+ * -> o [n_regions*P, dim] (heads merged).
+ * Which kernel runs, by head dim = dim / heads: 64 -> the head-dim-64 MFMA kernels; every other multiple of 16 in
+ * [16, 256] with epeg_k <= 63 -> the MFMA kernel of rrt_region_attention_hd_f32; anything else (above 256, not a
+ * multiple of 16) -> a VALU kernel, one wave per query. */
 int rrt_region_attention_f32(const float *qkv, const float *pe_w, float *o,
                              int32_t n_regions, int32_t P, int32_t dim, int32_t heads,
                              int32_t epeg_k, void *stream);
+
+/* host-only: 1 when rrt_region_attention_f32 takes the MFMA kernel for head dims other than 64, else 0:
+ * heads divides dim, dim / heads is a multiple of 16 in [16, 256] and not 64, epeg_k <= 63, any P >= 1. */
+int rrt_region_attention_hd_supported(int32_t P, int32_t dim, int32_t heads, int32_t epeg_k);
+/* That kernel alone (same arguments and result as rrt_region_attention_f32): RRT_E_UNSUPPORTED outside the predicate
+ * above -- checked before the pointers, which are not touched then -- and RRT_E_INVALID on NULL qkv / o. */
+int rrt_region_attention_hd_f32(const float *qkv, const float *pe_w, float *o,
+                                int32_t n_regions, int32_t P, int32_t dim, int32_t heads,
+                                int32_t epeg_k, void *stream);
 
 /* Fused R-MSA core (rmsa.py:100-122 in one kernel per (region, head)): u [n_regions*P, dim]
  * region-major LayerNorm-ed tokens -> o [n_regions*P, dim]; qkv_w [3*dim, dim], qkv_b [3*dim] or NULL,

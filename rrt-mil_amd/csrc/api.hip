@@ -262,7 +262,9 @@ int rrt_encoder_plan(const rrt_encoder_desc* desc, int64_t n_tokens, int32_t* fl
           crmsa_combine_parts_supported(D, desc->crmsa_k, to_dev(g8)))
         *flags |= RRT_PLAN_CRMSA_PARTS;
     }
+    return RRT_OK;
   }
+  if (region_attention_hd_supported(gd.P, D, desc->n_heads, ek)) *flags = RRT_PLAN_ATTN_HD;   // qkv linear + region_attn_hd
   return RRT_OK;
 }
 
@@ -1036,6 +1038,23 @@ int rrt_region_attention_f32(const float* qkv, const float* pe_w, float* o, int3
   if (!qkv || !o || n_regions <= 0 || P <= 0 || dim <= 0 || heads <= 0 || dim % heads) return RRT_E_INVALID;
   if (pe_w && epeg_k > 0 && epeg_k % 2 == 0) return unsupported("epeg_k must be odd");
   return (int)launch_region_attention(qkv, pe_w, o, n_regions, P, dim, heads, epeg_k, (hipStream_t)stream);
+}
+
+int rrt_region_attention_hd_supported(int32_t P, int32_t dim, int32_t heads, int32_t epeg_k) {
+  return region_attention_hd_supported(P, dim, heads, epeg_k) ? 1 : 0;
+}
+
+int rrt_region_attention_hd_f32(const float* qkv, const float* pe_w, float* o, int32_t n_regions, int32_t P, int32_t dim,
+                                int32_t heads, int32_t epeg_k, void* stream) {
+  if (n_regions <= 0 || P <= 0 || dim <= 0 || heads <= 0 || dim % heads) return RRT_E_INVALID;
+  const int ek = pe_w ? epeg_k : 0;
+  if (!region_attention_hd_supported(P, dim, heads, ek))      // before the pointers: nothing is touched outside the predicate
+    return unsupported("region_attention_hd: needs a head dim that is a multiple of 16 in [16, 256] other than 64 and "
+                       "epeg_k <= 63 (use rrt_region_attention_f32)");
+  if (!qkv || !o) return RRT_E_INVALID;
+  if (ek > 0 && ek % 2 == 0) return unsupported("epeg_k must be odd");
+  if (n_regions > 65535) return unsupported("region_attention_hd: more than 65535 regions in one call");
+  return (int)launch_region_attention_hd(qkv, pe_w, o, n_regions, P, dim, heads, ek, (hipStream_t)stream);
 }
 
 int rrt_rmsa_fused_f32(const float* u, const float* qkv_w, const float* qkv_b, const float* pe_w, float* o,

@@ -116,6 +116,11 @@ hipError_t launch_rmsa_fused16(const uint16_t* U16, const uint16_t* Wqkv16, cons
 
 hipError_t launch_region_attention(const float* qkv, const float* pe_w, float* o, int n_regions,
                                    int P, int dim, int heads, int epeg_k, hipStream_t st);
+// the MFMA forward at head dims 16 .. 256 (multiples of 16) other than 64, epeg_k <= 63, any P (region_attn_hd.hip);
+// launch_region_attention sends every call inside the predicate there
+bool region_attention_hd_supported(int P, int dim, int heads, int epeg_k);
+hipError_t launch_region_attention_hd(const float* qkv, const float* pe_w, float* o, int n_regions, int P, int dim,
+                                      int heads, int epeg_k, hipStream_t st);
 
 // fused qkv projection + EPEG + attention per (region, head) (rmsa_fused.hip); P in (112,144], head dim 64
 bool rmsa_fused_supported(int P, int D, int heads, int epeg_k);

@@ -24,7 +24,8 @@
 //     row-per-lane ds_read_b128 is bank-conflict free; V is read row-contiguous;
 //   * a lane's float4 of V covers 4 head-dim tiles (d = 4*(l&15)+c), so the O tile
 //     comes out as one float4 per row: coalesced 256-B row stores.
-// Head dim 64 only (dim/heads == 64); other head dims use region_attn_generic.
+// Head dim 64 only (dim/heads == 64).  The other multiples of 16 up to 256 (epeg_k <= 63) go to region_attn_hd.hip's MFMA
+// kernel; what is left -- head dims above 256 or not a multiple of 16 -- uses region_attn_generic.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -423,7 +424,7 @@ __global__ __launch_bounds__(1024) void region_attn_resident_kernel(const float*
   }
 }
 
-// Generic head-dim fallback (hd != 64: e.g. crmsa_heads=1 -> hd=dim, or dim=64 -> hd=8).
+// Generic head-dim fallback (hd > 256 or not a multiple of 16: e.g. crmsa_heads=1 -> hd=dim, or dim=64 -> hd=8).
 // One wave per query; VALU only (the published TCGA-BRCA-R50 / NSCLC-PLIP configs run CR-MSA's inner attention
 // with crmsa_heads=1: 3 x 64 queries of head dim 512).
 __global__ __launch_bounds__(256) void region_attn_generic_kernel(const float* __restrict__ qkv,
@@ -623,6 +624,8 @@ hipError_t launch_region_attention(const float* qkv, const float* pe_w, float* o
                                    int P, int dim, int heads, int epeg_k, hipStream_t st) {
   const int hd = dim / heads;
   if (pe_w == nullptr) epeg_k = 0;
+  if (region_attention_hd_supported(P, dim, heads, epeg_k))
+    return launch_region_attention_hd(qkv, pe_w, o, n_regions, P, dim, heads, epeg_k, st);
   if (hd != HD) {
     const int Ppad = (P + 3) & ~3;
     size_t lds = (size_t)4 * (hd + Ppad) * sizeof(float);

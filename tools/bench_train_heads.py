@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Training step of the encoder at several R-MSA head dims (fp32, drop_out = 0, one bag of N tokens, loss = <y, G>), and
-what its attention backward costs.
+what its attention backward and its forward attention kernel cost.
 
     python tools/bench_train_heads.py [--n 9000] [--steps 30] [--warmup 5]        step times (device events), one table
     python tools/bench_train_heads.py --run CONFIG [--n 9000] [--steps 20]        steps of one config only: run this under
@@ -27,6 +27,7 @@ from rrt_mil_amd import RRTEncoder, synth          # noqa: E402
 from oracle import rrt_oracle as O                  # noqa: E402
 
 PEAK = 157.3e12
+FWD_ATTN = ("region_attn_generic_kernel", "region_attn_hd_kernel")
 CONFIGS = {"d512_h8": (512, 8), "d512_h2": (512, 2), "d512_h4": (512, 4), "d512_h16": (512, 16), "d1024_h8": (1024, 8)}
 
 
@@ -67,15 +68,19 @@ def time_steps(name, n, steps, warmup):
 
 
 def report(name, db_path, n, steps):
-    """kernel times per step of an `--run` trace: the attention backward's kernels, the VALU forward kernel"""
+    """kernel times per step of an `--run` trace: the attention backward's kernels, the forward attention kernel"""
     D, heads = CONFIGS[name]
     R, P, prod = geometry(n, D)
     db = sqlite3.connect(db_path)
     cols = [r[1] for r in db.execute("pragma table_info(kernels)")]
     namecol = "name" if "name" in cols else [c for c in cols if "name" in c][0]
-    per = {}
-    for kname, s, e in db.execute(f"select {namecol}, start, end from kernels"):
-        per.setdefault(kname.replace("(anonymous namespace)::", "").replace("void ", ""), []).append((e - s) / 1e3)
+    gridcols = [c for c in ("grid_x", "grid_y", "grid_z") if c in cols] or [c for c in cols if c.startswith("grid")][:3]
+    per, fwd = {}, {}
+    for row in db.execute(f"select {', '.join([namecol, 'start', 'end'] + gridcols)} from kernels"):
+        kname = row[0].replace("(anonymous namespace)::", "").replace("void ", "")
+        per.setdefault(kname, []).append((row[2] - row[1]) / 1e3)
+        if kname.startswith(FWD_ATTN):                 # forward attention kernel: calls told apart by grid size
+            fwd.setdefault((kname.split("(")[0], tuple(row[3:])), []).append((row[2] - row[1]) / 1e3)
     calls = steps + 2                               # --run: two warm-up steps, then the timed ones
     attn = {k: v for k, v in per.items() if k.split("(")[0].startswith(("attn_bwd", "attn_stencil", "attn_adjoint"))}
     # CR-MSA's inner attention (k x 64 representatives, no EPEG) runs its own backward: the resident <4, .> instance or
@@ -91,10 +96,14 @@ def report(name, db_path, n, steps):
     print(f"R-MSA attention backward: {rmsa_us:.1f} us per layer; {5 * prod / 1e9:.2f} GFLOP algorithmic -> "
           f"{5 * prod / (rmsa_us * 1e-6) / PEAK:.3f} of the fp32 matrix peak; {issued} products issued ({issued * prod / 1e9:.2f} "
           f"GFLOP) -> {issued * prod / (rmsa_us * 1e-6) / PEAK:.3f}")
-    for k, v in per.items():
-        if k.startswith("region_attn_generic_kernel"):
-            print(f"forward VALU kernel region_attn_generic_kernel: {len(v) / calls:.2f} calls/step, avg {np.mean(v):.1f} us, "
-                  f"{sum(v) / calls:.1f} us/step")
+    # whichever forward attention kernel ran at this head dim (the VALU one, or the MFMA one of region_attn_hd.hip); the
+    # call with the largest grid is the R-MSA layer's, a smaller one CR-MSA's inner attention under the same name
+    rmsa_grid = max((int(np.prod(g)) for _, g in fwd), default=0)
+    for (k, g), v in sorted(fwd.items(), key=lambda kv: -sum(kv[1])):
+        is_rmsa = int(np.prod(g)) == rmsa_grid
+        share = f", {2 * prod / (np.mean(v) * 1e-6) / PEAK:.3f} of the fp32 matrix peak for 2 products" if is_rmsa else ""
+        print(f"forward attention kernel {k} grid {'x'.join(map(str, g))} ({'R-MSA' if is_rmsa else 'CR-MSA inner'}): "
+              f"{len(v) / calls:.2f} calls/step, avg {np.mean(v):.1f} us, {sum(v) / calls:.1f} us/step{share}")
     tot = sum(sum(v) for v in per.values()) / calls
     print(f"all kernels: {tot:.1f} us per step")
 

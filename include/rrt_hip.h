@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define RRT_ABI_VERSION 28
+#define RRT_ABI_VERSION 29
 #define RRT_MAX_RMSA_LAYERS 8
 #define RRT_MAX_CRMSA_K 8
 
@@ -479,6 +479,70 @@ int rrt_pool_predict_f32(const float *y, const float *a_w, const float *a_b, con
 /* nn.Linear with an activation epilogue: C = act(A . B^T + bias)   (patch_to_emb, rrt.py:208-217) */
 int rrt_linear_act_f32(const float *A, const float *B, const float *bias, float *C, int64_t M, int32_t N,
                        int32_t K, int32_t act, int32_t compute, void *stream);
+
+/* ---- CLAM_SB / CLAM_MB heads (modules/clam.py; ABI 29): multi-branch gated attention pooling ----
+ * The branch pool alone (clam.py:25-74 AFTER the first Linear + activation, :172-177, :203 / :293): K attention branches
+ * from ONE pass over y --
+ *     s[c, n] = c_w[c] . h_n + c_b[c]   (h = hid_a, or hid_a * hid_b when hid_b != NULL),
+ *     attn[c, :] = softmax_n(s[c, :]),   pooled[c, :] = sum_n attn[c, n] y_n.
+ * y [N, dim], hid_a / hid_b [N, hidden], c_w [K, hidden], c_b [K] or NULL.  Outputs: pooled [K, dim], a_raw [K, N] (the
+ * scores), attn [K, N] (optional, may be NULL).  1 <= K <= 8, dim % 32 == 0, dim <= 2048, hidden % 4 == 0, N <= 1e6,
+ * otherwise RRT_E_UNSUPPORTED (inside these limits the merge block's LDS, 4 * (N / 32 + dim) bytes + 16 KiB, always fits).
+ * Every sum has a fixed order: the same inputs give the same bits.
+ * ... and its adjoint: given d_pooled [K, dim] and optionally d_raw [K, N] -> dy [N, dim], dhid_a / dhid_b [N, hidden],
+ * dwcb [K * hidden + 8] = d c_w [K, hidden] | d c_b [K] (at [K * hidden]).  The adjoint alone has one more limit: its block
+ * keeps d_pooled and four d c_w partials in LDS, K * (dim + 4 * hidden) + 32 floats <= 150 KiB, otherwise
+ * RRT_E_UNSUPPORTED (the forward and the workspace query do not have it; CLAM's K <= 8, dim 512, hidden <= 384 need 65 KiB).
+ * workspace: rrt_branch_pool_workspace_size bytes (either call). */
+int rrt_branch_pool_workspace_size(int64_t n_tokens, int32_t dim, int32_t hidden, int32_t n_branches, size_t *bytes);
+int rrt_branch_pool_f32(const float *y, const float *hid_a, const float *hid_b, const float *c_w, const float *c_b,
+                        float *pooled, float *attn, float *a_raw, int64_t n_tokens, int32_t dim, int32_t hidden,
+                        int32_t n_branches, void *workspace, size_t workspace_bytes, void *stream);
+int rrt_branch_pool_backward_f32(const float *y, const float *hid_a, const float *hid_b, const float *c_w,
+                                 const float *attn, const float *pooled, const float *d_pooled, const float *d_raw,
+                                 float *dy, float *dhid_a, float *dhid_b, float *dwcb, int64_t n_tokens, int32_t dim,
+                                 int32_t hidden, int32_t n_branches, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+
+/* Top-k instance selection (the torch.topk calls of clam.py:141-143, :161): for each of n_rows rows of n floats,
+ * idx [n_rows, 2, k] (int64) = the indices of the k largest values in descending order ([r, 0, :]) and of the k smallest
+ * in ascending order ([r, 1, :]).  TIES: among equal values the LOWER index comes first, at both ends (torch leaves the
+ * order of ties unspecified).  NaN entries are never selected; a row with fewer than k non-NaN values has its unused slots
+ * set to -1.  1 <= k <= 32 (else RRT_E_UNSUPPORTED), n < k is RRT_E_INVALID, n <= 2^31 - 2, n_rows <= 65535. */
+int rrt_topk_rows_f32(const float *x, int64_t *idx, int32_t n_rows, int64_t n, int32_t k, void *stream);
+
+/* CLAM_SB / CLAM_MB.forward (eval, one bag, one stream): x [n_tokens, input_dim] -> Linear(input_dim, dim) + act ->
+ * RRTEncoder (has_rrt; the reference allows rrt=None) -> the two gate Linears tanh / sigmoid (enc.compute's arithmetic)
+ * -> branch pool -> bag logits [n_classes]. */
+typedef struct rrt_clam_desc {
+  rrt_encoder_desc enc;    /* has_rrt = 0: only dim (= 512 in the reference) and compute are read */
+  int32_t input_dim;       /* patch feature width (multiple of 32) */
+  int32_t emb_act;         /* RRT_ACT_RELU / RRT_ACT_GELU */
+  int32_t has_rrt;         /* 1: the encoder sits between the embedding and the attention net (clam.py:104-105) */
+  int32_t n_classes;
+  int32_t per_branch;      /* 0: CLAM_SB, one branch, logits = cls_w [n_classes, dim] . M[0] + cls_b;
+                            * 1: CLAM_MB, n_classes branches, logits[c] = cls_w[c] . M[c] + cls_b[c] */
+  int32_t gated;           /* 1: Attn_Net_Gated */
+  int32_t hidden;          /* gate width: 256 ('small') / 384 ('big'); a multiple of 4 */
+  int32_t k_sample;        /* width of topk_idx (1..32; read only when topk_idx != NULL) */
+} rrt_clam_desc;
+
+typedef struct rrt_clam_weights {
+  rrt_encoder_weights enc;
+  const float *emb_w, *emb_b;         /* attention_net.0        [dim, input_dim], [dim] */
+  const float *a_w, *a_b;             /* attention_a.0 / module.0   [hidden, dim], [hidden] */
+  const float *b_w, *b_b;             /* attention_b.0 (gated only) */
+  const float *c_w, *c_b;             /* attention_c / module's last Linear  [K, hidden], [K]   (K = per_branch ? n_classes : 1) */
+  const float *cls_w, *cls_b;         /* SB: classifiers [n_classes, dim], [n_classes]; MB: the n_classes Linear(dim, 1)
+                                       * rows packed by the caller into [n_classes, dim], [n_classes] */
+} rrt_clam_weights;
+
+int rrt_clam_workspace_size(const rrt_clam_desc *desc, int64_t n_tokens, size_t *bytes);
+/* Optional outputs (NULL: not wanted): a_raw [K, n_tokens] (what attention_only=True returns), attn [K, n_tokens]
+ * (softmax over the bag), features [K, dim] (M), topk_idx [K, 2, k_sample] (rrt_topk_rows_f32 of attn). */
+int rrt_clam_forward_f32(const rrt_clam_desc *desc, const rrt_clam_weights *w, const float *x, float *logits,
+                         float *a_raw, float *attn, float *features, int64_t *topk_idx, int64_t n_tokens,
+                         void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- batch-of-bags executor (BASELINE configs[4]: mixed-size bags, every bag an independent B=1 forward;
  * the reference loops `for bag in loader: model(bag)`, main.py:466-467 / :558-560) ----

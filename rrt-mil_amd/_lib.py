@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(HERE, "librrt_hip.so")
 
 RRT_MAX_RMSA_LAYERS = 8
 RRT_MAX_CRMSA_K = 8
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 _f32p = C.POINTER(C.c_float)
 
@@ -67,6 +67,17 @@ class MilWeights(C.Structure):
     _fields_ = [("enc", EncoderWeights)] + [(n, C.c_void_p) for n in (
         "emb_w", "emb_b", "pool_a_w", "pool_a_b", "pool_b_w", "pool_b_b", "pool_c_w", "pool_c_b",
         "pred_w", "pred_b")]
+
+
+class ClamDesc(C.Structure):
+    _fields_ = [("enc", EncoderDesc), ("input_dim", C.c_int32), ("emb_act", C.c_int32), ("has_rrt", C.c_int32),
+                ("n_classes", C.c_int32), ("per_branch", C.c_int32), ("gated", C.c_int32), ("hidden", C.c_int32),
+                ("k_sample", C.c_int32)]
+
+
+class ClamWeights(C.Structure):
+    _fields_ = [("enc", EncoderWeights)] + [(n, C.c_void_p) for n in (
+        "emb_w", "emb_b", "a_w", "a_b", "b_w", "b_b", "c_w", "c_b", "cls_w", "cls_b")]
 
 
 class Bag(C.Structure):
@@ -150,6 +161,15 @@ SIGNATURES = {
     "rrt_attn_pool_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rrt_attn_pool_backward_f32": (C.c_int, [C.c_void_p] * 14 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
                                                                  C.c_void_p]),
+    "rrt_branch_pool_workspace_size": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_branch_pool_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                                         C.c_void_p]),
+    "rrt_branch_pool_backward_f32": (C.c_int, [C.c_void_p] * 12 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                                   C.c_size_t, C.c_void_p]),
+    "rrt_topk_rows_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
+    "rrt_clam_workspace_size": (C.c_int, [C.POINTER(ClamDesc), C.c_int64, C.POINTER(C.c_size_t)]),
+    "rrt_clam_forward_f32": (C.c_int, [C.POINTER(ClamDesc), C.POINTER(ClamWeights)] + [C.c_void_p] * 6 +
+                             [C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rrt_executor_create": (C.c_int, [C.POINTER(EncoderDesc), C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     "rrt_executor_create_on_streams": (C.c_int, [C.POINTER(EncoderDesc), C.c_int32, C.POINTER(C.c_void_p), C.c_int64,
                                                  C.POINTER(C.c_void_p)]),

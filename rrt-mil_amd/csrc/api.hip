@@ -1413,6 +1413,60 @@ int check_mil(const rrt_mil_desc* d, int64_t N) {
   return check_pool(N, d->enc.dim, d->pool_hidden, d->pool_act, d->n_classes);
 }
 
+// ---- CLAM heads (clam_pool.hip)
+int check_branch_pool(int64_t N, int dim, int hidden, int K) {
+  if (N <= 0 || dim <= 0 || hidden <= 0) return RRT_E_INVALID;
+  if (K < 1 || K > 8) return unsupported("branch pool: 1 <= n_branches <= 8");
+  if (dim % 32) return unsupported("branch pool: dim must be a multiple of 32");
+  if (dim > 2048) return unsupported("branch pool: dim > 2048");
+  if (hidden % 4) return unsupported("branch pool: hidden width must be a multiple of 4");
+  if (N > (int64_t)1000000) return unsupported("branch pool: bag larger than 1e6 tokens");
+  return RRT_OK;
+}
+
+size_t branch_pool_workspace(int64_t N, int dim, int hidden, int K) {
+  const size_t fwd = align_up(branch_pool_part_floats((int)N, dim, K) * sizeof(float), 256);
+  const size_t bwd = align_up(branch_pool_backward_part_floats((int)N, hidden, K) * sizeof(float), 256);
+  return fwd > bwd ? fwd : bwd;
+}
+
+struct ClamWs {
+  float *hid_a, *hid_b, *a_raw, *attn, *pooled, *part;
+  size_t bytes;
+};
+ClamWs carve_clam(int64_t N, int dim, int hidden, int gated, int K, char* base) {
+  ClamWs w{};
+  size_t off = 0;
+  auto take = [&](size_t nfloat) {
+    float* p = base ? (float*)(base + off) : nullptr;
+    off = align_up(off + nfloat * sizeof(float), 256);
+    return p;
+  };
+  w.hid_a = take((size_t)N * hidden);
+  if (gated) w.hid_b = take((size_t)N * hidden);
+  w.a_raw = take((size_t)K * N);
+  w.attn = take((size_t)K * N);
+  w.pooled = take((size_t)K * dim);
+  w.part = take(branch_pool_part_floats((int)N, dim, K));
+  w.bytes = off;
+  return w;
+}
+
+int check_clam(const rrt_clam_desc* d, int64_t N) {
+  if (!d || N <= 0) return RRT_E_INVALID;
+  if (d->has_rrt) {
+    int rc = check_desc(&d->enc, N);
+    if (rc) return rc;
+  }
+  if (d->input_dim <= 0 || d->input_dim % 32) return unsupported("input_dim must be a positive multiple of 32");
+  if (d->emb_act != RRT_ACT_NONE && d->emb_act != RRT_ACT_RELU && d->emb_act != RRT_ACT_GELU)
+    return unsupported("emb_act must be none/relu/gelu");
+  if (d->enc.compute < 0 || d->enc.compute > RRT_COMPUTE_F32X3) return unsupported("compute must be RRT_COMPUTE_*");
+  if (d->n_classes <= 0) return RRT_E_INVALID;
+  if (d->per_branch && d->n_classes > 8) return unsupported("CLAM_MB: n_classes <= 8 (one attention branch per class)");
+  return check_branch_pool(N, d->enc.dim, d->hidden, d->per_branch ? d->n_classes : 1);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1596,6 +1650,163 @@ int rrt_mil_forward_f32(const rrt_mil_desc* desc, const rrt_mil_weights* w, cons
                       w->pool_c_w, w->pool_c_b, w->pred_w, w->pred_b, nullptr, logits, attn, no_norm, n_tokens,
                       D, desc->pool_hidden, desc->pool_act, desc->n_classes, gemm_prec, pws, st, p16 ? y16 : nullptr,
                       p16 ? pa16 : nullptr, (p16 && desc->pool_gated) ? pb16 : nullptr);
+}
+
+// ---- CLAM heads: the branch pool alone (forward, backward), top-k of rows, and the one-call CLAM_SB / CLAM_MB forward
+int rrt_branch_pool_workspace_size(int64_t n_tokens, int32_t dim, int32_t hidden, int32_t n_branches, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_branch_pool(n_tokens, dim, hidden, n_branches);
+  if (rc) return rc;
+  *bytes = branch_pool_workspace(n_tokens, dim, hidden, n_branches);
+  return RRT_OK;
+}
+
+int rrt_branch_pool_f32(const float* y, const float* hid_a, const float* hid_b, const float* c_w, const float* c_b,
+                        float* pooled, float* attn, float* a_raw, int64_t n_tokens, int32_t dim, int32_t hidden,
+                        int32_t n_branches, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!y || !hid_a || !c_w || !pooled || !a_raw) return RRT_E_INVALID;
+  int rc = check_branch_pool(n_tokens, dim, hidden, n_branches);
+  if (rc) return rc;
+  if (branch_pool_merge_lds((int)n_tokens, dim) > 150 * 1024) return unsupported("branch pool: bag too large for the merge block");
+  if (!workspace || workspace_bytes < branch_pool_workspace(n_tokens, dim, hidden, n_branches)) return RRT_E_WORKSPACE;
+  return (int)launch_branch_pool(y, hid_a, hid_b, c_w, c_b, nullptr, nullptr, pooled, nullptr, attn, a_raw, (float*)workspace, 0,
+                                 0, (int)n_tokens, dim, hidden, n_branches, (hipStream_t)stream);
+}
+
+int rrt_branch_pool_backward_f32(const float* y, const float* hid_a, const float* hid_b, const float* c_w, const float* attn,
+                                 const float* pooled, const float* d_pooled, const float* d_raw, float* dy, float* dhid_a,
+                                 float* dhid_b, float* dwcb, int64_t n_tokens, int32_t dim, int32_t hidden, int32_t n_branches,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  if (!y || !hid_a || !c_w || !attn || !pooled || !d_pooled || !dy || !dhid_a || !dwcb || (hid_b && !dhid_b)) return RRT_E_INVALID;
+  int rc = check_branch_pool(n_tokens, dim, hidden, n_branches);
+  if (rc) return rc;
+  if (branch_pool_backward_lds(dim, hidden, n_branches) > 150 * 1024)
+    return unsupported("branch pool backward: n_branches * (dim + 4 * hidden) floats exceed the block's LDS budget");
+  if (!workspace || workspace_bytes < branch_pool_workspace(n_tokens, dim, hidden, n_branches)) return RRT_E_WORKSPACE;
+  return (int)launch_branch_pool_backward(y, hid_a, hid_b, c_w, attn, pooled, d_pooled, d_raw, dy, dhid_a, dhid_b, dwcb,
+                                          (float*)workspace, (int)n_tokens, dim, hidden, n_branches, (hipStream_t)stream);
+}
+
+int rrt_topk_rows_f32(const float* x, int64_t* idx, int32_t n_rows, int64_t n, int32_t k, void* stream) {
+  if (!x || !idx || n_rows <= 0 || n <= 0 || k <= 0) return RRT_E_INVALID;
+  if (k > 32) return unsupported("topk: k <= 32");
+  if (n > (int64_t)2147483646) return unsupported("topk: rows of at most 2^31 - 2 values");
+  if (n_rows > 65535) return unsupported("topk: at most 65535 rows");
+  if (n < k) return RRT_E_INVALID;
+  return (int)launch_topk_rows(x, (long long*)idx, n_rows, (int)n, k, (hipStream_t)stream);
+}
+
+static size_t clam_act_bytes(const rrt_clam_desc* d, int64_t N) { return align_up((size_t)N * d->enc.dim * sizeof(float), 256); }
+
+int rrt_clam_workspace_size(const rrt_clam_desc* desc, int64_t n_tokens, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_clam(desc, n_tokens);
+  if (rc) return rc;
+  size_t enc = 0;
+  if (desc->has_rrt) {
+    rc = rrt_encoder_workspace_size(&desc->enc, n_tokens, &enc);
+    if (rc) return rc;
+  }
+  const int D = desc->enc.dim, K = desc->per_branch ? desc->n_classes : 1;
+  // (as rrt_mil_workspace_size: the 16-bit images of the reduced-precision modes are part of the size in every mode)
+  *bytes = 2 * clam_act_bytes(desc, n_tokens) + align_up(enc, 256) +
+           align_up(carve_clam(n_tokens, D, desc->hidden, desc->gated, K, nullptr).bytes, 256) +
+           align_up((size_t)n_tokens * desc->input_dim * 2, 256) + align_up((size_t)D * desc->input_dim * 2, 256) +
+           align_up((size_t)n_tokens * D * 2, 256) + 2 * align_up((size_t)desc->hidden * D * 2, 256);
+  return RRT_OK;
+}
+
+int rrt_clam_forward_f32(const rrt_clam_desc* desc, const rrt_clam_weights* w, const float* x, float* logits, float* a_raw,
+                         float* attn, float* features, int64_t* topk_idx, int64_t n_tokens, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  if (!desc || !w || !x || !logits) return RRT_E_INVALID;
+  int rc = check_clam(desc, n_tokens);
+  if (rc) return rc;
+  if (!w->emb_w || !w->a_w || !w->c_w || !w->cls_w || (desc->gated && !w->b_w)) return RRT_E_INVALID;
+  if (topk_idx) {
+    if (desc->k_sample <= 0) return RRT_E_INVALID;
+    if (desc->k_sample > 32) return unsupported("topk: k <= 32");
+    if (n_tokens < desc->k_sample) return RRT_E_INVALID;
+  }
+  if (branch_pool_merge_lds((int)n_tokens, desc->enc.dim) > 150 * 1024) return unsupported("branch pool: bag too large for the merge block");
+  size_t need = 0, enc_bytes = 0;
+  rc = rrt_clam_workspace_size(desc, n_tokens, &need);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < need) return RRT_E_WORKSPACE;
+  if (desc->has_rrt) {
+    rc = rrt_encoder_workspace_size(&desc->enc, n_tokens, &enc_bytes);
+    if (rc) return rc;
+  }
+  const int D = desc->enc.dim, K = desc->per_branch ? desc->n_classes : 1, H = desc->hidden;
+  const size_t act = clam_act_bytes(desc, n_tokens);
+  char* base = (char*)workspace;
+  float* emb = (float*)base;
+  float* y = desc->has_rrt ? (float*)(base + act) : emb;
+  char* enc_ws = base + 2 * act;
+  ClamWs cws = carve_clam(n_tokens, D, H, desc->gated, K, enc_ws + align_up(enc_bytes, 256));
+  hipStream_t st = (hipStream_t)stream;
+
+  // the GEMMs around the encoder follow enc.compute exactly as in rrt_mil_forward_f32 (F32X3: exact fp32 here)
+  const int gemm_prec = desc->enc.compute == RRT_COMPUTE_F32X3 ? RRT_COMPUTE_F32 : desc->enc.compute;
+  LinearEpilogue ep{};
+  ep.prec = gemm_prec;
+  ep.bias = w->emb_b;
+  ep.act = desc->emb_act;
+  uint16_t *y16 = nullptr, *pa16 = nullptr, *pb16 = nullptr;
+  bool pool16 = false, y16_done = false;
+  hipError_t e;
+  if ((gemm_prec == RRT_COMPUTE_BF16 || gemm_prec == RRT_COMPUTE_F16) && desc->input_dim % 64 == 0) {
+    char* tail = enc_ws + align_up(enc_bytes, 256) + align_up(cws.bytes, 256);
+    uint16_t* x16 = (uint16_t*)tail;
+    uint16_t* w16 = (uint16_t*)(tail + align_up((size_t)n_tokens * desc->input_dim * 2, 256));
+    y16 = (uint16_t*)((char*)w16 + align_up((size_t)D * desc->input_dim * 2, 256));
+    pa16 = (uint16_t*)((char*)y16 + align_up((size_t)n_tokens * D * 2, 256));
+    pb16 = (uint16_t*)((char*)pa16 + align_up((size_t)H * D * 2, 256));
+    Cast16Jobs cj{};
+    cj.src[0] = x; cj.dst[0] = x16; cj.n4[0] = (size_t)n_tokens * desc->input_dim / 4;
+    cj.src[1] = w->emb_w; cj.dst[1] = w16; cj.n4[1] = (size_t)D * desc->input_dim / 4;
+    cj.count = 2;
+    // the gate Linears' weights in the same launch: their 16-bit-operand product reads the encoder's y16
+    pool16 = desc->has_rrt && D % 64 == 0 && ((size_t)H * D) % 4 == 0;
+    if (pool16) {
+      cj.src[cj.count] = w->a_w; cj.dst[cj.count] = pa16; cj.n4[cj.count++] = (size_t)H * D / 4;
+      if (desc->gated) {
+        cj.src[cj.count] = w->b_w; cj.dst[cj.count] = pb16; cj.n4[cj.count++] = (size_t)H * D / 4;
+      }
+    }
+    e = launch_cast16(cj, gemm_prec, st);
+    if (e != hipSuccess) return (int)e;
+    e = launch_linear16(x16, w16, emb, (int)n_tokens, D, desc->input_dim, ep, st);
+  } else {
+    e = launch_linear(x, w->emb_w, emb, (int)n_tokens, D, desc->input_dim, ep, st);
+  }
+  if (e != hipSuccess) return (int)e;
+  if (desc->has_rrt) {
+    rc = encoder_forward(&desc->enc, &w->enc, emb, y, n_tokens, enc_ws, enc_bytes, stream, nullptr, nullptr, nullptr,
+                         pool16 ? y16 : nullptr, &y16_done);
+    if (rc) return rc;
+  }
+  const bool p16 = pool16 && y16_done;
+  ep.bias = w->a_b;
+  ep.act = RRT_ACT_TANH;
+  e = p16 ? launch_linear16(y16, pa16, cws.hid_a, (int)n_tokens, H, D, ep, st)
+          : launch_linear(y, w->a_w, cws.hid_a, (int)n_tokens, H, D, ep, st);
+  if (e != hipSuccess) return (int)e;
+  if (desc->gated) {
+    ep.bias = w->b_b;
+    ep.act = RRT_ACT_SIGMOID;
+    e = p16 ? launch_linear16(y16, pb16, cws.hid_b, (int)n_tokens, H, D, ep, st)
+            : launch_linear(y, w->b_w, cws.hid_b, (int)n_tokens, H, D, ep, st);
+    if (e != hipSuccess) return (int)e;
+  }
+  float* raw = a_raw ? a_raw : cws.a_raw;
+  float* at = attn ? attn : (topk_idx ? cws.attn : nullptr);
+  e = launch_branch_pool(y, cws.hid_a, desc->gated ? cws.hid_b : nullptr, w->c_w, w->c_b, w->cls_w, w->cls_b,
+                         features ? features : cws.pooled, logits, at, raw, cws.part, desc->per_branch, desc->n_classes,
+                         (int)n_tokens, D, H, K, st);
+  if (e != hipSuccess) return (int)e;
+  if (topk_idx) e = launch_topk_rows(at, (long long*)topk_idx, K, (int)n_tokens, desc->k_sample, st);
+  return (int)e;
 }
 
 }  // extern "C"

@@ -241,6 +241,19 @@ hipError_t launch_pool_backward(const float* y, const float* hid_a, const float*
                                 const float* c_ext, float* dy, float* dhid_a, float* dhid_b, float* dwcb, float* part, int N,
                                 int dim, int hid, hipStream_t st);
 
+// CLAM heads (clam_pool.hip): K attention branches from one pass over y, their adjoint, top-k of rows
+size_t branch_pool_part_floats(int N, int dim, int K);
+size_t branch_pool_backward_part_floats(int N, int hid, int K);
+size_t branch_pool_merge_lds(int N, int dim);
+size_t branch_pool_backward_lds(int dim, int hid, int K);
+hipError_t launch_branch_pool(const float* y, const float* hid_a, const float* hid_b, const float* wc, const float* bc,
+                              const float* cls_w, const float* cls_b, float* pooled, float* logits, float* attn, float* a_raw,
+                              float* part, int per_branch, int n_classes, int N, int dim, int hid, int K, hipStream_t st);
+hipError_t launch_branch_pool_backward(const float* y, const float* hid_a, const float* hid_b, const float* wc, const float* attn,
+                                       const float* pooled, const float* d_pooled, const float* d_raw, float* dy, float* dhid_a,
+                                       float* dhid_b, float* dwcb, float* part, int N, int dim, int hid, int K, hipStream_t st);
+hipError_t launch_topk_rows(const float* x, long long* out, int rows, int N, int k, hipStream_t st);
+
 // ---- row f2 building blocks (backward)
 // nn.Linear backward: dX = dY W (forward GEMM on a transposed W), dW = dY^T X (split-K TN kernel), db = colsum(dY)
 size_t linear_bwd_workspace(int M, int N, int K);

@@ -158,3 +158,21 @@ def mil_state(input_dim=1024, n_classes=2, da_bias=False, da_gated=False, da_act
     out["predictor.weight"] = (uniform("mil/pred.w", (n_classes, D), -1, 1) / np.sqrt(D)).astype(np.float32)
     out["predictor.bias"] = uniform("mil/pred.b", (n_classes,), -0.05, 0.05)
     return out
+
+
+def clam_head_state(shapes, tag):
+    """Closed-form parameters for a CLAM head (rrt_mil_amd.CLAM_SB / CLAM_MB without the encoder's entries): ``shapes`` is an
+    ordered {state_dict key: shape}.  Weights N(0, 1) * gain / sqrt(fan_in) -- gain 1.2 on the score Linear (attention_c / the
+    last Linear of Attn_Net.module), so that the attention over a bag is visibly non-uniform -- biases uniform in +-0.1,
+    ``instance_loss_fn.labels`` = arange."""
+    out = {}
+    for key, shape in shapes.items():
+        shape = tuple(shape)
+        if key.endswith("labels"):
+            out[key] = np.arange(shape[0], dtype=np.int64)
+        elif key.endswith(".bias"):
+            out[key] = uniform(f"clam/{tag}/{key}", shape, -0.1, 0.1)
+        else:
+            score = "attention_c" in key or (".module." in key and ".module.0." not in key)
+            out[key] = (normal(f"clam/{tag}/{key}", shape) * ((1.2 if score else 1.0) / np.sqrt(shape[-1]))).astype(np.float32)
+    return out

@@ -24,6 +24,13 @@ int64_t ceil_sqrt(int64_t n) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// a failed launch (or any other HIP call) ends the entry point with the HIP error as its return code
+#define RRT_TRY(call)                     \
+  do {                                    \
+    const hipError_t e_ = (call);         \
+    if (e_ != hipSuccess) return (int)e_; \
+  } while (0)
+
 struct Workspace {
   float *uo, *qkv, *xa, *xb, *mean_rstd, *logits, *wdisp, *rep, *rep_qkv, *rep_o, *rep2, *v8, *hid;
   float *ffn_ln, *ffn_hid, *xp;
@@ -132,19 +139,201 @@ int check_desc(const rrt_encoder_desc* d, int64_t N) {
   return RRT_OK;
 }
 
+// The two grids every encoder entry point needs -- the R-MSA layers' (g; zero when there is no such layer) and CR-MSA's, which
+// never receives region_num / region_size / min_region_* (modules/rrt.py:148): 8 x 8 -- and check_desc in front of them.
+int region_grids(const rrt_encoder_desc* d, int64_t N, rrt_grid* g, rrt_grid* g8) {
+  *g = rrt_grid{};
+  if (d->n_rmsa_layers > 0) {
+    int rc = rrt_region_grid(N, d->region_num, d->region_size, d->min_region_num, d->min_region_ratio, g);
+    if (rc) return rc;
+  }
+  return rrt_region_grid(N, 8, 0, 0, 0.f, g8);
+}
+// (an entry point with conditions of its own between the two steps calls them one by one: the order decides which error a
+// call with several faults reports)
+int resolve_grids(const rrt_encoder_desc* d, int64_t N, rrt_grid* g, rrt_grid* g8) {
+  int rc = check_desc(d, N);
+  return rc ? rc : region_grids(d, N, g, g8);
+}
+
+// one region that holds the whole bag in token order: slot == token, for GEMMs whose residual is not partitioned (the FFN)
+GridDev identity_grid(int64_t N) {
+  GridDev g{};
+  const int Hs = (int)ceil_sqrt(N);
+  g.L = (int)N;
+  g.H = g.s = Hs;
+  g.rs = 1;
+  g.P = g.Np = Hs * Hs;
+  g.inv_H = g.inv_s = 1.0f / (float)Hs;
+  g.inv_rs = 1.0f;
+  g.inv_P = 1.0f / (float)g.P;
+  g.Rt = 1;
+  return g;
+}
+
+// epilogue of a qkv projection: bias, then the q columns scaled by head_dim ** -0.5 (modules/rmsa.py:65,103)
+LinearEpilogue qkv_epilogue(const float* bias, int dim, int heads, int prec) {
+  LinearEpilogue ep{};
+  ep.prec = prec;
+  ep.bias = bias;
+  ep.q_cols = dim;
+  ep.q_scale = 1.0f / sqrtf((float)(dim / heads));
+  return ep;
+}
+
+// epilogue of an out-projection: bias, un-partition by g, residual (rmsa.py:131,41-54; rrt.py:125)
+LinearEpilogue proj_epilogue(const float* bias, const float* resid, const GridDev& g, int prec) {
+  LinearEpilogue ep{};
+  ep.prec = prec;
+  ep.bias = bias;
+  ep.resid = resid;
+  ep.g = g;
+  return ep;
+}
+
 hipError_t inner_attention(const float* u, int n_regions, int P, const rrt_attn_weights& w, int dim,
                            int heads, int epeg_k, float* qkv, float* o, int prec, bool solo, hipStream_t st) {
   const int M = n_regions * P;
-  LinearEpilogue ep{};
-  ep.prec = prec;
+  LinearEpilogue ep = qkv_epilogue(w.qkv_b, dim, heads, prec);
   ep.solo = solo;
-  ep.bias = w.qkv_b;
-  ep.q_cols = dim;
-  ep.q_scale = 1.0f / sqrtf((float)(dim / heads));   // head_dim ** -0.5, modules/rmsa.py:65,103
   hipError_t e = launch_linear(u, w.qkv_w, qkv, M, 3 * dim, dim, ep, st);
   if (e != hipSuccess) return e;
   return launch_region_attention(qkv, epeg_k > 0 ? w.pe_w : nullptr, o, n_regions, P, dim, heads,
                                  epeg_k, st);
+}
+
+// ---- the kernel plan of one forward: which launch sequence its R-MSA layers and its CR-MSA front take.  A pure function of
+// the descriptor, the two grids and "the call stops before CR-MSA" (no workspace pointer, no state between calls):
+// encoder_forward launches from it, rrt_encoder_plan reports it.  Where a kernel needs a workspace buffer that carve() only
+// hands out under a condition, that condition is restated here next to carve's name.
+enum class LayerKind {
+  Pair16Merged,   // 16-bit pair kernel with the out-projection as a phase of its launch (tuning builds only)
+  Fused16,        // 16-bit fused kernel, then the out-projection on 16-bit operands
+  FusedX3,        // RRT_COMPUTE_F32X3: fused kernel and out-projection on split (hi, lo) bf16 images
+  EpegVariant,    // EPEG ablations (epeg_2d, epeg_type = value_*): unfused, with their own kernels (epeg_variants.hip)
+  FusedProj,      // exact fp32: fused kernel with the out-projection as a later phase of the same launch
+  Fused,          // fused kernel, then the out-projection GEMM
+  Unfused,        // qkv GEMM, region attention, out-projection GEMM
+};
+enum class FrontKind { None, Mlp, Parts, RegionInFlight, Region4, Region, Stream4, TwoKernel };
+enum class CastKind { None, Images16, Split };
+struct EncoderPlan {
+  LayerKind layer;   // of every R-MSA layer (they share shape and mode); not looked at when there is none
+  bool parts;        // the last R-MSA layer also leaves the CR-MSA row records (FusedProj only)
+  bool gated;        // the layer's core launch takes the phase gate when the call has one
+  bool attn_hd;      // Unfused: the attention is region_attn_hd's (launch_region_attention decides that; reported only)
+  CastKind casts;    // the R-MSA layers' weight images this call writes
+  bool inner16;      // CR-MSA's inner MSA on the 16-bit kernels (its weight images ride with the cast launch)
+  FrontKind front;   // CR-MSA's first pass: logits + combine
+};
+
+// smallest CR-MSA region (tokens) that takes crmsa_stream4_kernel instead of crmsa_region4_kernel (A/B builds:
+// -DRRT_STREAM4_MIN_P=16)
+#ifndef RRT_STREAM4_MIN_P
+#define RRT_STREAM4_MIN_P 145
+#endif
+
+EncoderPlan plan_encoder(const rrt_encoder_desc& d, const rrt_grid& g, const rrt_grid& g8, bool stops_before_crmsa) {
+  EncoderPlan p{};
+  p.layer = LayerKind::Unfused;
+  const int D = d.dim;
+  // RRT_COMPUTE_F32X3 concerns the R-MSA layers' two big projections; everything else of the call is exact fp32
+  const bool want_x3 = d.compute == RRT_COMPUTE_F32X3;
+  const int compute = want_x3 ? RRT_COMPUTE_F32 : d.compute;
+  // Reduced-precision modes: every tensor that is only a matrix-core operand (LayerNorm output u, the weights, the attention
+  // output O) lives in HBM in 16 bits; 64-element K tiles
+  const bool lowp = compute != RRT_COMPUTE_F32 && D % 64 == 0;
+  const GridDev gd8 = to_dev(g8);
+  // CR-MSA's inner MSA over the 64 k representatives on the same 16-bit kernels (one fused launch + one GEMM instead
+  // of GEMM + attention + GEMM on fp32 data): head dim 64 only (crmsa_heads = dim / 64)
+  p.inner16 = d.cr_msa && lowp && rmsa_fused16_supported(64, D, d.crmsa_heads, 0);
+  if (d.n_rmsa_layers > 0) {
+    const GridDev gd = to_dev(g);
+    const int R = gd.rs * gd.rs, heads = d.n_heads, ek = d.epeg ? d.epeg_k : 0;
+    const bool rows_ok = rmsa_fused_supported_rows(gd.Np, D);
+    static const bool want_merged16 = rrt_tune_env("RRT_PAIR16_PROJ") != nullptr;
+    if (d.epeg && (d.epeg_2d || d.epeg_type != RRT_EPEG_ATTN)) {
+      p.layer = LayerKind::EpegVariant;
+    } else if (lowp && rmsa_fused16_supported(gd.P, D, heads, ek) && rows_ok) {
+      // round 6: bags of at least two rounds of (pair, head) items (N = 30000 at region_num = 16: four) CAN take the
+      // out-projection as a phase of the pair launch's blocks (rmsa_pair16.hip, PROJ; bit-identical, tested) -- built on the
+      // round-5 review's request and MEASURED SLOWER than the two launches: 109-116 us against 64.5 + 35.6 at N = 30000
+      // (profiles/r06_trace_pair16_proj.txt: a slab costs a block 25 K cycles -- 13 K of DMA-issue-bound K loop, the same
+      // bound the separate projection runs at with two blocks per CU hiding each other's prologue and epilogue -- plus 4 K
+      // waiting for the write-through O stores; the block owns its CU, so nothing overlaps the slab).  Off unless a tuning
+      // build asks for it (RRT_PAIR16_PROJ=1).  (carve: its arrival counters, proj_cnt, exist whenever n_rmsa_layers > 0)
+      p.layer = want_merged16 && rmsa_pair16_proj_supported(R, gd.P, D, heads, ek) ? LayerKind::Pair16Merged : LayerKind::Fused16;
+    } else if (want_x3 && D % 256 == 0 && rmsa_fused_x3_supported(gd.P, D, heads, ek) && rows_ok) {
+      // the qkv and proj GEMMs emulated in fp32 on the bf16 matrix cores (operands as (hi, lo) bf16 pairs, three MFMAs per
+      // product; rmsa_fused_x3.hip, cast16.hip); attention and everything else as F32.
+      // dim % 256 == 0 only: at other widths the LayerNorm-type kernels keep their lane-predicated column guards, and those
+      // mis-summed now and then with split-kernel waves co-resident (root cause not established) -- such
+      // widths get the exact fp32 kernels instead (more accurate than what was asked for)
+      p.layer = LayerKind::FusedX3;
+    } else if (compute == RRT_COMPUTE_F32 && rows_ok && rmsa_fused_proj_supported(R, gd.P, D, heads, ek, compute)) {
+      // the exact fp32 path of bags that fill the chip twice over: fused R-MSA kernel with the out-projection + un-partition
+      // + residual as a later phase of the same launch's blocks (rmsa_fused.hip, PROJ): one launch per R-MSA layer
+      // (carve: proj_cnt, as above)
+      p.layer = LayerKind::FusedProj;
+      // CR-MSA's first pass as a by-product of the last R-MSA layer's projection slabs: that layer's output must BE CR-MSA's
+      // input (no FFN behind the attention, not the batch entry point's per-bag stop), phi a plain parameter, 64-column slabs
+      // (carve: the records, cr_pstat, exist when cr_msa, n_rmsa_layers > 0 and dim % 64 == 0) -- and the forward has the GPU
+      // to itself (rrt_encoder_desc.solo): the statistics cost the merged launch ~3 us of matrix-pipe time and save ~6 us of
+      // the latency-bound CR-MSA front -- one bag in flight 0.2238 -> 0.2218 ms, but with four bags in flight the tail hides
+      // behind other bags' tails anyway and the matrix pipe is the scarce thing: 5.26 k against 5.31 k slides/s (round 5,
+      // same box); likewise k > 4 representatives (twice the record) stay with the region kernels
+      p.parts = d.solo != 0 && d.cr_msa && !d.crmsa_mlp && !d.ffn && d.crmsa_k <= 4 && !stops_before_crmsa && D % 64 == 0 &&
+                crmsa_combine_parts_supported(D, d.crmsa_k, gd8);
+    } else if (rmsa_fused_supported(gd.P, D, heads, ek) && rows_ok) {
+      // qkv projection + EPEG + attention in one kernel per (region, head): qkv never reaches HBM
+      p.layer = LayerKind::Fused;
+    } else {
+      p.attn_hd = region_attention_hd_supported(gd.P, D, heads, ek);
+    }
+    // the gate only pays for launches that fill the matrix pipes of the whole chip on their own: the fused
+    // kernels on regions of >= 113 tokens (measured on the configs[4] mix: gating small or unfused bags costs 5 %)
+    p.gated = gd.P > 112 && p.layer != LayerKind::EpegVariant && p.layer != LayerKind::Unfused;
+    // The images are written whenever a reduced / emulated mode is asked for -- whether or not THIS bag's regions take the
+    // 16-bit kernels: the workspace (and the caller's validity key) outlives the bag, and the next, smaller bag on it may
+    // take them (a 20 k-token bag followed by a 9 k-token one).
+    if (p.layer != LayerKind::EpegVariant) p.casts = lowp ? CastKind::Images16 : want_x3 ? CastKind::Split : CastKind::None;
+  }
+  if (!d.cr_msa || stops_before_crmsa) return p;
+  const int k = d.crmsa_k;
+  // carve: crmsa_region4 / crmsa_stream4's partial records and arrival counters (cr_part, cr_cnt) exist when there is an R-MSA
+  // layer -- whose out-projection also zeroes the counters
+  const bool has_counters = d.n_rmsa_layers > 0;
+  static const bool no_region_inflight = rrt_tune_env("RRT_NO_REGION_INFLIGHT") != nullptr;
+  static const bool region_lowp = rrt_tune_env("RRT_REGION_INFLIGHT_LOWP") != nullptr;      // (A/B: also in the 16-bit modes)
+  if (d.crmsa_mlp) {
+    p.front = FrontKind::Mlp;
+  } else if (p.parts) {
+    p.front = FrontKind::Parts;
+  } else if (!no_region_inflight && !d.solo && p.layer != LayerKind::FusedX3 && (compute == RRT_COMPUTE_F32 || region_lowp) &&
+             crmsa_region_supported(D, k, gd8)) {
+    // round 6: exact fp32 with SEVERAL bags in flight -- logits + combine as ONE sixteen-wave block per region
+    // (crmsa_region_kernel, its k = 1 .. 3 forms with gamma . phi in registers): 64 blocks, so three quarters of the chip stay
+    // with the other bags' fused R-MSA launches, which is what the line is made of (the fused launches' union is 187 of the
+    // 189 us a bag takes).  Same box, four bags in flight: 5.30-5.31 k -> 5.36-5.38 k slides/s with the round-1 kernel
+    // (profiles/r06_region1_in_flight_ab.txt); one bag in flight it loses (20 us on a quarter of the chip): the hint decides.
+    // The 16-bit modes keep crmsa_region4 (their chip-wide kernels are short: a 64-block front becomes the critical path).
+    p.front = FrontKind::RegionInFlight;
+  } else if (has_counters && crmsa_region4_supported(D, k, gd8) && gd8.P < RRT_STREAM4_MIN_P) {
+    // logits + combine in one pass over x1: four blocks per region, the last to arrive merges (crmsa_region4_kernel).
+    // Regions of more than 144 tokens (8 / 16 blocks per region: the kernel covers them, tests) stay with the two chip-wide
+    // kernels: measured on MI355X (tools/bench_crmsa.py) the merge of 8-16 partial records per region costs more than the
+    // second pass over x1 -- N = 15000: 36 vs 24 us, N = 30000: 46-74 vs 39 us.
+    p.front = FrontKind::Region4;
+  } else if (crmsa_region_enabled() && crmsa_region_supported(D, k, gd8)) {
+    p.front = FrontKind::Region;
+  } else if (has_counters && gd8.P >= RRT_STREAM4_MIN_P && crmsa_stream4_supported(D, k, gd8)) {
+    // round 6: regions of more than 144 tokens in ONE pass over x1 as well -- four blocks per region that stream their rows
+    // with an online softmax per wave, crmsa_region4's records and merge (crmsa_stream4_kernel)
+    p.front = FrontKind::Stream4;
+  } else {
+    p.front = FrontKind::TwoKernel;
+  }
+  return p;
 }
 
 }  // namespace
@@ -213,58 +402,31 @@ int rrt_region_grid(int64_t L, int32_t region_num, int32_t region_size, int32_t 
 
 int rrt_encoder_workspace_size(const rrt_encoder_desc* desc, int64_t n_tokens, size_t* bytes) {
   if (!bytes) return RRT_E_INVALID;
-  int rc = check_desc(desc, n_tokens);
-  if (rc) return rc;
   rrt_grid g{}, g8{};
-  if (desc->n_rmsa_layers > 0) {
-    rc = rrt_region_grid(n_tokens, desc->region_num, desc->region_size, desc->min_region_num,
-                         desc->min_region_ratio, &g);
-    if (rc) return rc;
-  }
-  rc = rrt_region_grid(n_tokens, 8, 0, 0, 0.f, &g8);
+  int rc = resolve_grids(desc, n_tokens, &g, &g8);
   if (rc) return rc;
   *bytes = carve(*desc, n_tokens, g, g8, nullptr).bytes;
   return RRT_OK;
 }
 
-// Mirrors the kernel choice of encoder_forward's R-MSA layer loop (same predicates, same order); measurement only.
+// The forward's own plan (plan_encoder) for the R-MSA layers, as RRT_PLAN_* bits; measurement only.
 int rrt_encoder_plan(const rrt_encoder_desc* desc, int64_t n_tokens, int32_t* flags) {
   if (!flags) return RRT_E_INVALID;
   *flags = 0;
-  int rc = check_desc(desc, n_tokens);
+  rrt_grid g{}, g8{};
+  int rc = resolve_grids(desc, n_tokens, &g, &g8);
   if (rc) return rc;
   if (desc->n_rmsa_layers <= 0) return RRT_OK;
-  rrt_grid g{};
-  rc = rrt_region_grid(n_tokens, desc->region_num, desc->region_size, desc->min_region_num, desc->min_region_ratio, &g);
-  if (rc) return rc;
-  const GridDev gd = to_dev(g);
-  const int D = desc->dim, ek = desc->epeg ? desc->epeg_k : 0;
-  const bool want_x3 = desc->compute == RRT_COMPUTE_F32X3;
-  const int compute = want_x3 ? RRT_COMPUTE_F32 : desc->compute;
-  const bool epeg_variant = desc->epeg && (desc->epeg_2d || desc->epeg_type != RRT_EPEG_ATTN);
-  if (epeg_variant) return RRT_OK;
-  const bool rows_ok = rmsa_fused_supported_rows(gd.Np, D);
-  if (compute != RRT_COMPUTE_F32 && D % 64 == 0 && rmsa_fused16_supported(gd.P, D, desc->n_heads, ek) && rows_ok) {
-    *flags = RRT_PLAN_FUSED16;
-    return RRT_OK;
+  const EncoderPlan plan = plan_encoder(*desc, g, g8, false);
+  switch (plan.layer) {
+    case LayerKind::Pair16Merged:
+    case LayerKind::Fused16: *flags = RRT_PLAN_FUSED16; break;
+    case LayerKind::FusedX3: *flags = RRT_PLAN_FUSED_X3; break;
+    case LayerKind::FusedProj: *flags = RRT_PLAN_FUSED | RRT_PLAN_FUSED_PROJ | (plan.parts ? RRT_PLAN_CRMSA_PARTS : 0); break;
+    case LayerKind::Fused: *flags = RRT_PLAN_FUSED; break;
+    case LayerKind::Unfused: *flags = plan.attn_hd ? RRT_PLAN_ATTN_HD : 0; break;      // qkv linear + region_attn_hd
+    case LayerKind::EpegVariant: break;
   }
-  if (want_x3 && D % 256 == 0 && rmsa_fused_x3_supported(gd.P, D, desc->n_heads, ek) && rows_ok) {
-    *flags = RRT_PLAN_FUSED_X3;
-    return RRT_OK;
-  }
-  if (rmsa_fused_supported(gd.P, D, desc->n_heads, ek) && rows_ok) {
-    *flags = RRT_PLAN_FUSED;
-    if (compute == RRT_COMPUTE_F32 && rmsa_fused_proj_supported(gd.rs * gd.rs, gd.P, D, desc->n_heads, ek, compute)) {
-      *flags |= RRT_PLAN_FUSED_PROJ;
-      rrt_grid g8{};
-      if (rrt_region_grid(n_tokens, 8, 0, 0, 0.f, &g8) == RRT_OK && desc->solo != 0 && desc->crmsa_k <= 4 && desc->cr_msa &&
-          !desc->crmsa_mlp && !desc->ffn && D % 64 == 0 &&
-          crmsa_combine_parts_supported(D, desc->crmsa_k, to_dev(g8)))
-        *flags |= RRT_PLAN_CRMSA_PARTS;
-    }
-    return RRT_OK;
-  }
-  if (region_attention_hd_supported(gd.P, D, desc->n_heads, ek)) *flags = RRT_PLAN_ATTN_HD;   // qkv linear + region_attn_hd
   return RRT_OK;
 }
 
@@ -282,45 +444,14 @@ static int ffn_apply(const rrt_encoder_desc* desc, const rrt_attn_weights& lw, c
                      const Workspace& ws, int64_t N, hipStream_t st) {
   if (!lw.norm2_w || !lw.norm2_b || !lw.fc1_w || !lw.fc1_b || !lw.fc2_w || !lw.fc2_b) return RRT_E_INVALID;
   const int D = desc->dim;
-  GridDev gid{};
-  const int Hs = (int)ceil_sqrt(N);
-  gid.L = (int)N;
-  gid.H = gid.s = Hs;
-  gid.rs = 1;
-  gid.P = gid.Np = Hs * Hs;
-  gid.inv_H = gid.inv_s = 1.0f / (float)Hs;
-  gid.inv_rs = 1.0f;
-  gid.inv_P = 1.0f / (float)gid.P;
-  gid.Rt = 1;
-  hipError_t fe = launch_layernorm(xi, nullptr, lw.norm2_w, lw.norm2_b, ws.ffn_ln, (int)N, D, st);
-  if (fe != hipSuccess) return (int)fe;
+  RRT_TRY(launch_layernorm(xi, nullptr, lw.norm2_w, lw.norm2_b, ws.ffn_ln, (int)N, D, st));
   LinearEpilogue e1{};
   e1.prec = desc->compute;
   e1.bias = lw.fc1_b;
   e1.act = desc->ffn_act;
-  fe = launch_linear(ws.ffn_ln, lw.fc1_w, ws.ffn_hid, (int)N, desc->ffn_hidden, D, e1, st);
-  if (fe != hipSuccess) return (int)fe;
-  LinearEpilogue e2{};
-  e2.prec = desc->compute;
-  e2.bias = lw.fc2_b;
-  e2.resid = xi;
-  e2.g = gid;
-  return (int)launch_linear(ws.ffn_hid, lw.fc2_w, xo, (int)N, D, desc->ffn_hidden, e2, st);
-}
-
-// CR-MSA's first pass as a by-product of the last R-MSA layer's projection slabs: that layer's output must BE CR-MSA's
-// input (no FFN behind the attention, not the batch entry point's per-bag stop), phi a plain parameter, 64-column slabs
-// ... and the forward has the GPU to itself (rrt_encoder_desc.solo): the statistics cost the merged launch ~3 us of matrix-pipe
-// time and save ~6 us of the latency-bound CR-MSA front -- one bag in flight 0.2238 -> 0.2218 ms, but with four bags in
-// flight the tail hides behind other bags' tails anyway and the matrix pipe is the scarce thing: 5.26 k against 5.31 k
-// slides/s (round 5, same box); likewise k > 4 representatives (twice the record) stay with the region kernels
-// smallest CR-MSA region (tokens) that takes crmsa_stream4_kernel instead of crmsa_region4_kernel (A/B builds: -DRRT_STREAM4_MIN_P=16)
-#ifndef RRT_STREAM4_MIN_P
-#define RRT_STREAM4_MIN_P 145
-#endif
-static bool crmsa_parts_wanted(const rrt_encoder_desc& d, const Workspace& ws, const GridDev& g8, bool stops_before_crmsa) {
-  return d.solo != 0 && d.cr_msa && !d.crmsa_mlp && !d.ffn && d.crmsa_k <= 4 && !stops_before_crmsa && ws.cr_pstat != nullptr &&
-         crmsa_combine_parts_supported(d.dim, d.crmsa_k, g8);
+  RRT_TRY(launch_linear(ws.ffn_ln, lw.fc1_w, ws.ffn_hid, (int)N, desc->ffn_hidden, D, e1, st));
+  return (int)launch_linear(ws.ffn_hid, lw.fc2_w, xo, (int)N, D, desc->ffn_hidden,
+                            proj_epilogue(lw.fc2_b, xi, identity_grid(N), desc->compute), st);
 }
 
 static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_weights* w, const float* x,
@@ -334,39 +465,26 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
   int rc = check_desc(desc_in, n_tokens);
   if (rc) return rc;
   if (handover_err_peek(false)) return RRT_E_HANDOVER;    // (a host read of pinned memory; rrt_hip.h, rrt_device_error)
-  // RRT_COMPUTE_F32X3 concerns the R-MSA layers' two big projections (below); every other GEMM of the call is exact fp32
+  rrt_grid g{}, g8{};
+  rc = region_grids(desc_in, n_tokens, &g, &g8);
+  if (rc) return rc;
+  // RRT_COMPUTE_F32X3 concerns the R-MSA layers' two big projections (plan_encoder); every other GEMM of the call is exact fp32
   rrt_encoder_desc dloc = *desc_in;
-  const bool want_x3 = dloc.compute == RRT_COMPUTE_F32X3;
-  if (want_x3) dloc.compute = RRT_COMPUTE_F32;
+  if (dloc.compute == RRT_COMPUTE_F32X3) dloc.compute = RRT_COMPUTE_F32;
   const rrt_encoder_desc* const desc = &dloc;
   hipStream_t st = (hipStream_t)stream;
   const int D = desc->dim;
   const int64_t N = n_tokens;
-  rrt_grid g{}, g8{};
-  if (desc->n_rmsa_layers > 0) {
-    rc = rrt_region_grid(N, desc->region_num, desc->region_size, desc->min_region_num,
-                         desc->min_region_ratio, &g);
-    if (rc) return rc;
-  }
-  // CR-MSA never receives region_num / region_size / min_region_* (modules/rrt.py:148): grid 8x8
-  rc = rrt_region_grid(N, 8, 0, 0, 0.f, &g8);
-  if (rc) return rc;
   Workspace ws = carve(*desc, N, g, g8, nullptr);
   if (!workspace || workspace_bytes < ws.bytes) return RRT_E_WORKSPACE;
   ws = carve(*desc, N, g, g8, (char*)workspace);
+  const EncoderPlan plan = plan_encoder(*desc_in, g, g8, rmsa_out != nullptr);
 
-  hipError_t e = hipSuccess;
-#define RRT_TRY(call)            \
-  do {                           \
-    e = (call);                  \
-    if (e != hipSuccess) return (int)e; \
-  } while (0)
   // optional stage-boundary events (bench.py / profiling): events[i] recorded after stage i-1
-#define RRT_MARK(i)                                                          \
-  do {                                                                       \
-    if (events && events[i]) RRT_TRY(hipEventRecord((hipEvent_t)events[i], st)); \
-  } while (0)
-  RRT_MARK(RRT_EV_START);
+  auto mark = [&](int i) -> hipError_t {
+    return (events && events[i]) ? hipEventRecord((hipEvent_t)events[i], st) : hipSuccess;
+  };
+  RRT_TRY(mark(RRT_EV_START));
 
   auto ffn_block = [&](const rrt_attn_weights& lw, const float* xi, float* xo) -> int {
     return ffn_apply(desc, lw, xi, xo, ws, N, st);
@@ -376,9 +494,7 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
   // PEG / PPEG (ablation): before the first layer (pos_pos = -1) or before layer index 1 (pos_pos = 0), rrt.py:181-187
   auto pos_embed = [&]() -> int {
     if (!w->pos_w[0] || (desc->pos == RRT_POS_PPEG && (!w->pos_w[1] || !w->pos_w[2]))) return RRT_E_INVALID;
-    hipError_t pe = launch_peg(xin, w->pos_w, w->pos_b, ws.xp, (int)N, D, desc->peg_k, desc->peg_1d,
-                               desc->pos == RRT_POS_PPEG, st);
-    if (pe != hipSuccess) return (int)pe;
+    RRT_TRY(launch_peg(xin, w->pos_w, w->pos_b, ws.xp, (int)N, D, desc->peg_k, desc->peg_1d, desc->pos == RRT_POS_PPEG, st));
     xin = ws.xp;
     return RRT_OK;
   };
@@ -386,62 +502,57 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
     rc = pos_embed();
     if (rc) return rc;
   }
-  // Reduced-precision modes on regions the 16-bit fused kernel covers: every tensor that is only a matrix-core
-  // operand (LayerNorm output u, the weights, the attention output O) lives in HBM in 16 bits.  The weights are
-  // cast once per call (one launch for all layers) unless the caller vouches for the images already in the
-  // workspace (desc.weights16_valid; the ABI itself keeps no state).
-  // EPEG ablations (epeg_2d, epeg_type = value_*): unfused path with their own kernels (epeg_variants.hip)
-  const bool epeg_variant = desc->epeg && (desc->epeg_2d || desc->epeg_type != RRT_EPEG_ATTN);
-  // The images are written whenever a reduced / emulated mode is asked for and the caller does not vouch for them --
-  // whether or not THIS bag's regions take the 16-bit kernels: the workspace (and the caller's validity key) outlives
-  // the bag, and the next, smaller bag on it may take them (a 20 k-token bag followed by a 9 k-token one).
-  bool lowp16 = false;
-  // CR-MSA's inner MSA over the 64 k representatives on the same 16-bit kernels (one fused launch + one GEMM instead
-  // of GEMM + attention + GEMM on fp32 data): head dim 64 only (crmsa_heads = dim / 64)
-  const bool inner16 = desc->cr_msa && desc->compute != RRT_COMPUTE_F32 && D % 64 == 0 &&
-                       rmsa_fused16_supported(64, D, desc->crmsa_heads, 0);
-  if (desc->compute != RRT_COMPUTE_F32 && D % 64 == 0) {
+  // The weight images of the reduced-precision / emulated modes (plan.casts: 16-bit copies, or (hi, lo) bf16 pairs = two
+  // 16-bit values per weight; plan.inner16: CR-MSA's inner qkv / proj as well) are cast once per call, one launch for all
+  // layers, unless the caller vouches for the images already in the workspace (desc.weights16_valid; the ABI keeps no state).
+  {
+    const bool split = plan.casts == CastKind::Split;
+    const size_t per_w = split ? 2 : 1;
     Cast16Jobs jobs{};
-    if (desc->n_rmsa_layers > 0 && !epeg_variant) {
-      const GridDev gd = to_dev(g);
-      lowp16 = rmsa_fused16_supported(gd.P, D, desc->n_heads, desc->epeg ? desc->epeg_k : 0) &&
-               rmsa_fused_supported_rows(gd.Np, D);
+    auto add = [&](const float* src, uint16_t* dst, size_t n) {
+      jobs.src[jobs.count] = src; jobs.dst[jobs.count] = dst; jobs.n4[jobs.count++] = n / 4;
+    };
+    if (plan.casts != CastKind::None) {
       for (int li = 0; li < desc->n_rmsa_layers; ++li) {
         const rrt_attn_weights& lw = w->rmsa[li];
         if (!lw.qkv_w || !lw.proj_w) return RRT_E_INVALID;
-        uint16_t* base = ws.w16 + (size_t)li * 4 * D * D;
-        jobs.src[jobs.count] = lw.qkv_w; jobs.dst[jobs.count] = base; jobs.n4[jobs.count++] = (size_t)3 * D * D / 4;
-        jobs.src[jobs.count] = lw.proj_w; jobs.dst[jobs.count] = base + (size_t)3 * D * D; jobs.n4[jobs.count++] = (size_t)D * D / 4;
+        uint16_t* base = ws.w16 + (size_t)li * per_w * 4 * D * D;
+        add(lw.qkv_w, base, (size_t)3 * D * D);
+        add(lw.proj_w, base + per_w * 3 * D * D, (size_t)D * D);
       }
     }
-    if (inner16) {
+    if (plan.inner16) {
       if (!w->crmsa.qkv_w || !w->crmsa.proj_w) return RRT_E_INVALID;
-      jobs.src[jobs.count] = w->crmsa.qkv_w; jobs.dst[jobs.count] = ws.wcr16; jobs.n4[jobs.count++] = (size_t)3 * D * D / 4;
-      jobs.src[jobs.count] = w->crmsa.proj_w; jobs.dst[jobs.count] = ws.wcr16 + (size_t)3 * D * D; jobs.n4[jobs.count++] = (size_t)D * D / 4;
+      add(w->crmsa.qkv_w, ws.wcr16, (size_t)3 * D * D);
+      add(w->crmsa.proj_w, ws.wcr16 + (size_t)3 * D * D, (size_t)D * D);
     }
-    if (jobs.count && !desc->weights16_valid) RRT_TRY(launch_cast16(jobs, desc->compute, st));
+    if (jobs.count && !desc->weights16_valid) RRT_TRY(split ? launch_cast_split(jobs, st) : launch_cast16(jobs, desc->compute, st));
   }
-  // RRT_COMPUTE_F32X3: the qkv and proj GEMMs of the R-MSA layers emulated in fp32 on the bf16 matrix cores (operands
-  // as (hi, lo) bf16 pairs, three MFMAs per product; rmsa_fused_x3.hip, cast16.hip); attention and everything else as F32
-  bool x3 = false;
-  if (want_x3 && desc->n_rmsa_layers > 0 && !epeg_variant) {
-    const GridDev gd = to_dev(g);
-    // dim % 256 == 0 only: at other widths the LayerNorm-type kernels keep their lane-predicated column guards, and those
-    // mis-summed now and then with split-kernel waves co-resident (root cause not established) -- such
-    // widths get the exact fp32 kernels instead (more accurate than what was asked for)
-    x3 = D % 256 == 0 && rmsa_fused_x3_supported(gd.P, D, desc->n_heads, desc->epeg ? desc->epeg_k : 0) &&
-         rmsa_fused_supported_rows(gd.Np, D);
-    Cast16Jobs jobs{};
-    for (int li = 0; li < desc->n_rmsa_layers; ++li) {
-      const rrt_attn_weights& lw = w->rmsa[li];
-      if (!lw.qkv_w || !lw.proj_w) return RRT_E_INVALID;
-      uint16_t* base = ws.w16 + (size_t)li * 8 * D * D;          // 4 D^2 weights x 2 bf16
-      jobs.src[jobs.count] = lw.qkv_w; jobs.dst[jobs.count] = base; jobs.n4[jobs.count++] = (size_t)3 * D * D / 4;
-      jobs.src[jobs.count] = lw.proj_w; jobs.dst[jobs.count] = base + (size_t)6 * D * D; jobs.n4[jobs.count++] = (size_t)D * D / 4;
+  // The phase gate around a layer's MFMA-bound core launch (plan.gated): wait for the previous gated core of any stream, then
+  // the LayerNorm-partition mark (it brackets the kernel, not the wait); after the launch, record the gate and mark the core.
+  // Marks: layer 0 only, and none for the EPEG ablations.
+  rrt_phase_gate* const gt = (gate && plan.gated) ? gate : nullptr;
+  auto gate_record = [&]() -> hipError_t {
+    if (!gt) return hipSuccess;
+    const hipError_t ge = hipEventRecord(gt->done, st);
+    if (ge == hipSuccess) gt->armed = true;
+    return ge;
+  };
+  auto core_begin = [&](bool marks) -> hipError_t {
+    if (gt && gt->armed) {
+      const hipError_t ge = hipStreamWaitEvent(st, gt->done, 0);
+      if (ge != hipSuccess) return ge;
     }
-    if (!desc->weights16_valid) RRT_TRY(launch_cast_split(jobs, st));
-  }
-  bool parts_done = false;      // the last R-MSA layer left CR-MSA's row records in ws.cr_pstat
+    return marks ? mark(RRT_EV_LN_PARTITION) : hipSuccess;
+  };
+  auto core_end = [&](bool marks, bool record = true) -> hipError_t {
+    hipError_t ge = record ? gate_record() : hipSuccess;
+    if (ge == hipSuccess && marks) ge = mark(RRT_EV_QKV);
+    if (ge == hipSuccess && marks) ge = mark(RRT_EV_ATTN);
+    return ge;
+  };
+  // (tuning build: the two-launch fused kind holds the gate until its out-projection is queued)
+  static const bool gate_proj = rrt_tune_env("RRT_GATE_PROJ") != nullptr;
   // ---- R-MSA TransLayers: x = x + unpart(InnerAttention(part(pad(LN(x)))))  (rrt.py:117-125)
   for (int li = 0; li < desc->n_rmsa_layers; ++li) {
     if (li == 1 && desc->pos && desc->pos_pos == 0) {
@@ -449,235 +560,131 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
       if (rc) return rc;
     }
     const rrt_attn_weights& lw = w->rmsa[li];
+    const bool last = li == desc->n_rmsa_layers - 1;
     if (!lw.norm_w || !lw.norm_b || !lw.qkv_w || !lw.proj_w || !lw.proj_b) return RRT_E_INVALID;
     if (desc->epeg && !lw.pe_w) return RRT_E_INVALID;
+    if (plan.parts && last && (!w->crmsa.norm_w || !w->crmsa.norm_b || !w->phi)) return RRT_E_INVALID;
     const GridDev gd = to_dev(g);
+    const int R = gd.rs * gd.rs, ek = desc->epeg ? desc->epeg_k : 0;
+    const float* const pe_w = desc->epeg ? lw.pe_w : nullptr;
     // without FFN the layers ping-pong xa / xb; with it attention writes xa and the FFN writes xb
     // (rmsa_out: the batch entry point takes the R-MSA layers' result of each bag in its own buffer)
-    const bool to_out = rmsa_out != nullptr && li == desc->n_rmsa_layers - 1;
+    const bool to_out = rmsa_out != nullptr && last;
     float* xout = desc->ffn ? ws.xa : (to_out ? rmsa_out : ((li & 1) ? ws.xb : ws.xa));
     float* const fout = to_out ? rmsa_out : ws.xb;      // the layer's FFN output
-    const int ek = desc->epeg ? desc->epeg_k : 0;
-    if (lowp16) {
-      // u (16-bit) in the uo buffer, O (16-bit) in the qkv buffer; qkv, scores and probabilities never leave the CU
-      uint16_t* u16 = (uint16_t*)ws.uo;
-      uint16_t* o16 = (uint16_t*)ws.qkv;
-      const uint16_t* wq16 = ws.w16 + (size_t)li * 4 * D * D;
-      // round 6: bags of at least two rounds of (pair, head) items (N = 30000 at region_num = 16: four) CAN take the
-      // out-projection as a phase of the pair launch's blocks (rmsa_pair16.hip, PROJ; bit-identical, tested) -- built on the
-      // round-5 review's request and MEASURED SLOWER than the two launches: 109-116 us against 64.5 + 35.6 at N = 30000
-      // (profiles/r06_trace_pair16_proj.txt: a slab costs a block 25 K cycles -- 13 K of DMA-issue-bound K loop, the same
-      // bound the separate projection runs at with two blocks per CU hiding each other's prologue and epilogue -- plus 4 K
-      // waiting for the write-through O stores; the block owns its CU, so nothing overlaps the slab).  Off unless a tuning
-      // build asks for it (RRT_PAIR16_PROJ=1).
-      static const bool want_merged16 = rrt_tune_env("RRT_PAIR16_PROJ") != nullptr;
-      const bool merged16 = want_merged16 && ws.proj_cnt != nullptr &&
-                            rmsa_pair16_proj_supported(gd.rs * gd.rs, gd.P, D, desc->n_heads, ek);
-      RRT_TRY(launch_ln_partition16(xin, lw.norm_w, lw.norm_b, u16, D, gd, desc->compute, st, merged16 ? ws.proj_cnt : nullptr,
-                                    merged16 ? gd.rs * gd.rs / 2 : 0));
-      rrt_phase_gate* const gt16 = (gate && gd.P > 112) ? gate : nullptr;
-      if (gt16 && gt16->armed) RRT_TRY(hipStreamWaitEvent(st, gt16->done, 0));
-      if (li == 0) RRT_MARK(RRT_EV_LN_PARTITION);
-      if (merged16) {
-        PairProj pj{};
-        pj.Wp = wq16 + (size_t)3 * D * D;
+    const bool marks = li == 0 && plan.layer != LayerKind::EpegVariant;
+    // the out-projection's epilogue; its side job zeroes the CR-MSA region kernels' arrival counters
+    auto out_ep = [&](int prec) {
+      LinearEpilogue ep = proj_epilogue(lw.proj_b, xin, gd, prec);
+      ep.zero64 = ws.cr_cnt;
+      return ep;
+    };
+    switch (plan.layer) {
+      case LayerKind::Pair16Merged:
+      case LayerKind::Fused16: {
+        // u (16-bit) in the uo buffer, O (16-bit) in the qkv buffer; qkv, scores and probabilities never leave the CU
+        const bool merged16 = plan.layer == LayerKind::Pair16Merged;
+        uint16_t* u16 = (uint16_t*)ws.uo;
+        uint16_t* o16 = (uint16_t*)ws.qkv;
+        const uint16_t* wq16 = ws.w16 + (size_t)li * 4 * D * D;
+        RRT_TRY(launch_ln_partition16(xin, lw.norm_w, lw.norm_b, u16, D, gd, desc->compute, st, merged16 ? ws.proj_cnt : nullptr,
+                                      merged16 ? R / 2 : 0));
+        RRT_TRY(core_begin(marks));
+        if (merged16) {
+          PairProj pj{};
+          pj.Wp = wq16 + (size_t)3 * D * D;
+          pj.bias = lw.proj_b;
+          pj.resid = xin;
+          pj.out = xout;
+          pj.cnt = ws.proj_cnt;
+          pj.zero64 = ws.cr_cnt;
+          pj.g = gd;
+          RRT_TRY(launch_rmsa_pair16_proj(u16, wq16, lw.qkv_b, pe_w, o16, R, gd.P, D, desc->n_heads, ek, desc->compute, pj, st));
+          RRT_TRY(core_end(marks));
+        } else {
+          RRT_TRY(launch_rmsa_fused16(u16, wq16, lw.qkv_b, pe_w, o16, R, gd.P, D, desc->n_heads, ek, desc->compute, st));
+          RRT_TRY(core_end(marks));
+          LinearEpilogue ep = out_ep(desc->compute);
+          ep.solo = desc->solo != 0;          // (picks the tile shape: one bag in flight / several, launch_linear16)
+          RRT_TRY(launch_linear16(o16, wq16 + (size_t)3 * D * D, xout, gd.Np, D, D, ep, st));
+        }
+        break;
+      }
+      case LayerKind::FusedX3: {
+        // u and O as split images (4 bytes per element: the uo / qkv buffers as they are)
+        const uint16_t* wq = ws.w16 + (size_t)li * 8 * D * D;          // 4 D^2 weights x 2 bf16
+        RRT_TRY(launch_ln_partition_split(xin, lw.norm_w, lw.norm_b, ws.uo, D, gd, st));
+        RRT_TRY(core_begin(marks));
+        RRT_TRY(launch_rmsa_fused_x3(ws.uo, wq, lw.qkv_b, pe_w, ws.qkv, R, gd.P, D, desc->n_heads, ek, st));
+        RRT_TRY(core_end(marks));
+        RRT_TRY(launch_linear_split(ws.qkv, wq + (size_t)6 * D * D, xout, gd.Np, D, D, out_ep(0), st));
+        break;
+      }
+      case LayerKind::FusedProj: {
+        // one launch per layer; its arrival counters are zeroed by LayerNorm + partition
+        RRT_TRY(launch_ln_partition(xin, lw.norm_w, lw.norm_b, ws.uo, D, gd, st, ws.proj_cnt, R));
+        RRT_TRY(core_begin(marks));
+        FusedProj pj{};
+        pj.Wp = lw.proj_w;
         pj.bias = lw.proj_b;
         pj.resid = xin;
         pj.out = xout;
         pj.cnt = ws.proj_cnt;
         pj.zero64 = ws.cr_cnt;
         pj.g = gd;
-        RRT_TRY(launch_rmsa_pair16_proj(u16, wq16, lw.qkv_b, desc->epeg ? lw.pe_w : nullptr, o16, gd.rs * gd.rs, gd.P, D,
-                                        desc->n_heads, ek, desc->compute, pj, st));
-        if (gt16) { RRT_TRY(hipEventRecord(gt16->done, st)); gt16->armed = true; }
-        if (li == 0) { RRT_MARK(RRT_EV_QKV); RRT_MARK(RRT_EV_ATTN); RRT_MARK(RRT_EV_PROJ); }
-        xin = xout;
-        if (desc->ffn) {
-          rc = ffn_block(lw, xout, fout);
-          if (rc) return rc;
-          xin = fout;
+        // the LAST R-MSA layer feeding CR-MSA directly: its slabs also leave LayerNorm 2's statistics and the logits' dot
+        // products of every row (x1 is in their registers), and CR-MSA's first pass shrinks to the combine
+        if (plan.parts && last) {
+          pj.part = ws.cr_pstat;
+          pj.ln_g = w->crmsa.norm_w;
+          pj.phi = w->phi;
+          pj.k = desc->crmsa_k;
         }
-        continue;
+        RRT_TRY(launch_rmsa_fused(ws.uo, lw.qkv_w, lw.qkv_b, pe_w, ws.qkv, R, gd.P, D, desc->n_heads, ek, desc->compute, st,
+                                  nullptr, &pj));
+        RRT_TRY(core_end(marks));
+        break;
       }
-      RRT_TRY(launch_rmsa_fused16(u16, wq16, lw.qkv_b, desc->epeg ? lw.pe_w : nullptr, o16, gd.rs * gd.rs, gd.P, D,
-                                  desc->n_heads, ek, desc->compute, st));
-      if (gt16) { RRT_TRY(hipEventRecord(gt16->done, st)); gt16->armed = true; }
-      if (li == 0) { RRT_MARK(RRT_EV_QKV); RRT_MARK(RRT_EV_ATTN); }
-      LinearEpilogue ep{};
-      ep.prec = desc->compute;
-      ep.bias = lw.proj_b;
-      ep.resid = xin;
-      ep.g = gd;
-      ep.zero64 = ws.cr_cnt;
-      ep.solo = desc->solo != 0;          // (picks the tile shape: one bag in flight / several, launch_linear16)
-      RRT_TRY(launch_linear16(o16, wq16 + (size_t)3 * D * D, xout, gd.Np, D, D, ep, st));
-      if (li == 0) RRT_MARK(RRT_EV_PROJ);
-      xin = xout;
-      if (desc->ffn) {
-        rc = ffn_block(lw, xout, fout);
-        if (rc) return rc;
-        xin = fout;
+      case LayerKind::Fused: {
+        // O goes to the qkv workspace (first Np*D floats), u stays in uo
+        RRT_TRY(launch_ln_partition(xin, lw.norm_w, lw.norm_b, ws.uo, D, gd, st));
+        RRT_TRY(core_begin(marks));
+        RRT_TRY(launch_rmsa_fused(ws.uo, lw.qkv_w, lw.qkv_b, pe_w, ws.qkv, R, gd.P, D, desc->n_heads, ek, desc->compute, st));
+        RRT_TRY(core_end(marks, !gate_proj));
+        RRT_TRY(launch_linear(ws.qkv, lw.proj_w, xout, gd.Np, D, D, out_ep(desc->compute), st));
+        if (gate_proj) RRT_TRY(gate_record());
+        break;
       }
-      continue;
+      case LayerKind::Unfused: {
+        RRT_TRY(launch_ln_partition(xin, lw.norm_w, lw.norm_b, ws.uo, D, gd, st));
+        RRT_TRY(core_begin(marks));
+        RRT_TRY(launch_linear(ws.uo, lw.qkv_w, ws.qkv, gd.Np, 3 * D, D, qkv_epilogue(lw.qkv_b, D, desc->n_heads, desc->compute), st));
+        if (marks) RRT_TRY(mark(RRT_EV_QKV));
+        RRT_TRY(launch_region_attention(ws.qkv, pe_w, ws.uo, R, gd.P, D, desc->n_heads, ek, st));
+        if (marks) RRT_TRY(mark(RRT_EV_ATTN));
+        RRT_TRY(launch_linear(ws.uo, lw.proj_w, xout, gd.Np, D, D, out_ep(desc->compute), st));
+        break;
+      }
+      case LayerKind::EpegVariant: {
+        RRT_TRY(launch_ln_partition(xin, lw.norm_w, lw.norm_b, ws.uo, D, gd, st));
+        RRT_TRY(launch_linear(ws.uo, lw.qkv_w, ws.qkv, gd.Np, 3 * D, D, qkv_epilogue(lw.qkv_b, D, desc->n_heads, desc->compute), st));
+        if (desc->epeg_type == RRT_EPEG_ATTN) {           // epeg_2d: k x k stencil over the score map
+          // (regions of more than ~180 tokens: the score maps live in the workspace instead of the LDS)
+          RRT_TRY(launch_attn_scoremap(ws.qkv, lw.pe_w, ws.uo, ws.smap, R, gd.P, D, desc->n_heads, desc->epeg_k, st));
+        } else {
+          RRT_TRY(launch_value_pe(ws.qkv, lw.pe_w, lw.pe_b, ws.pe_out, R, gd.P, gd.s, D, desc->n_heads, desc->epeg_k,
+                                  desc->epeg_2d, st));
+          if (desc->epeg_type == RRT_EPEG_VALUE_BF)       // v += pe before attn @ v (rmsa.py:114-118)
+            RRT_TRY(launch_add_cols(ws.qkv + 2 * D, ws.pe_out, (size_t)gd.Np, D, 3 * D, st));
+          RRT_TRY(launch_region_attention(ws.qkv, nullptr, ws.uo, R, gd.P, D, desc->n_heads, 0, st));
+          if (desc->epeg_type == RRT_EPEG_VALUE_AF)       // x += pe after it (rmsa.py:124-129)
+            RRT_TRY(launch_add_cols(ws.uo, ws.pe_out, (size_t)gd.Np, D, D, st));
+        }
+        RRT_TRY(launch_linear(ws.uo, lw.proj_w, xout, gd.Np, D, D, out_ep(desc->compute), st));
+        break;
+      }
     }
-    if (x3) {
-      // u and O as split images (4 bytes per element: the uo / qkv buffers as they are)
-      const uint16_t* wq = ws.w16 + (size_t)li * 8 * D * D;
-      RRT_TRY(launch_ln_partition_split(xin, lw.norm_w, lw.norm_b, ws.uo, D, gd, st));
-      rrt_phase_gate* const gt3 = (gate && gd.P > 112) ? gate : nullptr;
-      if (gt3 && gt3->armed) RRT_TRY(hipStreamWaitEvent(st, gt3->done, 0));
-      if (li == 0) RRT_MARK(RRT_EV_LN_PARTITION);
-      RRT_TRY(launch_rmsa_fused_x3(ws.uo, wq, lw.qkv_b, desc->epeg ? lw.pe_w : nullptr, ws.qkv, gd.rs * gd.rs, gd.P, D,
-                                   desc->n_heads, ek, st));
-      if (gt3) { RRT_TRY(hipEventRecord(gt3->done, st)); gt3->armed = true; }
-      if (li == 0) { RRT_MARK(RRT_EV_QKV); RRT_MARK(RRT_EV_ATTN); }
-      LinearEpilogue ep{};
-      ep.bias = lw.proj_b;
-      ep.resid = xin;
-      ep.g = gd;
-      ep.zero64 = ws.cr_cnt;
-      RRT_TRY(launch_linear_split(ws.qkv, wq + (size_t)6 * D * D, xout, gd.Np, D, D, ep, st));
-      if (li == 0) RRT_MARK(RRT_EV_PROJ);
-      xin = xout;
-      if (desc->ffn) {
-        rc = ffn_block(lw, xout, fout);
-        if (rc) return rc;
-        xin = fout;
-      }
-      continue;
-    }
-    // the exact fp32 path of bags that fill the chip twice over: fused R-MSA kernel with the out-projection as a
-    // later phase of the same launch (rmsa_fused.hip, PROJ); its arrival counters are zeroed by LayerNorm + partition
-    const bool merged = !epeg_variant && desc->compute == RRT_COMPUTE_F32 && ws.proj_cnt != nullptr &&
-                        rmsa_fused_supported_rows(gd.Np, D) &&
-                        rmsa_fused_proj_supported(gd.rs * gd.rs, gd.P, D, desc->n_heads, ek, desc->compute);
-    const bool parts = merged && li == desc->n_rmsa_layers - 1 && !epeg_variant &&
-                       rmsa_fused_supported(gd.P, D, desc->n_heads, ek) &&
-                       crmsa_parts_wanted(*desc, ws, to_dev(g8), rmsa_out != nullptr);
-    if (parts && (!w->crmsa.norm_w || !w->crmsa.norm_b || !w->phi)) return RRT_E_INVALID;
-    RRT_TRY(launch_ln_partition(xin, lw.norm_w, lw.norm_b, ws.uo, D, gd, st, merged ? ws.proj_cnt : nullptr,
-                                merged ? gd.rs * gd.rs : 0));
-    if (epeg_variant) {
-      if (!lw.pe_w) return RRT_E_INVALID;
-      const int nreg = gd.rs * gd.rs;
-      {
-        LinearEpilogue ep{};
-        ep.prec = desc->compute;
-        ep.bias = lw.qkv_b;
-        ep.q_cols = D;
-        ep.q_scale = 1.0f / sqrtf((float)(D / desc->n_heads));
-        RRT_TRY(launch_linear(ws.uo, lw.qkv_w, ws.qkv, gd.Np, 3 * D, D, ep, st));
-      }
-      if (desc->epeg_type == RRT_EPEG_ATTN) {           // epeg_2d: k x k stencil over the score map
-        // (regions of more than ~180 tokens: the score maps live in the workspace instead of the LDS)
-        RRT_TRY(launch_attn_scoremap(ws.qkv, lw.pe_w, ws.uo, ws.smap, nreg, gd.P, D, desc->n_heads, desc->epeg_k, st));
-      } else {
-        RRT_TRY(launch_value_pe(ws.qkv, lw.pe_w, lw.pe_b, ws.pe_out, nreg, gd.P, gd.s, D, desc->n_heads, desc->epeg_k,
-                                desc->epeg_2d, st));
-        if (desc->epeg_type == RRT_EPEG_VALUE_BF)       // v += pe before attn @ v (rmsa.py:114-118)
-          RRT_TRY(launch_add_cols(ws.qkv + 2 * D, ws.pe_out, (size_t)gd.Np, D, 3 * D, st));
-        RRT_TRY(launch_region_attention(ws.qkv, nullptr, ws.uo, nreg, gd.P, D, desc->n_heads, 0, st));
-        if (desc->epeg_type == RRT_EPEG_VALUE_AF)       // x += pe after it (rmsa.py:124-129)
-          RRT_TRY(launch_add_cols(ws.uo, ws.pe_out, (size_t)gd.Np, D, D, st));
-      }
-      LinearEpilogue ep{};
-      ep.prec = desc->compute;
-      ep.bias = lw.proj_b;
-      ep.resid = xin;
-      ep.g = gd;
-      ep.zero64 = ws.cr_cnt;
-      RRT_TRY(launch_linear(ws.uo, lw.proj_w, xout, gd.Np, D, D, ep, st));
-      xin = xout;
-      if (desc->ffn) {
-        rc = ffn_block(lw, xout, fout);
-        if (rc) return rc;
-        xin = fout;
-      }
-      continue;
-    }
-    const bool fused = rmsa_fused_supported(gd.P, D, desc->n_heads, ek) && rmsa_fused_supported_rows(gd.Np, D);
-    // the gate only pays for launches that fill the matrix pipes of the whole chip on their own: the fused
-    // kernel on regions of >= 113 tokens (measured on the configs[4] mix: gating small or unfused bags costs 5 %)
-    rrt_phase_gate* const gt = (gate && fused && gd.P > 112) ? gate : nullptr;
-    if (gt && gt->armed) RRT_TRY(hipStreamWaitEvent(st, gt->done, 0));
-    if (li == 0) RRT_MARK(RRT_EV_LN_PARTITION);    // after the gate: the mark brackets the kernel, not the wait
-    if (fused && merged) {
-      // ... and the out-projection + un-partition + residual as a later phase of the same launch's blocks (fp32,
-      // bags of >= two rounds of (region, head) items): one launch per R-MSA layer
-      FusedProj pj{};
-      pj.Wp = lw.proj_w;
-      pj.bias = lw.proj_b;
-      pj.resid = xin;
-      pj.out = xout;
-      pj.cnt = ws.proj_cnt;
-      pj.zero64 = ws.cr_cnt;
-      pj.g = gd;
-      // the LAST R-MSA layer feeding CR-MSA directly: its slabs also leave LayerNorm 2's statistics and the logits' dot
-      // products of every row (x1 is in their registers), and CR-MSA's first pass shrinks to the combine
-      if (parts) {
-        pj.part = ws.cr_pstat;
-        pj.ln_g = w->crmsa.norm_w;
-        pj.phi = w->phi;
-        pj.k = desc->crmsa_k;
-        parts_done = true;
-      }
-      RRT_TRY(launch_rmsa_fused(ws.uo, lw.qkv_w, lw.qkv_b, desc->epeg ? lw.pe_w : nullptr, ws.qkv,
-                                gd.rs * gd.rs, gd.P, D, desc->n_heads, ek, desc->compute, st, nullptr, &pj));
-      if (gt) { RRT_TRY(hipEventRecord(gt->done, st)); gt->armed = true; }
-      if (li == 0) { RRT_MARK(RRT_EV_QKV); RRT_MARK(RRT_EV_ATTN); RRT_MARK(RRT_EV_PROJ); }
-      xin = xout;
-      if (desc->ffn) {
-        rc = ffn_block(lw, xout, fout);
-        if (rc) return rc;
-        xin = fout;
-      }
-      continue;
-    }
-    if (fused) {
-      // qkv projection + EPEG + attention in one kernel per (region, head): qkv never reaches HBM.
-      // O goes to the qkv workspace (first Np*D floats), u stays in uo.
-      RRT_TRY(launch_rmsa_fused(ws.uo, lw.qkv_w, lw.qkv_b, desc->epeg ? lw.pe_w : nullptr, ws.qkv,
-                                gd.rs * gd.rs, gd.P, D, desc->n_heads, ek, desc->compute, st));
-      static const bool gate_proj = rrt_tune_env("RRT_GATE_PROJ") != nullptr;
-      if (gt && !gate_proj) { RRT_TRY(hipEventRecord(gt->done, st)); gt->armed = true; }
-      if (li == 0) { RRT_MARK(RRT_EV_QKV); RRT_MARK(RRT_EV_ATTN); }
-      LinearEpilogue ep{};
-      ep.prec = desc->compute;
-      ep.bias = lw.proj_b;
-      ep.resid = xin;
-      ep.g = gd;
-      ep.zero64 = ws.cr_cnt;
-      RRT_TRY(launch_linear(ws.qkv, lw.proj_w, xout, gd.Np, D, D, ep, st));
-      if (gt && gate_proj) { RRT_TRY(hipEventRecord(gt->done, st)); gt->armed = true; }
-      if (li == 0) RRT_MARK(RRT_EV_PROJ);
-      xin = xout;
-      if (desc->ffn) {
-        rc = ffn_block(lw, xout, fout);
-        if (rc) return rc;
-        xin = fout;
-      }
-      continue;
-    }
-    {
-      LinearEpilogue ep{};
-      ep.prec = desc->compute;
-      ep.bias = lw.qkv_b;
-      ep.q_cols = D;
-      ep.q_scale = 1.0f / sqrtf((float)(D / desc->n_heads));   // head_dim ** -0.5, rmsa.py:65,103
-      RRT_TRY(launch_linear(ws.uo, lw.qkv_w, ws.qkv, gd.Np, 3 * D, D, ep, st));
-    }
-    if (li == 0) RRT_MARK(RRT_EV_QKV);
-    RRT_TRY(launch_region_attention(ws.qkv, desc->epeg ? lw.pe_w : nullptr, ws.uo, gd.rs * gd.rs, gd.P, D,
-                                    desc->n_heads, desc->epeg ? desc->epeg_k : 0, st));
-    if (li == 0) RRT_MARK(RRT_EV_ATTN);
-    LinearEpilogue ep{};
-    ep.prec = desc->compute;
-    ep.bias = lw.proj_b;
-    ep.resid = xin;
-    ep.g = gd;
-    ep.zero64 = ws.cr_cnt;
-    RRT_TRY(launch_linear(ws.uo, lw.proj_w, xout, gd.Np, D, D, ep, st));
-    if (li == 0) RRT_MARK(RRT_EV_PROJ);
+    if (marks) RRT_TRY(mark(RRT_EV_PROJ));
     xin = xout;
     if (desc->ffn) {
       rc = ffn_block(lw, xout, fout);
@@ -693,7 +700,7 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
   if (!w->norm_w || !w->norm_b) return RRT_E_INVALID;
   if (!desc->cr_msa) {
     RRT_TRY(launch_layernorm(xin, x0, w->norm_w, w->norm_b, y, (int)N, D, st));
-    RRT_MARK(RRT_EV_END);
+    RRT_TRY(mark(RRT_EV_END));
     return RRT_OK;
   }
   // ---- CR-MSA TransLayer (rmsa.py:290-337) + all_shortcut + final LayerNorm (rrt.py:190-195)
@@ -702,68 +709,57 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
   if (desc->crmsa_mlp ? (!w->phi0_w || !w->phi2_w) : !w->phi) return RRT_E_INVALID;
   const GridDev gd8 = to_dev(g8);
   const int k = desc->crmsa_k, R8 = gd8.rs * gd8.rs;
-  bool rep16_done = false;
-  static const bool no_region_inflight = rrt_tune_env("RRT_NO_REGION_INFLIGHT") != nullptr;
-  static const bool region_lowp = rrt_tune_env("RRT_REGION_INFLIGHT_LOWP") != nullptr;      // (A/B: also in the 16-bit modes)
-  const bool region_inflight = !no_region_inflight && !desc->solo && !desc->crmsa_mlp && !parts_done && !x3 &&
-                               (desc->compute == RRT_COMPUTE_F32 || region_lowp) && crmsa_region_supported(D, k, gd8);
-  if (desc->crmsa_mlp) {
-    // MLP phi (rmsa.py:248-252,305): v = LN(x1) materialised in region-major order, hidden = v W1^T on
-    // the matrix cores, logits = tanh(hidden) W2^T; the combine then runs on the normalised rows
-    RRT_TRY(launch_ln_partition(xin, cw.norm_w, cw.norm_b, ws.v8, D, gd8, st));
-    LinearEpilogue ep{};
-    ep.prec = desc->compute;
-    RRT_TRY(launch_linear(ws.v8, w->phi0_w, ws.hid, gd8.Np, D / 4, D, ep, st));
-    RRT_TRY(launch_crmsa_mlp_logits(ws.hid, w->phi2_w, ws.logits, gd8.Np, D / 4, k, st));
-    RRT_TRY(launch_crmsa_combine(ws.v8, nullptr, nullptr, nullptr, ws.logits, ws.wdisp, ws.rep, inner16 ? ws.rep16 : nullptr,
-                                 desc->compute, D, k, gd8, st));
-    rep16_done = inner16;
-  } else if (parts_done) {
-    // LayerNorm 2's statistics and the logits' dot products came out of the projection slabs: one pass over x1, 64 x D / 64
-    // independent blocks (crmsa_combine_parts_kernel)
-    RRT_TRY(launch_crmsa_combine_parts(xin, ws.cr_pstat, cw.norm_w, cw.norm_b, w->phi, ws.wdisp, ws.rep,
-                                       inner16 ? ws.rep16 : nullptr, desc->compute, D, k, gd8, st));
-    rep16_done = inner16;
-  } else if (region_inflight) {
-    // round 6: exact fp32 with SEVERAL bags in flight -- logits + combine as ONE sixteen-wave block per region
-    // (crmsa_region_kernel, its k = 1 .. 3 forms with gamma . phi in registers): 64 blocks, so three quarters of the chip stay
-    // with the other bags' fused R-MSA launches, which is what the line is made of (the fused launches' union is 187 of the
-    // 189 us a bag takes).  Same box, four bags in flight: 5.30-5.31 k -> 5.36-5.38 k slides/s with the round-1 kernel
-    // (profiles/r06_region1_in_flight_ab.txt); one bag in flight it loses (20 us on a quarter of the chip): the hint decides.
-    // The 16-bit modes keep crmsa_region4 (their chip-wide kernels are short: a 64-block front becomes the critical path).
-    RRT_TRY(launch_crmsa_region(xin, cw.norm_w, cw.norm_b, w->phi, nullptr, nullptr, ws.wdisp, ws.rep, k, gd8, st,
-                                inner16 ? ws.rep16 : nullptr, desc->compute));
-    rep16_done = inner16;
-  } else if (ws.cr_cnt && desc->n_rmsa_layers > 0 && crmsa_region4_supported(D, k, gd8) && gd8.P < RRT_STREAM4_MIN_P) {
-    // logits + combine in one pass over x1: four blocks per region, the last to arrive merges (crmsa_region4_kernel).
-    // Its counters were zeroed by this forward's last R-MSA out-projection.  Regions of more than 144 tokens (8 / 16
-    // blocks per region: the kernel covers them, tests) stay with the two chip-wide kernels: measured on MI355X
-    // (tools/bench_crmsa.py) the merge of 8-16 partial records per region costs more than the second pass over x1
-    // -- N = 15000: 36 vs 24 us, N = 30000: 46-74 vs 39 us.
-    RRT_TRY(launch_crmsa_region4(xin, cw.norm_w, cw.norm_b, w->phi, nullptr, ws.logits, ws.wdisp, ws.rep,
-                                 inner16 ? ws.rep16 : nullptr, desc->compute, ws.cr_part, ws.cr_cnt, k, gd8, st));
-    rep16_done = inner16;
-  } else if (crmsa_region_enabled() && crmsa_region_supported(D, k, gd8)) {
-    // logits + combine in one pass over x1 (one block of 16 waves per region, the rows stay in registers)
-    RRT_TRY(launch_crmsa_region(xin, cw.norm_w, cw.norm_b, w->phi, nullptr, nullptr, ws.wdisp, ws.rep, k, gd8, st));
-  } else if (ws.cr_cnt && desc->n_rmsa_layers > 0 && gd8.P >= RRT_STREAM4_MIN_P && crmsa_stream4_supported(D, k, gd8)) {
-    // round 6: regions of more than 144 tokens in ONE pass over x1 as well -- four blocks per region that stream their rows
-    // with an online softmax per wave, crmsa_region4's records and merge (crmsa_stream4_kernel); counters as above
-    RRT_TRY(launch_crmsa_stream4(xin, cw.norm_w, cw.norm_b, w->phi, nullptr, ws.logits, ws.wdisp, ws.rep,
-                                 inner16 ? ws.rep16 : nullptr, desc->compute, ws.cr_part, ws.cr_cnt, k, gd8, st));
-    rep16_done = inner16;
-  } else {
-    RRT_TRY(launch_crmsa_logits(xin, cw.norm_w, cw.norm_b, w->phi, ws.mean_rstd, ws.logits, D, k, gd8, st));
-    RRT_TRY(launch_crmsa_combine(xin, cw.norm_w, cw.norm_b, ws.mean_rstd, ws.logits, ws.wdisp, ws.rep,
-                                 inner16 ? ws.rep16 : nullptr, desc->compute, D, k, gd8, st));
-    rep16_done = inner16;
+  // every front but Region also leaves the representatives as 16-bit values for the 16-bit inner MSA
+  uint16_t* const rep16 = plan.inner16 ? ws.rep16 : nullptr;
+  switch (plan.front) {
+    case FrontKind::Mlp: {
+      // MLP phi (rmsa.py:248-252,305): v = LN(x1) materialised in region-major order, hidden = v W1^T on
+      // the matrix cores, logits = tanh(hidden) W2^T; the combine then runs on the normalised rows
+      RRT_TRY(launch_ln_partition(xin, cw.norm_w, cw.norm_b, ws.v8, D, gd8, st));
+      LinearEpilogue ep{};
+      ep.prec = desc->compute;
+      RRT_TRY(launch_linear(ws.v8, w->phi0_w, ws.hid, gd8.Np, D / 4, D, ep, st));
+      RRT_TRY(launch_crmsa_mlp_logits(ws.hid, w->phi2_w, ws.logits, gd8.Np, D / 4, k, st));
+      RRT_TRY(launch_crmsa_combine(ws.v8, nullptr, nullptr, nullptr, ws.logits, ws.wdisp, ws.rep, rep16, desc->compute, D, k, gd8, st));
+      break;
+    }
+    case FrontKind::Parts:
+      // LayerNorm 2's statistics and the logits' dot products came out of the projection slabs: one pass over x1, 64 x D / 64
+      // independent blocks (crmsa_combine_parts_kernel)
+      RRT_TRY(launch_crmsa_combine_parts(xin, ws.cr_pstat, cw.norm_w, cw.norm_b, w->phi, ws.wdisp, ws.rep, rep16, desc->compute, D,
+                                         k, gd8, st));
+      break;
+    case FrontKind::RegionInFlight:
+      RRT_TRY(launch_crmsa_region(xin, cw.norm_w, cw.norm_b, w->phi, nullptr, nullptr, ws.wdisp, ws.rep, k, gd8, st, rep16,
+                                  desc->compute));
+      break;
+    case FrontKind::Region4:
+      // (its counters were zeroed by this forward's last R-MSA out-projection)
+      RRT_TRY(launch_crmsa_region4(xin, cw.norm_w, cw.norm_b, w->phi, nullptr, ws.logits, ws.wdisp, ws.rep, rep16, desc->compute,
+                                   ws.cr_part, ws.cr_cnt, k, gd8, st));
+      break;
+    case FrontKind::Region:
+      // logits + combine in one pass over x1 (one block of 16 waves per region, the rows stay in registers)
+      RRT_TRY(launch_crmsa_region(xin, cw.norm_w, cw.norm_b, w->phi, nullptr, nullptr, ws.wdisp, ws.rep, k, gd8, st));
+      break;
+    case FrontKind::Stream4:
+      // (counters as Region4's)
+      RRT_TRY(launch_crmsa_stream4(xin, cw.norm_w, cw.norm_b, w->phi, nullptr, ws.logits, ws.wdisp, ws.rep, rep16, desc->compute,
+                                   ws.cr_part, ws.cr_cnt, k, gd8, st));
+      break;
+    case FrontKind::TwoKernel:
+      RRT_TRY(launch_crmsa_logits(xin, cw.norm_w, cw.norm_b, w->phi, ws.mean_rstd, ws.logits, D, k, gd8, st));
+      RRT_TRY(launch_crmsa_combine(xin, cw.norm_w, cw.norm_b, ws.mean_rstd, ws.logits, ws.wdisp, ws.rep, rep16, desc->compute, D, k,
+                                   gd8, st));
+      break;
+    case FrontKind::None: break;      // (cr_msa = 0 and the batch entry point's stop returned above)
   }
-  RRT_MARK(RRT_EV_CR_COMBINE);
+  RRT_TRY(mark(RRT_EV_CR_COMBINE));
   // inner MSA over the representatives: batch = k, sequence = R8 regions, no EPEG (rmsa.py:322)
-  if (inner16) {
+  if (plan.inner16) {
     // reduced-precision modes: qkv projection + attention of the (n, head) pairs as ONE launch of the 16-bit fused R-MSA
     // kernel (k "regions" of 64 tokens, no EPEG), then the out-projection on 16-bit operands
-    if (!rep16_done) {
+    if (plan.front == FrontKind::Region) {
       Cast16Jobs cj{};
       cj.src[0] = ws.rep; cj.dst[0] = ws.rep16; cj.n4[0] = (size_t)k * R8 * D / 4; cj.count = 1;
       RRT_TRY(launch_cast16(cj, desc->compute, st));
@@ -783,7 +779,7 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
     ep.solo = desc->solo != 0 || inner_solo;
     RRT_TRY(launch_linear(ws.rep_o, cw.proj_w, ws.rep2, k * R8, D, D, ep, st));
   }
-  RRT_MARK(RRT_EV_CR_INNER);
+  RRT_TRY(mark(RRT_EV_CR_INNER));
   if (desc->ffn) {
     // x2 = x1 + dispatch (no LayerNorm yet) -> FFN -> (+ shortcut) -> final LayerNorm.  xin is xb or the
     // caller's x: xa is free for x2, and xin is dead once the dispatch has read it.
@@ -791,16 +787,14 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
     rc = ffn_block(cw, ws.xa, ws.xb);
     if (rc) return rc;
     RRT_TRY(launch_layernorm(ws.xb, x0, w->norm_w, w->norm_b, y, (int)N, D, st));
-    RRT_MARK(RRT_EV_END);
+    RRT_TRY(mark(RRT_EV_END));
     return RRT_OK;
   }
   const bool want16 = y16 != nullptr && (desc->compute == RRT_COMPUTE_BF16 || desc->compute == RRT_COMPUTE_F16) && D % 4 == 0;
   RRT_TRY(launch_crmsa_dispatch_ln(xin, x0, ws.wdisp, ws.rep2, w->norm_w, w->norm_b, y, D, k,
                                    gd8, st, want16 ? y16 : nullptr, want16 ? desc->compute : 0));
   if (want16 && y16_done) *y16_done = true;
-  RRT_MARK(RRT_EV_END);
-#undef RRT_TRY
-#undef RRT_MARK
+  RRT_TRY(mark(RRT_EV_END));
   return RRT_OK;
 }
 
@@ -885,14 +879,8 @@ BatchWs carve_batch(const rrt_encoder_desc& d, int64_t B, int64_t N, const rrt_g
 
 int rrt_encoder_batch_workspace_size(const rrt_encoder_desc* desc, int32_t batch, int64_t n_tokens, size_t* bytes) {
   if (!bytes || batch <= 0) return RRT_E_INVALID;
-  int rc = check_desc(desc, n_tokens);
-  if (rc) return rc;
   rrt_grid g{}, g8{};
-  if (desc->n_rmsa_layers > 0) {
-    rc = rrt_region_grid(n_tokens, desc->region_num, desc->region_size, desc->min_region_num, desc->min_region_ratio, &g);
-    if (rc) return rc;
-  }
-  rc = rrt_region_grid(n_tokens, 8, 0, 0, 0.f, &g8);
+  int rc = resolve_grids(desc, n_tokens, &g, &g8);
   if (rc) return rc;
   *bytes = carve_batch(*desc, batch, n_tokens, g, g8, nullptr).bytes;
   return RRT_OK;
@@ -912,21 +900,11 @@ int rrt_encoder_forward_batch_f32(const rrt_encoder_desc* desc_in, const rrt_enc
   const int D = desc->dim;
   hipStream_t st = (hipStream_t)stream;
   rrt_grid g{}, g8{};
-  if (desc->n_rmsa_layers > 0) {
-    rc = rrt_region_grid(N, desc->region_num, desc->region_size, desc->min_region_num, desc->min_region_ratio, &g);
-    if (rc) return rc;
-  }
-  rc = rrt_region_grid(N, 8, 0, 0, 0.f, &g8);
+  rc = region_grids(desc, N, &g, &g8);
   if (rc) return rc;
   BatchWs bw = carve_batch(*desc, B, N, g, g8, nullptr);
   if (!workspace || workspace_bytes < bw.bytes) return RRT_E_WORKSPACE;
   bw = carve_batch(*desc, B, N, g, g8, (char*)workspace);
-  hipError_t e = hipSuccess;
-#define RRT_TRY(call)                   \
-  do {                                  \
-    e = (call);                         \
-    if (e != hipSuccess) return (int)e; \
-  } while (0)
   // ---- positional encoder + R-MSA layers, bag by bag -> x1 [B, N, D]
   for (int64_t b = 0; b < B; ++b) {
     rc = encoder_forward(&dloc, w, x + (size_t)b * N * D, y + (size_t)b * N * D, N, workspace, bw.one_bytes, stream, nullptr,
@@ -994,7 +972,6 @@ int rrt_encoder_forward_batch_f32(const rrt_encoder_desc* desc_in, const rrt_enc
       RRT_TRY(launch_crmsa_dispatch_ln(xb1, x0, wd, rep2b, w->norm_w, w->norm_b, yb, D, k, gd8, st));
     }
   }
-#undef RRT_TRY
   return RRT_OK;
 }
 
@@ -1025,11 +1002,7 @@ int rrt_linear_unpartition_residual_f32(const float* A, const float* B, const fl
   if (!A || !B || !resid || !out || !g || N <= 0 || K <= 0) return RRT_E_INVALID;
   if (K % 32) return unsupported("linear: K must be a multiple of 32");
   if (compute < 0 || compute > 2) return unsupported("compute must be RRT_COMPUTE_F32/BF16/F16");
-  LinearEpilogue ep{};
-  ep.prec = compute;
-  ep.bias = bias;
-  ep.resid = resid;
-  ep.g = to_dev(*g);
+  const LinearEpilogue ep = proj_epilogue(bias, resid, to_dev(*g), compute);
   return (int)launch_linear(A, B, out, ep.g.Np, N, K, ep, (hipStream_t)stream);
 }
 
@@ -2249,17 +2222,14 @@ int check_train(const rrt_encoder_desc* d, int64_t N, rrt_grid* g, rrt_grid* g8)
   if (rc) return rc;
   if (d->compute == RRT_COMPUTE_F32X3) return unsupported("training: RRT_COMPUTE_F32X3 is an inference mode (train in F32 or under autocast)");
   if (d->dim > 1024) return unsupported("training: dim > 1024");
-  memset(g, 0, sizeof(*g));
+  rc = region_grids(d, N, g, g8);
+  if (rc) return rc;
   if (d->n_rmsa_layers > 0) {
-    rc = rrt_region_grid(N, d->region_num, d->region_size, d->min_region_num, d->min_region_ratio, g);
-    if (rc) return rc;
     const bool e2d = d->epeg && d->epeg_2d && d->epeg_type == RRT_EPEG_ATTN, evalue = d->epeg && d->epeg_type != RRT_EPEG_ATTN;
     // (the 2-D 'attn' EPEG has its own backward kernel, any head dim; the value variants run the plain attention backward)
     if (!e2d && !attn_bwd_supported(g->s * g->s, d->dim, d->n_heads, (d->epeg && !evalue) ? d->epeg_k : 0))
       return unsupported("training: the R-MSA attention backward needs a head dim that is a multiple of 16 up to 256 (any region size, epeg_k <= 63); other head dims (not a multiple of 16, or above 256) only without EPEG on regions of <= 128 tokens, or with epeg_2d");
   }
-  rc = rrt_region_grid(N, 8, 0, 0, 0.f, g8);
-  if (rc) return rc;
   if (d->cr_msa) {
     const int R8 = g8->regions_side * g8->regions_side;
     if (!attn_bwd_supported(R8, d->dim, d->crmsa_heads, 0))
@@ -2329,24 +2299,8 @@ int rrt_encoder_forward_train_f32(const rrt_encoder_desc* desc, const rrt_encode
   hipStream_t st = (hipStream_t)stream;
   const int D = desc->dim;
   const int64_t N = n_tokens;
-  hipError_t e = hipSuccess;
-#define RRT_TRY(call)                   \
-  do {                                  \
-    e = (call);                         \
-    if (e != hipSuccess) return (int)e; \
-  } while (0)
   // TransLayer's FFN (ffn = 1): xf = xi + fc2(act(fc1(LN2(xi)))), stashing LN2's output and the pre-activation
-  GridDev gid{};
-  {
-    const int Hs = (int)ceil_sqrt(N);
-    gid.L = (int)N;
-    gid.H = gid.s = Hs;
-    gid.rs = 1;
-    gid.P = gid.Np = Hs * Hs;
-    gid.inv_H = gid.inv_s = 1.0f / (float)Hs;
-    gid.inv_rs = 1.0f;
-    gid.inv_P = 1.0f / (float)gid.P;
-  }
+  const GridDev gid = identity_grid(N);
   auto train_ffn = [&](const rrt_attn_weights& lw, const float* xi, int idx) -> int {
     if (!lw.norm2_w || !lw.norm2_b || !lw.fc1_w || !lw.fc1_b || !lw.fc2_w || !lw.fc2_b) return RRT_E_INVALID;
     hipError_t fe = launch_layernorm(xi, nullptr, lw.norm2_w, lw.norm2_b, s.ffn_u[idx], (int)N, D, st);
@@ -2360,10 +2314,7 @@ int rrt_encoder_forward_train_f32(const rrt_encoder_desc* desc, const rrt_encode
     fe = launch_act_forward(s.ffn_hpre[idx], s.hscr, (size_t)N * desc->ffn_hidden, desc->ffn_act, dc.thresh,
                             dc.seed(drop_seed, 200 + 2 * idx), dc.scale, st);
     if (fe != hipSuccess) return (int)fe;
-    LinearEpilogue e2{};
-    e2.bias = lw.fc2_b;
-    e2.resid = xi;
-    e2.g = gid;
+    LinearEpilogue e2 = proj_epilogue(lw.fc2_b, xi, gid, RRT_COMPUTE_F32);      // (fc2 of the training FFN: exact fp32 in every mode)
     const float bsf = br.ffn[idx < RRT_MAX_RMSA_LAYERS ? idx : desc->n_rmsa_layers];
     e2.drop_thresh = dc.thresh;
     e2.drop_scale = dc.scale * bsf;
@@ -2388,11 +2339,7 @@ int rrt_encoder_forward_train_f32(const rrt_encoder_desc* desc, const rrt_encode
     if (desc->epeg && !lw.pe_w) return RRT_E_INVALID;
     const GridDev gd = to_dev(g);
     RRT_TRY(launch_ln_partition(xin, lw.norm_w, lw.norm_b, s.u[li], D, gd, st));
-    LinearEpilogue ep{};
-    ep.prec = desc->compute;
-    ep.bias = lw.qkv_b;
-    ep.q_cols = D;
-    ep.q_scale = 1.0f / sqrtf((float)(D / desc->n_heads));
+    const LinearEpilogue ep = qkv_epilogue(lw.qkv_b, D, desc->n_heads, desc->compute);
     const bool e2d = desc->epeg && desc->epeg_2d && desc->epeg_type == RRT_EPEG_ATTN;
     const bool evalue = desc->epeg && desc->epeg_type != RRT_EPEG_ATTN;
     // the inference path's fused kernel (projection + EPEG + attention per (region, head)) with the q | k | v tiles
@@ -2417,15 +2364,12 @@ int rrt_encoder_forward_train_f32(const rrt_encoder_desc* desc, const rrt_encode
     RRT_TRY(launch_region_attention(s.qkv[li], desc->epeg ? lw.pe_w : nullptr, s.o[li], gd.rs * gd.rs, gd.P, D,
                                     desc->n_heads, desc->epeg ? desc->epeg_k : 0, st));
     }
-    LinearEpilogue ep2{};
-    ep2.bias = lw.proj_b;
-    ep2.resid = xin;
-    ep2.g = gd;
+    const bool drop_on = dc.thresh || br.attn[li] != 1.0f;
+    LinearEpilogue ep2 = proj_epilogue(lw.proj_b, xin, gd, drop_on ? RRT_COMPUTE_F32 : desc->compute);      // the dropout epilogue exists in fp32 only
     ep2.drop_thresh = dc.thresh;
     ep2.drop_scale = dc.scale * br.attn[li];
-    ep2.drop_on = dc.thresh || br.attn[li] != 1.0f;
+    ep2.drop_on = drop_on;
     ep2.drop_seed = dc.seed(drop_seed, li);
-    ep2.prec = ep2.drop_on ? RRT_COMPUTE_F32 : desc->compute;      // the dropout epilogue exists in fp32 only
     RRT_TRY(launch_linear(s.o[li], lw.proj_w, s.xout[li], gd.Np, D, D, ep2, st));
     xin = s.xout[li];
     if (desc->ffn) {
@@ -2456,11 +2400,7 @@ int rrt_encoder_forward_train_f32(const rrt_encoder_desc* desc, const rrt_encode
       RRT_TRY(launch_crmsa_logits(xin, cw.norm_w, cw.norm_b, w->phi, s.mean_rstd, s.logits, D, k, gd8, st));
       RRT_TRY(launch_crmsa_combine(xin, cw.norm_w, cw.norm_b, s.mean_rstd, s.logits, s.wdisp, s.rep, nullptr, 0, D, k, gd8, st));
     }
-    LinearEpilogue ep{};
-    ep.prec = desc->compute;
-    ep.bias = cw.qkv_b;
-    ep.q_cols = D;
-    ep.q_scale = 1.0f / sqrtf((float)(D / desc->crmsa_heads));
+    LinearEpilogue ep = qkv_epilogue(cw.qkv_b, D, desc->crmsa_heads, desc->compute);
     ep.solo = true;
     RRT_TRY(launch_linear(s.rep, cw.qkv_w, s.rep_qkv, k * R8, 3 * D, D, ep, st));
     RRT_TRY(launch_region_attention(s.rep_qkv, nullptr, s.rep_o, k, R8, D, desc->crmsa_heads, 0, st));
@@ -2488,7 +2428,6 @@ int rrt_encoder_forward_train_f32(const rrt_encoder_desc* desc, const rrt_encode
     RRT_TRY(launch_layernorm(xin, x0, nullptr, nullptr, s.x2, (int)N, D, st));                            // x2 = x1 (+ x)
   }
   RRT_TRY(launch_layernorm(s.x2, nullptr, w->norm_w, w->norm_b, y, (int)N, D, st));
-#undef RRT_TRY
   return RRT_OK;
 }
 
@@ -2513,12 +2452,6 @@ int rrt_encoder_backward_f32(const rrt_encoder_desc* desc, const rrt_encoder_wei
   hipStream_t st = (hipStream_t)stream;
   const int D = desc->dim, L = desc->n_rmsa_layers;
   const int N = (int)n_tokens;
-  hipError_t e = hipSuccess;
-#define RRT_TRY(call)                   \
-  do {                                  \
-    e = (call);                         \
-    if (e != hipSuccess) return (int)e; \
-  } while (0)
   if (!gr->norm) return RRT_E_INVALID;
   {
     // W^T of every attention Linear, for the dX products (dX = dY . W as the forward GEMM on W^T): one launch up front
@@ -2712,7 +2645,6 @@ int rrt_encoder_backward_f32(const rrt_encoder_desc* desc, const rrt_encoder_wei
   }
   if (dx) RRT_TRY(launch_layernorm(cur, desc->all_shortcut ? b.dx2 : nullptr, nullptr, nullptr, dx, N, D, st));
   RRT_TRY(launch_reduce_jobs(rj, st));
-#undef RRT_TRY
   return RRT_OK;
 }
 

@@ -88,6 +88,56 @@ def test_encoder_plan_flags(lib):
     assert lib.rrt_encoder_plan(C.byref(enc._desc), 9000, None) == -1
 
 
+@pytest.fixture(scope="module")
+def plan_golden():
+    """the host-side answers of the library before the forward launched from one plan value (tools/make_golden_plan.py)"""
+    import json
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import make_golden_plan as tool
+    with open(tool.OUT) as fh:
+        rec = json.load(fh)
+    crmsa = [list(c) for c in tool.AXES["crmsa"]]
+    assert rec["axes"] == dict(tool.AXES, crmsa=crmsa) and rec["size_axes"] == dict(tool.SIZE_AXES, crmsa=crmsa), \
+        "the recorded grid is not the tool's"
+    return tool, rec
+
+
+def test_encoder_plan_grid(lib, plan_golden):
+    """rrt_encoder_plan reports the forward's own plan: over the recorded grid of bag sizes, region counts, compute modes,
+    head counts, solo hint, CR-MSA forms and EPEG forms the flags are what they were when the choice was written out twice
+    (once in the layer loop, once in rrt_encoder_plan) -- and the grid reaches every flag combination there is."""
+    tool, rec = plan_golden
+    want = rec["flags"]
+    both = _lib.PLAN_FUSED | _lib.PLAN_FUSED_PROJ
+    for v in (0, _lib.PLAN_FUSED, both, both | _lib.PLAN_CRMSA_PARTS, _lib.PLAN_FUSED16, _lib.PLAN_FUSED_X3, _lib.PLAN_ATTN_HD):
+        assert v in want, f"the recorded table never holds {v}"
+    got = tool.plan_table(lib)
+    assert len(got) == len(want) == 9720
+    bad = [(i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != w]
+    assert not bad, f"{len(bad)} entries differ, first (index, got, recorded): {bad[:5]}"
+
+
+def test_workspace_and_stash_sizes_grid(lib, plan_golden):
+    """Every workspace / stash size query answers with the recorded number of bytes (and return code): the carve offsets --
+    which the cached weight images' validity depends on -- did not move."""
+    tool, rec = plan_golden
+    got = tool.size_table(lib)
+    assert len(got) == len(rec["sizes"]) == 1080 and any(r[1] and r[3] and r[5] and r[6] for r in rec["sizes"])
+    bad = [(i, g, w) for i, (g, w) in enumerate(zip(got, rec["sizes"])) if g != w]
+    assert not bad, f"{len(bad)} records differ, first (index, got, recorded): {bad[:3]}"
+
+
+def test_forward_refusals_before_the_first_launch(lib, plan_golden):
+    """A null weight (an R-MSA layer's LayerNorm, the weight images' sources, CR-MSA's qkv, phi -- also where the last R-MSA
+    layer's merged launch reads it -- the final LayerNorm) and a workspace one byte short are refused on the host with the
+    recorded codes.  The calls run in a child process that sees no GPU (tools/make_golden_plan.py, _NULL_CHILD)."""
+    tool, rec = plan_golden
+    want = rec["null_codes"]
+    assert len(want) == 10 and set(want.values()) == {-1, -3}
+    assert tool.null_codes() == want
+
+
 def test_missing_library_fails_loudly(tmp_path):
     with pytest.raises(_lib.RRTHipError):
         _lib.load(str(tmp_path / "nope.so"))

@@ -544,6 +544,65 @@ int rrt_clam_forward_f32(const rrt_clam_desc *desc, const rrt_clam_weights *w, c
                          float *a_raw, float *attn, float *features, int64_t *topk_idx, int64_t n_tokens,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- DSMIL head (modules/dsmil.py:96-135 MILNet with rrt=; exports added under ABI 29, no existing struct touched) ----
+ * Instance stream (dsmil.py:123 i_classifier, :126 torch.max, :84-85 the sort that picks the critical instances):
+ *     classes[n, j] = y_n . w[j] + b[j]   [N, C] (optional, may be NULL),
+ *     cmax[j] = max_n classes[n, j]       [C]    (optional),   argmax[j] = the row that holds it   [C] int64.
+ * y [N, dim], w [C, dim], b [C] or NULL.  One pass over y, fixed summation order (the same inputs give the same bits).
+ * TIES: the LOWEST index wins (torch leaves it unspecified).  NaN is never selected; a column without any non-NaN value
+ * selects index 0 and its cmax is NaN.  1 <= C <= 8, dim % 32 == 0, dim <= 2048, N <= 1e6, otherwise RRT_E_UNSUPPORTED.
+ * workspace: rrt_instance_max_workspace_size bytes (one (max, index) record per class and 128 tokens). */
+int rrt_instance_max_workspace_size(int64_t n_tokens, int32_t dim, int32_t n_classes, size_t *bytes);
+int rrt_instance_max_f32(const float *y, const float *w, const float *b, float *classes, float *cmax, int64_t *argmax,
+                         int64_t n_tokens, int32_t dim, int32_t n_classes, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
+/* Bag stream (dsmil.py:78-94 BClassifier with nonlinear=False, passing_v=False) in ONE pass over feats [N, dim]:
+ *     q_max[c] = q_w feats[argmax[c]] + q_b                       [C, Q]    (:85-86; argmax is read on the device)
+ *     a_raw[n, c] = (q_w feats_n + q_b) . q_max[c] / sqrt(Q)      [N, C]    (:81, :87-88)
+ *     A[:, c] = softmax_n(a_raw[:, c])                            [N, C]    (:88, the reference's layout)
+ *     B[c, :] = sum_n A[n, c] feats_n                             [C, dim]  (:89)
+ *     logits[o] = sum_{c, j} fcc_w[o, c, j] B[c, j] + fcc_b[o]    [C]       (:91-93, Conv1d(C, C, kernel_size = dim))
+ * The scores are computed FOLDED, a_raw[n, c] = feats_n . (q_w^T q_max[c]) / sqrt(Q) + q_b . q_max[c] / sqrt(Q): Q [N, Q]
+ * never exists, and feats is read once for scores and pooling (online softmax over 32-token chunks, fixed-order merge).
+ * q_w [Q, dim], q_b [Q] or NULL, fcc_w [C, C, dim], fcc_b [C] or NULL.  A, B, a_raw are optional (NULL: not wanted; the
+ * other outputs keep their bits).  An index outside [0, N) is clamped into the bag.  1 <= C <= 8, Q % 4 == 0, Q <= 4096,
+ * dim % 32 == 0, dim <= 2048, N <= 1e6, otherwise RRT_E_UNSUPPORTED.  workspace: rrt_dsmil_pool_workspace_size bytes.
+ * Not yet timed against the composition (rrt_branch_pool_f32 with y = hid_a = feats + torch ops): tools/bench_dsmil.py. */
+int rrt_dsmil_pool_workspace_size(int64_t n_tokens, int32_t dim, int32_t q_dim, int32_t n_classes, size_t *bytes);
+int rrt_dsmil_pool_f32(const float *feats, const int64_t *argmax, const float *q_w, const float *q_b, const float *fcc_w,
+                       const float *fcc_b, float *logits, float *A, float *B, float *a_raw, int64_t n_tokens, int32_t dim,
+                       int32_t q_dim, int32_t n_classes, void *workspace, size_t workspace_bytes, void *stream);
+
+/* MILNet.forward (eval, one bag, one stream; dsmil.py:117-135): x [n_tokens, input_dim] -> Linear(input_dim, dim) + act
+ * = feats (enc.compute's arithmetic, as CLAM's embedding) -> RRTEncoder (has_rrt; the reference allows rrt=None) ->
+ * instance max on the ENCODER OUTPUT -> bag stream on feats, the embedding BEFORE the encoder (dsmil.py:124) -> logits.
+ * Everything behind the encoder is fp32 in every compute mode: a 16-bit instance score could select another critical
+ * instance, a discontinuity no tolerance covers. */
+typedef struct rrt_dsmil_desc {
+  rrt_encoder_desc enc;    /* has_rrt = 0: only dim (= 512 in the reference) and compute are read */
+  int32_t input_dim;       /* patch feature width (multiple of 32) */
+  int32_t emb_act;         /* RRT_ACT_NONE / RRT_ACT_RELU / RRT_ACT_GELU (dsmil.py:101-104) */
+  int32_t has_rrt;         /* 1: the encoder sits in front of the instance classifier (dsmil.py:109, :123) */
+  int32_t n_classes;       /* C, 1..8 */
+  int32_t q_dim;           /* 128 in the reference (dsmil.py:65) */
+} rrt_dsmil_desc;
+
+typedef struct rrt_dsmil_weights {
+  rrt_encoder_weights enc;
+  const float *emb_w, *emb_b;         /* patch_to_emb.0      [dim, input_dim], [dim] */
+  const float *icls_w, *icls_b;       /* i_classifier        [C, dim], [C] */
+  const float *q_w, *q_b;             /* b_classifier.q      [q_dim, dim], [q_dim] */
+  const float *fcc_w, *fcc_b;         /* b_classifier.fcc    [C, C, dim], [C] */
+} rrt_dsmil_weights;
+
+int rrt_dsmil_workspace_size(const rrt_dsmil_desc *desc, int64_t n_tokens, size_t *bytes);
+/* logits [C] (prediction_bag); optional (NULL: not wanted): classes_max [C] (the eval-mode second output), A [n_tokens, C],
+ * B [C, dim], argmax [C] int64 (the critical instances).  The indices never visit the host. */
+int rrt_dsmil_forward_f32(const rrt_dsmil_desc *desc, const rrt_dsmil_weights *w, const float *x, float *logits,
+                          float *classes_max, float *A, float *B, int64_t *argmax, int64_t n_tokens, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
 /* ---- batch-of-bags executor (BASELINE configs[4]: mixed-size bags, every bag an independent B=1 forward;
  * the reference loops `for bag in loader: model(bag)`, main.py:466-467 / :558-560) ----
  * Bags are independent units, and one bag's forward is a dependent chain of ~10 kernels that leaves

@@ -80,6 +80,16 @@ class ClamWeights(C.Structure):
         "emb_w", "emb_b", "a_w", "a_b", "b_w", "b_b", "c_w", "c_b", "cls_w", "cls_b")]
 
 
+class DsmilDesc(C.Structure):
+    _fields_ = [("enc", EncoderDesc), ("input_dim", C.c_int32), ("emb_act", C.c_int32), ("has_rrt", C.c_int32),
+                ("n_classes", C.c_int32), ("q_dim", C.c_int32)]
+
+
+class DsmilWeights(C.Structure):
+    _fields_ = [("enc", EncoderWeights)] + [(n, C.c_void_p) for n in (
+        "emb_w", "emb_b", "icls_w", "icls_b", "q_w", "q_b", "fcc_w", "fcc_b")]
+
+
 class Bag(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("n_tokens", C.c_int64)]
 
@@ -170,6 +180,14 @@ SIGNATURES = {
     "rrt_clam_workspace_size": (C.c_int, [C.POINTER(ClamDesc), C.c_int64, C.POINTER(C.c_size_t)]),
     "rrt_clam_forward_f32": (C.c_int, [C.POINTER(ClamDesc), C.POINTER(ClamWeights)] + [C.c_void_p] * 6 +
                              [C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_instance_max_workspace_size": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_instance_max_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_dsmil_pool_workspace_size": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_dsmil_pool_f32": (C.c_int, [C.c_void_p] * 10 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                                         C.c_void_p]),
+    "rrt_dsmil_workspace_size": (C.c_int, [C.POINTER(DsmilDesc), C.c_int64, C.POINTER(C.c_size_t)]),
+    "rrt_dsmil_forward_f32": (C.c_int, [C.POINTER(DsmilDesc), C.POINTER(DsmilWeights)] + [C.c_void_p] * 6 +
+                              [C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rrt_executor_create": (C.c_int, [C.POINTER(EncoderDesc), C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     "rrt_executor_create_on_streams": (C.c_int, [C.POINTER(EncoderDesc), C.c_int32, C.POINTER(C.c_void_p), C.c_int64,
                                                  C.POINTER(C.c_void_p)]),

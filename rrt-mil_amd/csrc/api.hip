@@ -1440,6 +1440,78 @@ int check_clam(const rrt_clam_desc* d, int64_t N) {
   return check_branch_pool(N, d->enc.dim, d->hidden, d->per_branch ? d->n_classes : 1);
 }
 
+
+// ---- DSMIL head (dsmil_pool.hip)
+int check_instance_max(int64_t N, int dim, int C) {
+  if (N <= 0 || dim <= 0) return RRT_E_INVALID;
+  if (C < 1 || C > 8) return unsupported("instance max: 1 <= n_classes <= 8");
+  if (dim % 32) return unsupported("instance max: dim must be a multiple of 32");
+  if (dim > 2048) return unsupported("instance max: dim > 2048");
+  if (N > (int64_t)1000000) return unsupported("instance max: bag larger than 1e6 tokens");
+  return RRT_OK;
+}
+
+struct IMaxWs {
+  float* pv;
+  int* pi;
+  size_t bytes;
+};
+IMaxWs carve_imax(int64_t N, int C, char* base) {
+  IMaxWs w{};
+  const size_t rec = align_up(instance_max_part_records((int)N) * C * sizeof(float), 256);
+  w.pv = base ? (float*)base : nullptr;
+  w.pi = base ? (int*)(base + rec) : nullptr;
+  w.bytes = 2 * rec;
+  return w;
+}
+
+int check_dsmil_pool(int64_t N, int dim, int Q, int C) {
+  if (N <= 0 || dim <= 0 || Q <= 0) return RRT_E_INVALID;
+  if (C < 1 || C > 8) return unsupported("dsmil pool: 1 <= n_classes <= 8");
+  if (dim % 32) return unsupported("dsmil pool: dim must be a multiple of 32");
+  if (dim > 2048) return unsupported("dsmil pool: dim > 2048");
+  if (Q % 4) return unsupported("dsmil pool: q_dim must be a multiple of 4");
+  if (Q > 4096) return unsupported("dsmil pool: q_dim > 4096");
+  if (N > (int64_t)1000000) return unsupported("dsmil pool: bag larger than 1e6 tokens");
+  return RRT_OK;
+}
+
+struct DsmilWs {
+  float *v, *vb, *raw, *lpart, *part;
+  size_t bytes;
+};
+DsmilWs carve_dsmil_pool(int64_t N, int dim, int C, char* base) {
+  DsmilWs w{};
+  size_t off = 0;
+  auto take = [&](size_t nfloat) {
+    float* p = base ? (float*)(base + off) : nullptr;
+    off = align_up(off + nfloat * sizeof(float), 256);
+    return p;
+  };
+  w.v = take((size_t)C * dim);
+  w.vb = take(16);
+  w.lpart = take(64);
+  w.raw = take((size_t)N * C);
+  w.part = take(dsmil_pool_part_floats((int)N, dim, C));
+  w.bytes = off;
+  return w;
+}
+
+int check_dsmil(const rrt_dsmil_desc* d, int64_t N) {
+  if (!d || N <= 0) return RRT_E_INVALID;
+  if (d->has_rrt) {
+    int rc = check_desc(&d->enc, N);
+    if (rc) return rc;
+  }
+  if (d->input_dim <= 0 || d->input_dim % 32) return unsupported("input_dim must be a positive multiple of 32");
+  if (d->emb_act != RRT_ACT_NONE && d->emb_act != RRT_ACT_RELU && d->emb_act != RRT_ACT_GELU)
+    return unsupported("emb_act must be none/relu/gelu");
+  if (d->enc.compute < 0 || d->enc.compute > RRT_COMPUTE_F32X3) return unsupported("compute must be RRT_COMPUTE_*");
+  int rc = check_instance_max(N, d->enc.dim, d->n_classes);
+  if (rc) return rc;
+  return check_dsmil_pool(N, d->enc.dim, d->q_dim, d->n_classes);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1780,6 +1852,130 @@ int rrt_clam_forward_f32(const rrt_clam_desc* desc, const rrt_clam_weights* w, c
   if (e != hipSuccess) return (int)e;
   if (topk_idx) e = launch_topk_rows(at, (long long*)topk_idx, K, (int)n_tokens, desc->k_sample, st);
   return (int)e;
+}
+
+// ---- DSMIL head: the instance stream and the bag stream alone, and the one-call MILNet forward
+int rrt_instance_max_workspace_size(int64_t n_tokens, int32_t dim, int32_t n_classes, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_instance_max(n_tokens, dim, n_classes);
+  if (rc) return rc;
+  *bytes = carve_imax(n_tokens, n_classes, nullptr).bytes;
+  return RRT_OK;
+}
+
+int rrt_instance_max_f32(const float* y, const float* w, const float* b, float* classes, float* cmax, int64_t* argmax,
+                         int64_t n_tokens, int32_t dim, int32_t n_classes, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  if (!y || !w || !argmax) return RRT_E_INVALID;
+  int rc = check_instance_max(n_tokens, dim, n_classes);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < carve_imax(n_tokens, n_classes, nullptr).bytes) return RRT_E_WORKSPACE;
+  IMaxWs ws = carve_imax(n_tokens, n_classes, (char*)workspace);
+  return (int)launch_instance_max(y, w, b, classes, cmax, (long long*)argmax, ws.pv, ws.pi, (int)n_tokens, dim, n_classes,
+                                  (hipStream_t)stream);
+}
+
+int rrt_dsmil_pool_workspace_size(int64_t n_tokens, int32_t dim, int32_t q_dim, int32_t n_classes, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_dsmil_pool(n_tokens, dim, q_dim, n_classes);
+  if (rc) return rc;
+  *bytes = carve_dsmil_pool(n_tokens, dim, n_classes, nullptr).bytes;
+  return RRT_OK;
+}
+
+int rrt_dsmil_pool_f32(const float* feats, const int64_t* argmax, const float* q_w, const float* q_b, const float* fcc_w,
+                       const float* fcc_b, float* logits, float* A, float* B, float* a_raw, int64_t n_tokens, int32_t dim,
+                       int32_t q_dim, int32_t n_classes, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!feats || !argmax || !q_w || !fcc_w || !logits) return RRT_E_INVALID;
+  int rc = check_dsmil_pool(n_tokens, dim, q_dim, n_classes);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < carve_dsmil_pool(n_tokens, dim, n_classes, nullptr).bytes) return RRT_E_WORKSPACE;
+  DsmilWs ws = carve_dsmil_pool(n_tokens, dim, n_classes, (char*)workspace);
+  return (int)launch_dsmil_pool(feats, (const long long*)argmax, q_w, q_b, fcc_w, fcc_b, logits, A, B, a_raw ? a_raw : ws.raw,
+                                ws.v, ws.vb, ws.lpart, ws.part, (int)n_tokens, dim, q_dim, n_classes, (hipStream_t)stream);
+}
+
+static size_t dsmil_act_bytes(const rrt_dsmil_desc* d, int64_t N) { return align_up((size_t)N * d->enc.dim * sizeof(float), 256); }
+
+int rrt_dsmil_workspace_size(const rrt_dsmil_desc* desc, int64_t n_tokens, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_dsmil(desc, n_tokens);
+  if (rc) return rc;
+  size_t enc = 0;
+  if (desc->has_rrt) {
+    rc = rrt_encoder_workspace_size(&desc->enc, n_tokens, &enc);
+    if (rc) return rc;
+  }
+  const int D = desc->enc.dim, K = desc->n_classes;
+  // (the 16-bit images of patch_to_emb's operands are part of the size in every mode, as in rrt_clam_workspace_size)
+  *bytes = 2 * dsmil_act_bytes(desc, n_tokens) + align_up(enc, 256) + align_up(carve_imax(n_tokens, K, nullptr).bytes, 256) +
+           align_up(carve_dsmil_pool(n_tokens, D, K, nullptr).bytes, 256) + 256 /* arg-max [8] + class maxima [8] */ +
+           align_up((size_t)n_tokens * desc->input_dim * 2, 256) + align_up((size_t)D * desc->input_dim * 2, 256);
+  return RRT_OK;
+}
+
+int rrt_dsmil_forward_f32(const rrt_dsmil_desc* desc, const rrt_dsmil_weights* w, const float* x, float* logits,
+                          float* classes_max, float* A, float* B, int64_t* argmax, int64_t n_tokens, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  if (!desc || !w || !x || !logits) return RRT_E_INVALID;
+  int rc = check_dsmil(desc, n_tokens);
+  if (rc) return rc;
+  if (!w->emb_w || !w->icls_w || !w->q_w || !w->fcc_w) return RRT_E_INVALID;
+  size_t need = 0, enc_bytes = 0;
+  rc = rrt_dsmil_workspace_size(desc, n_tokens, &need);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < need) return RRT_E_WORKSPACE;
+  if (desc->has_rrt) {
+    rc = rrt_encoder_workspace_size(&desc->enc, n_tokens, &enc_bytes);
+    if (rc) return rc;
+  }
+  const int D = desc->enc.dim, K = desc->n_classes;
+  const size_t act = dsmil_act_bytes(desc, n_tokens);
+  char* base = (char*)workspace;
+  float* emb = (float*)base;                                   // feats: the bag stream reads it AFTER the encoder has run
+  float* y = desc->has_rrt ? (float*)(base + act) : emb;
+  char* enc_ws = base + 2 * act;
+  char* p = enc_ws + align_up(enc_bytes, 256);
+  IMaxWs iws = carve_imax(n_tokens, K, p);
+  p += align_up(iws.bytes, 256);
+  DsmilWs dws = carve_dsmil_pool(n_tokens, D, K, p);
+  p += align_up(dws.bytes, 256);
+  long long* am = argmax ? (long long*)argmax : (long long*)p;
+  float* cm = classes_max ? classes_max : (float*)(p + 64);
+  p += 256;
+  hipStream_t st = (hipStream_t)stream;
+
+  // patch_to_emb follows enc.compute exactly as in rrt_clam_forward_f32 (F32X3: exact fp32 here); everything behind the
+  // encoder -- instance classifier, q, scores, softmax, pooling, fcc -- is fp32 in every mode: a 16-bit instance score
+  // could pick another critical instance
+  const int gemm_prec = desc->enc.compute == RRT_COMPUTE_F32X3 ? RRT_COMPUTE_F32 : desc->enc.compute;
+  LinearEpilogue ep{};
+  ep.prec = gemm_prec;
+  ep.bias = w->emb_b;
+  ep.act = desc->emb_act;
+  hipError_t e;
+  if ((gemm_prec == RRT_COMPUTE_BF16 || gemm_prec == RRT_COMPUTE_F16) && desc->input_dim % 64 == 0) {
+    uint16_t* x16 = (uint16_t*)p;
+    uint16_t* w16 = (uint16_t*)(p + align_up((size_t)n_tokens * desc->input_dim * 2, 256));
+    Cast16Jobs cj{};
+    cj.src[0] = x; cj.dst[0] = x16; cj.n4[0] = (size_t)n_tokens * desc->input_dim / 4;
+    cj.src[1] = w->emb_w; cj.dst[1] = w16; cj.n4[1] = (size_t)D * desc->input_dim / 4;
+    cj.count = 2;
+    e = launch_cast16(cj, gemm_prec, st);
+    if (e != hipSuccess) return (int)e;
+    e = launch_linear16(x16, w16, emb, (int)n_tokens, D, desc->input_dim, ep, st);
+  } else {
+    e = launch_linear(x, w->emb_w, emb, (int)n_tokens, D, desc->input_dim, ep, st);
+  }
+  if (e != hipSuccess) return (int)e;
+  if (desc->has_rrt) {
+    rc = encoder_forward(&desc->enc, &w->enc, emb, y, n_tokens, enc_ws, enc_bytes, stream, nullptr);
+    if (rc) return rc;
+  }
+  e = launch_instance_max(y, w->icls_w, w->icls_b, nullptr, cm, am, iws.pv, iws.pi, (int)n_tokens, D, K, st);
+  if (e != hipSuccess) return (int)e;
+  return (int)launch_dsmil_pool(emb, am, w->q_w, w->q_b, w->fcc_w, w->fcc_b, logits, A, B, dws.raw, dws.v, dws.vb, dws.lpart,
+                                dws.part, (int)n_tokens, D, desc->q_dim, K, st);
 }
 
 }  // extern "C"

@@ -254,6 +254,18 @@ hipError_t launch_branch_pool_backward(const float* y, const float* hid_a, const
                                        float* dhid_b, float* dwcb, float* part, int N, int dim, int hid, int K, hipStream_t st);
 hipError_t launch_topk_rows(const float* x, long long* out, int rows, int N, int k, hipStream_t st);
 
+// DSMIL head (dsmil_pool.hip): instance classifier + column max / arg-max, and the bag stream in one pass over feats
+constexpr int IMAX_CHUNK = 128;  // tokens per (max, index) record of the instance stream
+constexpr int DS_CHUNK = 32;     // tokens per online-softmax record of the bag stream (one wave)
+size_t instance_max_part_records(int N);
+size_t dsmil_pool_part_floats(int N, int dim, int K);
+size_t dsmil_pool_merge_lds(int N, int dim);
+hipError_t launch_instance_max(const float* y, const float* w, const float* b, float* classes, float* cmax, long long* argmax,
+                               float* pv, int* pi, int N, int dim, int K, hipStream_t st);
+hipError_t launch_dsmil_pool(const float* feats, const long long* argmax, const float* q_w, const float* q_b, const float* fcc_w,
+                             const float* fcc_b, float* logits, float* A, float* B, float* raw, float* v, float* vb, float* lpart,
+                             float* part, int N, int dim, int Q, int K, hipStream_t st);
+
 // ---- row f2 building blocks (backward)
 // nn.Linear backward: dX = dY W (forward GEMM on a transposed W), dW = dY^T X (split-K TN kernel), db = colsum(dY)
 size_t linear_bwd_workspace(int M, int N, int K);

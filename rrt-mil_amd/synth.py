@@ -176,3 +176,21 @@ def clam_head_state(shapes, tag):
             score = "attention_c" in key or (".module." in key and ".module.0." not in key)
             out[key] = (normal(f"clam/{tag}/{key}", shape) * ((1.2 if score else 1.0) / np.sqrt(shape[-1]))).astype(np.float32)
     return out
+
+
+def dsmil_head_state(shapes, tag):
+    """Closed-form parameters for a DSMIL head (rrt_mil_amd.MILNet without the encoder's entries): ``shapes`` is an ordered
+    {state_dict key: shape}.  Weights N(0, 1) * gain / sqrt(fan_in) -- gain 1.5 on ``i_classifier`` (instance scores of O(1)
+    on the encoder's LayerNorm-ed rows, so that the critical instances stand out) and 2.0 on ``b_classifier.q`` (the scores
+    q . q_max / sqrt(128) are a product of two of them: an attention that is visibly non-uniform over the bag); biases
+    uniform in +-0.1."""
+    out = {}
+    for key, shape in shapes.items():
+        shape = tuple(shape)
+        if key.endswith(".bias"):
+            out[key] = uniform(f"dsmil/{tag}/{key}", shape, -0.1, 0.1)
+        else:
+            gain = 1.5 if key.startswith("i_classifier") else (2.0 if ".q." in key else 1.0)
+            fan_in = int(np.prod(shape[1:]))
+            out[key] = (normal(f"dsmil/{tag}/{key}", shape) * (gain / np.sqrt(fan_in))).astype(np.float32)
+    return out

@@ -652,6 +652,38 @@ int rrt_region_attention_backward_f32(const float *qkv, const float *pe_w, const
                                       float *d_qkv, float *d_pe_w, int32_t n_regions, int32_t P, int32_t dim,
                                       int32_t heads, int32_t epeg_k, void *workspace, size_t workspace_bytes,
                                       void *stream);
+/* ---- stage entry points of the ablation kernels: one launcher each, so that a test can hold a single kernel to a reference.
+ * PEG / PPEG (emb_position.py:24-82) on x [N, dim] -> y [N, dim].  w / b / dw / db: HOST arrays of three DEVICE pointers, proj
+ * [dim, 1, k, kw], proj1 (5) and proj2 (3), kw = 1 when conv_1d else the kernel's side; PEG reads [0] only; b, db and any of
+ * their entries may be NULL.  k odd <= 11, dim a multiple of 4.  The backward takes the stage's input x and dy, writes dx, every
+ * dw and the db that are given; workspace: rrt_peg_backward_workspace_size bytes. */
+int rrt_peg_f32(const float *x, const float *const *w, const float *const *b, float *y, int64_t N, int32_t dim, int32_t k,
+                int32_t conv_1d, int32_t ppeg, void *stream);
+int rrt_peg_backward_workspace_size(int64_t N, int32_t dim, int32_t k, int32_t ppeg, size_t *bytes);
+int rrt_peg_backward_f32(const float *x, const float *dy, const float *const *w, float *dx, float *const *dw, float *const *db,
+                         int64_t N, int32_t dim, int32_t k, int32_t conv_1d, int32_t ppeg, void *workspace,
+                         size_t workspace_bytes, void *stream);
+/* 2-D 'attn' EPEG (rmsa.py:78-79,106-108): o = softmax(S + conv2d_k(S)) V per (region, head), S = q k^T, on qkv
+ * [n_regions*P, 3*dim] as the qkv linear wrote it (q scaled); pe_w [heads, k, k], k odd <= 63.  The conv bias cancels in the softmax
+ * and is not an argument.  scratch: rrt_attn_scoremap_scratch_size bytes -- the forward's is 0 while a [P, P] map fits the LDS
+ * (scratch may then be NULL); the backward's holds three maps per (region, head) once they no longer fit, and the per-region tap
+ * partials behind them.  The backward writes d_qkv (gradient w.r.t. the qkv linear's raw output) and d_pe_w. */
+int rrt_attn_scoremap_scratch_size(int32_t n_regions, int32_t P, int32_t heads, int32_t k, int32_t backward, size_t *bytes);
+int rrt_attn_scoremap_f32(const float *qkv, const float *pe_w, float *o, int32_t n_regions, int32_t P, int32_t dim,
+                          int32_t heads, int32_t k, void *scratch, size_t scratch_bytes, void *stream);
+int rrt_attn_scoremap_backward_f32(const float *qkv, const float *pe_w, const float *d_o, float *d_qkv, float *d_pe_w,
+                                   int32_t n_regions, int32_t P, int32_t dim, int32_t heads, int32_t k, void *scratch,
+                                   size_t scratch_bytes, void *stream);
+/* value EPEG (rmsa.py:80-85,114-129): pe [n_regions*P, dim] = depth-wise conv (k x k when two_d, else (k, 1)) over the v columns of
+ * qkv laid out as an s x s image per region (P = s*s), image channel c reading v column (c % heads) * (dim / heads) + c / heads;
+ * w [dim, 1, k, kw], bias [dim] or NULL.  The backward ADDS the conv's dv into the v columns of d_qkv (q and k columns untouched),
+ * writes d_w and, when given, d_b; vsub [n_regions*P, dim] (or NULL) is subtracted from the v columns first ('value_bf' keeps
+ * v + pe in qkv). */
+int rrt_value_pe_f32(const float *qkv, const float *w, const float *bias, float *pe, int32_t n_regions, int32_t P, int32_t s,
+                     int32_t dim, int32_t heads, int32_t k, int32_t two_d, void *stream);
+int rrt_value_pe_backward_f32(const float *d_pe, const float *qkv, const float *vsub, const float *w, float *d_qkv, float *d_w,
+                              float *d_b, int32_t n_regions, int32_t P, int32_t s, int32_t dim, int32_t heads, int32_t k,
+                              int32_t two_d, void *stream);
 /* LayerNorm backward (eps 1e-5): dx [L, dim] = d/dx of LN(x) . dy (+ add, the residual branch's gradient,
  * optional); dgamma_dbeta [2, dim].  g != NULL: dy is region-major padded [H*H, dim] (the qkv-linear backward's
  * output) and token t reads its slot -- the adjoint of zero-pad + region_partition.  workspace: 512*2*dim floats. */

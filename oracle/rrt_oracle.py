@@ -403,12 +403,14 @@ def forward_f64(x, state, cfg=None, taps=None, lowp=None):
 
 
 # --------------------------------------------------------------------------- eager-equivalent torch/CPU port
-def forward_eager(x, state, cfg=None, grad=False, drop=None, autocast=None, branch=None):
+def forward_eager(x, state, cfg=None, grad=False, drop=None, autocast=None, branch=None, grad_dtype=None):
     """torch fp32 CPU port issuing the reference's aten op sequence; x: (N, D)
     torch tensor or array -> torch (N, D); or (B, N, D) -> (B, N, D): at B > 1 the reference couples the bags
     inside CR-MSA (its inner attention runs over the regions of all bags, rmsa.py:296-322).  Used as the timed CPU baseline.
     grad=True: float64 leaves with requires_grad (x and every parameter) and a recorded graph -- torch autograd
     then yields the reference's gradients (the oracle of the backward, row f2); returns (y, x_leaf, params).
+    grad_dtype = torch.float32 with grad=True: the same graph on float32 leaves -- what plain fp32 eager arithmetic makes of
+    the gradients, the yardstick a kernel's own distance from float64 is held against.
     drop = (p, {layer: keep mask [rows, D]}): train-mode proj_drop (rmsa.py:132) with GIVEN masks (layer index, or
     "cr_msa"), i.e. nn.Dropout's arithmetic x * keep / (1 - p) without its random number generator.
     branch = {(layer index | "cr_msa", "attn" | "ffn"): multiplier}: stochastic depth with GIVEN draws -- timm's
@@ -423,8 +425,9 @@ def forward_eager(x, state, cfg=None, grad=False, drop=None, autocast=None, bran
           for k_, v_ in state.items()}
     x = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
     if grad:
-        st = {k_: v_.double().requires_grad_(True) for k_, v_ in st.items()}
-        x = x.double().requires_grad_(True)
+        gd = grad_dtype or torch.float64
+        st = {k_: v_.to(gd).requires_grad_(True) for k_, v_ in st.items()}
+        x = x.to(gd).requires_grad_(True)
         x_leaf = x
     batched = x.dim() == 3                                                   # (B,N,D): returned with its batch axis
     if not batched:

@@ -160,6 +160,14 @@ SIGNATURES = {
                                                               C.POINTER(Grid), C.c_void_p]),
     "rrt_crmsa_mlp_logits_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "rrt_layernorm_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_void_p]),
+    "rrt_peg_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int64] + [C.c_int32] * 4 + [C.c_void_p]),
+    "rrt_peg_backward_workspace_size": (C.c_int, [C.c_int64] + [C.c_int32] * 3 + [C.POINTER(C.c_size_t)]),
+    "rrt_peg_backward_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int64] + [C.c_int32] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_attn_scoremap_scratch_size": (C.c_int, [C.c_int32] * 5 + [C.POINTER(C.c_size_t)]),
+    "rrt_attn_scoremap_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_attn_scoremap_backward_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_value_pe_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 7 + [C.c_void_p]),
+    "rrt_value_pe_backward_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 7 + [C.c_void_p]),
     "rrt_mil_workspace_size": (C.c_int, [C.POINTER(MilDesc), C.c_int64, C.POINTER(C.c_size_t)]),
     "rrt_mil_forward_f32": (C.c_int, [C.POINTER(MilDesc), C.POINTER(MilWeights), C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,

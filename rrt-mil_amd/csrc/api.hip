@@ -2214,6 +2214,111 @@ int rrt_layernorm_backward_f32(const float* dy, const float* x, const float* gam
                                  g ? &gd : nullptr, (hipStream_t)stream);
 }
 
+// ---- stage entry points of the ablation kernels (peg.hip, epeg_variants.hip): one launcher each, arguments checked
+namespace {
+int check_peg_stage(int64_t N, int32_t dim, int32_t k) {
+  if (N <= 0 || N > (int64_t)4000000 || dim <= 0) return RRT_E_INVALID;
+  if (dim % 4) return unsupported("peg: dim must be a multiple of 4");
+  if (k <= 0 || k % 2 == 0 || k > 11) return unsupported("peg_k must be odd and <= 11");
+  return RRT_OK;
+}
+int check_epeg_stage(int32_t n_regions, int32_t P, int32_t dim, int32_t heads, int32_t k) {
+  if (n_regions <= 0 || P <= 0 || dim <= 0 || heads <= 0) return RRT_E_INVALID;
+  if (dim % 4) return unsupported("epeg ablations: dim must be a multiple of 4");
+  if (dim % heads) return unsupported("n_heads must divide dim");
+  if (k <= 0 || k % 2 == 0) return unsupported("epeg_k must be odd");
+  if (k > 63) return unsupported("epeg ablations: epeg_k <= 63");
+  if ((int64_t)n_regions * P > (int64_t)4000000 || n_regions > 65535) return unsupported("epeg ablations: more than 65535 regions or 4e6 slots");
+  return RRT_OK;
+}
+size_t scoremap_scratch_bytes(int n_regions, int P, int heads, int k, int backward) {
+  if (!backward) return attn_scoremap_scratch_floats(n_regions, P, heads, k, 1) * sizeof(float);
+  return (attn_scoremap_scratch_floats(n_regions, P, heads, k, 3) + (size_t)n_regions * heads * k * k) * sizeof(float);
+}
+}  // namespace
+
+int rrt_peg_f32(const float* x, const float* const* w, const float* const* b, float* y, int64_t N, int32_t dim, int32_t k,
+                int32_t conv_1d, int32_t ppeg, void* stream) {
+  if (!x || !y || !w || !w[0] || (ppeg && (!w[1] || !w[2]))) return RRT_E_INVALID;
+  const int rc = check_peg_stage(N, dim, k);
+  if (rc) return rc;
+  const float* nob[3] = {nullptr, nullptr, nullptr};
+  return (int)launch_peg(x, w, b ? b : nob, y, (int)N, dim, k, conv_1d != 0, ppeg != 0, (hipStream_t)stream);
+}
+
+int rrt_peg_backward_workspace_size(int64_t N, int32_t dim, int32_t k, int32_t ppeg, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  const int rc = check_peg_stage(N, dim, k);
+  if (rc) return rc;
+  *bytes = peg_bwd_workspace((int)N, dim, k, ppeg != 0);
+  return RRT_OK;
+}
+
+int rrt_peg_backward_f32(const float* x, const float* dy, const float* const* w, float* dx, float* const* dw, float* const* db,
+                         int64_t N, int32_t dim, int32_t k, int32_t conv_1d, int32_t ppeg, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  if (!x || !dy || !dx || !w || !dw || !w[0] || !dw[0] || (ppeg && (!w[1] || !w[2] || !dw[1] || !dw[2]))) return RRT_E_INVALID;
+  const int rc = check_peg_stage(N, dim, k);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < peg_bwd_workspace((int)N, dim, k, ppeg != 0)) return RRT_E_WORKSPACE;
+  float* const nodb[3] = {nullptr, nullptr, nullptr};
+  return (int)launch_peg_backward(x, dy, w, dx, dw, db ? db : nodb, (int)N, dim, k, conv_1d != 0, ppeg != 0, workspace,
+                                  (hipStream_t)stream);
+}
+
+int rrt_attn_scoremap_scratch_size(int32_t n_regions, int32_t P, int32_t heads, int32_t k, int32_t backward, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  const int rc = check_epeg_stage(n_regions, P, 4 * heads, heads, k);
+  if (rc) return rc;
+  *bytes = scoremap_scratch_bytes(n_regions, P, heads, k, backward != 0);
+  return RRT_OK;
+}
+
+int rrt_attn_scoremap_f32(const float* qkv, const float* pe_w, float* o, int32_t n_regions, int32_t P, int32_t dim,
+                          int32_t heads, int32_t k, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!qkv || !pe_w || !o) return RRT_E_INVALID;
+  const int rc = check_epeg_stage(n_regions, P, dim, heads, k);
+  if (rc) return rc;
+  if (((size_t)k * k + 4 * (size_t)P) * sizeof(float) > 160 * 1024) return unsupported("attn_scoremap: region too large");
+  const size_t need = scoremap_scratch_bytes(n_regions, P, heads, k, 0);
+  if (need && (!scratch || scratch_bytes < need)) return RRT_E_WORKSPACE;
+  return (int)launch_attn_scoremap(qkv, pe_w, o, need ? (float*)scratch : nullptr, n_regions, P, dim, heads, k,
+                                   (hipStream_t)stream);
+}
+
+int rrt_attn_scoremap_backward_f32(const float* qkv, const float* pe_w, const float* d_o, float* d_qkv, float* d_pe_w,
+                                   int32_t n_regions, int32_t P, int32_t dim, int32_t heads, int32_t k, void* scratch,
+                                   size_t scratch_bytes, void* stream) {
+  if (!qkv || !pe_w || !d_o || !d_qkv || !d_pe_w) return RRT_E_INVALID;
+  const int rc = check_epeg_stage(n_regions, P, dim, heads, k);
+  if (rc) return rc;
+  if (((size_t)k * k + 4 * (size_t)P) * sizeof(float) > 160 * 1024) return unsupported("attn_scoremap: region too large");
+  if (!scratch || scratch_bytes < scoremap_scratch_bytes(n_regions, P, heads, k, 1)) return RRT_E_WORKSPACE;
+  return (int)launch_attn_scoremap_backward(qkv, pe_w, d_o, d_qkv, d_pe_w, (float*)scratch, n_regions, P, dim, heads, k,
+                                            (hipStream_t)stream);
+}
+
+int rrt_value_pe_f32(const float* qkv, const float* w, const float* bias, float* pe, int32_t n_regions, int32_t P, int32_t s,
+                     int32_t dim, int32_t heads, int32_t k, int32_t two_d, void* stream) {
+  if (!qkv || !w || !pe || s <= 0) return RRT_E_INVALID;
+  const int rc = check_epeg_stage(n_regions, P, dim, heads, k);
+  if (rc) return rc;
+  if ((int64_t)s * s != P) return unsupported("value epeg: the region must be an s x s image");
+  return (int)launch_value_pe(qkv, w, bias, pe, n_regions, P, s, dim, heads, k, two_d != 0, (hipStream_t)stream);
+}
+
+int rrt_value_pe_backward_f32(const float* d_pe, const float* qkv, const float* vsub, const float* w, float* d_qkv, float* d_w,
+                              float* d_b, int32_t n_regions, int32_t P, int32_t s, int32_t dim, int32_t heads, int32_t k,
+                              int32_t two_d, void* stream) {
+  if (!d_pe || !qkv || !w || !d_qkv || !d_w || s <= 0) return RRT_E_INVALID;
+  const int rc = check_epeg_stage(n_regions, P, dim, heads, k);
+  if (rc) return rc;
+  if ((int64_t)s * s != P) return unsupported("value epeg: the region must be an s x s image");
+  if ((size_t)2 * P * sizeof(float) > 160 * 1024) return unsupported("value epeg backward: region too large");
+  return (int)launch_value_pe_backward(d_pe, qkv, vsub, w, d_qkv, d_w, d_b, n_regions, P, s, dim, heads, k, two_d != 0,
+                                       (hipStream_t)stream);
+}
+
 int rrt_reduce_partials_f32(const float* part, float* out, float* out_tr, int32_t S, int64_t n, int64_t split,
                             int32_t tr_dim, int32_t tr_k, int32_t deferred, int32_t copies, void* stream) {
   if (!part || !out || S <= 0 || n <= 0 || S > (1 << 20)) return RRT_E_INVALID;

@@ -96,19 +96,31 @@ __global__ __launch_bounds__(256) void peg_kernel(const float* __restrict__ x, c
 
 }  // namespace
 
-// w[0..2], b[0..2]: proj (k), proj1 (5), proj2 (3); PEG: only [0].  k odd <= 11.
-static hipError_t launch_peg_impl(const float* x, const float* const* w, const float* const* b, float* y, int N, int C,
-                                  int k, int conv_1d, int ppeg, int bwd, hipStream_t st) {
+// side of the wrapped square H0 = ceil(sqrt(N)) (exact: the double square root is corrected in both directions) and of the
+// grid the stencil runs on (PPEG zero-pads a square smaller than 7 x 7 up to 7 x 7)
+static void peg_sides(int N, int ppeg, int* H0_out, int* H_out) {
   int H0 = (int)ceil(sqrt((double)N));
   while ((long)H0 * H0 < N) ++H0;
   while (H0 > 1 && (long)(H0 - 1) * (H0 - 1) >= N) --H0;
-  const int H = (ppeg && H0 < 7) ? 7 : H0;
+  *H0_out = H0;
+  *H_out = (ppeg && H0 < 7) ? 7 : H0;
+}
+
+// the CU's LDS: no instantiation may ask for more (checked where each one is launched)
+constexpr size_t PEG_LDS_MAX = 160 * 1024;
+
+// w[0..2], b[0..2]: proj (k), proj1 (5), proj2 (3); PEG: only [0].  k odd <= 11.
+static hipError_t launch_peg_impl(const float* x, const float* const* w, const float* const* b, float* y, int N, int C,
+                                  int k, int conv_1d, int ppeg, int bwd, hipStream_t st) {
+  int H0, H;
+  peg_sides(N, ppeg, &H0, &H);
   const int KK = ppeg ? (k > 5 ? k : 5) : k;
   const int tiles = ((H + 7) / 8) * ((H + 7) / 8);
   dim3 grid(tiles, (C + 63) / 64), block(256);
 #define RRT_PEG(K_)                                                                                           \
   do {                                                                                                        \
     constexpr size_t lds = (size_t)(8 + 2 * (K_ / 2)) * (8 + 2 * (K_ / 2)) * 64 * sizeof(float);              \
+    static_assert(lds <= PEG_LDS_MAX, "peg_kernel<K>: the patch does not fit the CU's LDS");                  \
     auto kern = peg_kernel<K_>;                                                                               \
     if (lds > 64 * 1024)                                                                                      \
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     \
@@ -155,7 +167,7 @@ __global__ __launch_bounds__(256) void peg_bwd_dw_kernel(const float* __restrict
   constexpr int HALO = KK / 2, SIDE = 8 + 2 * HALO;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* tile = (float*)smem;                           // [SIDE * SIDE][64]
-  float* red = tile + SIDE * SIDE * 64;                 // [3][KK * KK][64]
+  float* red = (float*)smem;                            // [3][KK * KK][64], in the patch's place once acc[] is formed
   const int tid = threadIdx.x;
   const int tiles_w = (H + 7) / 8;
   const int ti0 = (blockIdx.x / tiles_w) * 8, tj0 = (blockIdx.x % tiles_w) * 8;
@@ -188,6 +200,7 @@ __global__ __launch_bounds__(256) void peg_bwd_dw_kernel(const float* __restrict
       }
   }
   const int q = tid >> 6;
+  __syncthreads();                                      // every read of the patch is done: its storage takes the partial sums
   if (q > 0) {
 #pragma unroll
     for (int i = 0; i < KK * KK; ++i) red[((q - 1) * KK * KK + i) * 64 + cl] = acc[i];
@@ -199,6 +212,12 @@ __global__ __launch_bounds__(256) void peg_bwd_dw_kernel(const float* __restrict
       part[((size_t)blockIdx.x * KK * KK + i) * C + c] =
           acc[i] + red[i * 64 + cl] + red[(KK * KK + i) * 64 + cl] + red[(2 * KK * KK + i) * 64 + cl];
   }
+}
+
+// LDS of peg_bwd_dw_kernel<K>: the larger of the patch and the three waves' partial sums that take its place
+constexpr size_t peg_bwd_dw_lds(int K) {
+  const size_t side = 8 + 2 * (K / 2), patch = side * side * 64, red = (size_t)3 * K * K * 64;
+  return (patch > red ? patch : red) * sizeof(float);
 }
 
 // dWeff [KK*KK][C] -> the convs' own weight gradients [C, 1, k, kw]
@@ -214,9 +233,8 @@ __global__ __launch_bounds__(256) void peg_scatter_dw_kernel(const float* __rest
 }  // namespace
 
 size_t peg_bwd_workspace(int N, int C, int k, int ppeg) {
-  int H0 = (int)ceil(sqrt((double)N));
-  while ((long)H0 * H0 < N) ++H0;
-  const int H = (ppeg && H0 < 7) ? 7 : H0;
+  int H0, H;
+  peg_sides(N, ppeg, &H0, &H);
   const int KK = ppeg ? (k > 5 ? k : 5) : (k < 3 ? 3 : k);
   const size_t tiles = (size_t)((H + 7) / 8) * ((H + 7) / 8);
   return ((size_t)H0 * H0 * C + (tiles + 1) * KK * KK * C + (size_t)((N + 127) / 128 + 1) * C) * sizeof(float) + 1024;
@@ -226,10 +244,8 @@ size_t peg_bwd_workspace(int N, int C, int k, int ppeg) {
 // forward stage.  ws: peg_bwd_workspace bytes.
 hipError_t launch_peg_backward(const float* x, const float* dy, const float* const* w, float* dx, float* const* dw,
                                float* const* db, int N, int C, int k, int conv_1d, int ppeg, void* ws, hipStream_t st) {
-  int H0 = (int)ceil(sqrt((double)N));
-  while ((long)H0 * H0 < N) ++H0;
-  while (H0 > 1 && (long)(H0 - 1) * (H0 - 1) >= N) --H0;
-  const int H = (ppeg && H0 < 7) ? 7 : H0;
+  int H0, H;
+  peg_sides(N, ppeg, &H0, &H);
   const int KK = ppeg ? (k > 5 ? k : 5) : (k < 3 ? 3 : k);
   const int tiles = ((H + 7) / 8) * ((H + 7) / 8);
   float* g = (float*)ws;                                  // [H0*H0][C] adjoint-stencil output
@@ -244,7 +260,8 @@ hipError_t launch_peg_backward(const float* x, const float* dy, const float* con
   dim3 grid(tiles, (C + 63) / 64);
 #define RRT_PEGW(K_)                                                                                          \
   do {                                                                                                        \
-    constexpr size_t lds = ((size_t)(8 + 2 * (K_ / 2)) * (8 + 2 * (K_ / 2)) * 64 + 3 * K_ * K_ * 64) * sizeof(float); \
+    constexpr size_t lds = peg_bwd_dw_lds(K_);                                                                \
+    static_assert(lds <= PEG_LDS_MAX, "peg_bwd_dw_kernel<K>: patch / partial sums do not fit the CU's LDS");  \
     auto kern = peg_bwd_dw_kernel<K_>;                                                                        \
     if (lds > 64 * 1024)                                                                                      \
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     \

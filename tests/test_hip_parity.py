@@ -2208,6 +2208,11 @@ TRAIN_CASES = {
     "attn2d_n1000_k5": (1000, dict(mlp_dim=512, epeg_k=5, crmsa_k=3, epeg_2d=True)),
     "valuebf_n700": (700, dict(mlp_dim=512, epeg_k=9, crmsa_k=3, epeg_type="value_bf")),
     "valueaf2d_n9000_k3": (9000, dict(mlp_dim=512, epeg_k=3, crmsa_k=3, epeg_type="value_af", epeg_2d=True)),
+    # the other two value-EPEG type / shape combinations and the PEG / PPEG kernels' largest instantiations
+    "valueaf1d_n700_k9": (700, dict(mlp_dim=512, epeg_k=9, crmsa_k=3, epeg_type="value_af")),
+    "valuebf2d_n700_k3": (700, dict(mlp_dim=512, epeg_k=3, crmsa_k=3, epeg_type="value_bf", epeg_2d=True)),
+    "pos_peg_k11_n500": (500, dict(mlp_dim=512, crmsa_k=3, pos="peg", pos_pos=-1, peg_k=11)),
+    "pos_ppeg1d_k9_n500": (500, dict(mlp_dim=512, crmsa_k=3, pos="ppeg", pos_pos=-1, peg_k=9, peg_1d=True)),
 }
 
 

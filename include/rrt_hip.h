@@ -751,6 +751,93 @@ int rrt_encoder_backward_f32(const rrt_encoder_desc *desc, const rrt_encoder_wei
                              size_t workspace_bytes, float drop_p, uint64_t drop_seed,
                              const float *branch_scale, void *stream);
 
+/* ---- Nystrom attention and the TransMIL baseline (modules/nystrom_attention.py:67-149, modules/transmil.py:26-125; exports
+ * added under ABI 29, no existing struct touched).  Inference, exact fp32 on the fp32 matrix cores, no atomics: the same inputs
+ * give the same bits.  There is no mask argument (the reference's mask branch names undefined variables).
+ * Supported: dim_head = 64, num_landmarks = 256, residual_conv_kernel odd <= 63, pinv_iterations 1..16, heads 1..16,
+ * dim % 32 == 0, dim <= 1024, n <= 1e6; otherwise RRT_E_UNSUPPORTED with the field's name in rrt_strerror. */
+typedef struct rrt_nystrom_desc {
+  int32_t dim;
+  int32_t heads;
+  int32_t dim_head;
+  int32_t num_landmarks;
+  int32_t pinv_iterations;
+  int32_t residual;              /* 1: + the depth-wise conv of v along the tokens (res_conv) */
+  int32_t residual_conv_kernel;
+} rrt_nystrom_desc;
+
+/* to_qkv.weight [3 * heads * dim_head, dim] (no bias), to_out.0.weight [dim, heads * dim_head], to_out.0.bias [dim],
+ * res_conv.weight [heads, 1, k, 1] (read only when residual != 0) */
+typedef struct rrt_nystrom_weights {
+  const float *qkv_w;
+  const float *out_w, *out_b;
+  const float *conv_w;
+} rrt_nystrom_weights;
+
+int rrt_nystrom_workspace_size(const rrt_nystrom_desc *desc, int64_t n, size_t *bytes);
+/* NystromAttention.forward: x [n, dim] (already normalised by the caller's LayerNorm) -> y [n, dim]; the caller's residual
+ * is NOT included.  np = n rounded up to a multiple of 256; the np - n zero rows go in FRONT of x and take part in the
+ * landmarks, in both softmaxes over the keys and in the conv, as in the reference. */
+int rrt_nystrom_attention_f32(const rrt_nystrom_desc *desc, const rrt_nystrom_weights *w, const float *x, float *y,
+                              int64_t n, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Stage entry points, one per kernel.  n_padded = np, a positive multiple of 256 (l = np / 256).
+ * qkv [np, 3 * heads * 64]: the qkv linear's output, q columns already scaled by 64^-0.5, front pad rows zero.
+ *  landmarks     : ql, kl [heads, 256, 64] = means of l consecutive rows of q and of k (divisor always l);
+ *  landmark_sim  : a2 [heads, 256, 256] = softmax(ql kl^T);
+ *  landmark_attn : av [heads, 256, 64] = softmax(ql k^T) v over all np keys (chunks of keys with an online softmax, the
+ *                  chunk records merged in chunk order);
+ *  pinv          : z [heads, 256, 256] = `iterations` steps of z <- 1/4 z (13 I - a2 z (15 I - a2 z (7 I - a2 z))) from
+ *                  z0 = a2^T / (max row abs sum * max column abs sum), both maxima over ALL heads;
+ *  zav           : wz [heads, 256, 64] = z av;
+ *  output        : o [np, heads * 64] = softmax(q kl^T) wz + conv_k(v) (conv_w [heads, conv_k] or NULL = no conv), heads merged. */
+int rrt_nystrom_landmarks_f32(const float *qkv, float *ql, float *kl, int64_t n_padded, int32_t heads, void *stream);
+int rrt_nystrom_landmark_sim_f32(const float *ql, const float *kl, float *a2, int32_t heads, void *stream);
+int rrt_nystrom_landmark_attn_workspace_size(int64_t n_padded, int32_t heads, size_t *bytes);
+int rrt_nystrom_landmark_attn_f32(const float *qkv, const float *ql, float *av, int64_t n_padded, int32_t heads,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+int rrt_nystrom_pinv_workspace_size(int32_t heads, size_t *bytes);
+int rrt_nystrom_pinv_f32(const float *a2, float *z, int32_t heads, int32_t iterations, void *workspace,
+                         size_t workspace_bytes, void *stream);
+int rrt_nystrom_zav_f32(const float *z, const float *av, float *wz, int32_t heads, void *stream);
+int rrt_nystrom_output_f32(const float *qkv, const float *kl, const float *wz, const float *conv_w, float *o,
+                           int64_t n_padded, int32_t heads, int32_t conv_k, void *stream);
+
+/* TransMIL's PPEG (transmil.py:47-61): x, y [1 + side * side, dim]; row 0 (the cls token) passes through, the other rows as
+ * a side x side image become x + conv7(x) + conv5(x) + conv3(x), depth-wise with zero borders.  The side is EXACTLY the
+ * caller's (rrt_peg_f32 derives it from the row count, wraps, and lifts sides below 7 to 7).  w / b: HOST arrays of three
+ * DEVICE pointers proj [dim, 1, 7, 7], proj1 (5), proj2 (3); b or its entries may be NULL.  dim % 4 == 0, side <= 1000. */
+int rrt_ppeg_side_f32(const float *x, const float *const *w, const float *const *b, float *y, int32_t side, int32_t dim,
+                      void *stream);
+
+/* TransMIL.forward (eval, one bag): _fc1 Linear(input_dim, dim) + act -> wrap to H * H rows (H = ceil(sqrt(N))) ->
+ * cls token in front -> x + Nystrom(LN(x)) -> PPEG -> x + Nystrom(LN(x)) -> LN, row 0 -> _fc2. */
+typedef struct rrt_transmil_desc {
+  int32_t input_dim;       /* patch feature width (multiple of 32) */
+  int32_t n_classes;       /* 1..64 */
+  int32_t act;             /* RRT_ACT_RELU / RRT_ACT_GELU / RRT_ACT_NONE */
+  rrt_nystrom_desc attn;   /* both layers; attn.dim is the model width (512 in the reference) */
+} rrt_transmil_desc;
+
+typedef struct rrt_transmil_layer_weights {
+  const float *norm_w, *norm_b;   /* layer{1,2}.norm */
+  rrt_nystrom_weights attn;        /* layer{1,2}.attn */
+} rrt_transmil_layer_weights;
+
+typedef struct rrt_transmil_weights {
+  const float *fc1_w, *fc1_b;      /* _fc1.0 [dim, input_dim], [dim] */
+  const float *cls_token;          /* [dim] */
+  rrt_transmil_layer_weights layer[2];
+  const float *pos_w[3], *pos_b[3];/* pos_layer.proj / proj1 / proj2 */
+  const float *norm_w, *norm_b;    /* norm */
+  const float *fc2_w, *fc2_b;      /* _fc2 [n_classes, dim], [n_classes] */
+} rrt_transmil_weights;
+
+int rrt_transmil_workspace_size(const rrt_transmil_desc *desc, int64_t n_tokens, size_t *bytes);
+/* x [n_tokens, input_dim] -> logits [n_classes].  feat (optional, [1 + H * H, dim]): the rows before the last LayerNorm. */
+int rrt_transmil_forward_f32(const rrt_transmil_desc *desc, const rrt_transmil_weights *w, const float *x, float *logits,
+                             float *feat, int64_t n_tokens, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,8 +32,9 @@ from ._lib import device_error  # noqa: F401,E402
 from .mil import Attention, AttentionGated, DAttention, RRTMIL  # noqa: F401,E402
 from .clam import CLAM_MB, CLAM_SB  # noqa: F401,E402
 from .dsmil import DSMIL, MILNet  # noqa: F401,E402
+from .transmil import NystromAttention, TransMIL  # noqa: F401,E402
 from .encoder import (CrossRegionAttntion, InnerAttention, RegionAttntion, RRTEncoder,  # noqa: F401
                       TransLayer, initialize_weights)
 
-__all__ = ["RRTEncoder", "RRTMIL", "CLAM_SB", "CLAM_MB", "MILNet", "DSMIL", "DAttention", "TransLayer", "RegionAttntion", "CrossRegionAttntion", "InnerAttention",
+__all__ = ["RRTEncoder", "RRTMIL", "CLAM_SB", "CLAM_MB", "MILNet", "DSMIL", "TransMIL", "NystromAttention", "DAttention", "TransLayer", "RegionAttntion", "CrossRegionAttntion", "InnerAttention",
            "initialize_weights", "geometry", "sharding", "synth", "device_error"]

@@ -90,6 +90,29 @@ class DsmilWeights(C.Structure):
         "emb_w", "emb_b", "icls_w", "icls_b", "q_w", "q_b", "fcc_w", "fcc_b")]
 
 
+class NystromDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dim", "heads", "dim_head", "num_landmarks", "pinv_iterations", "residual",
+                                         "residual_conv_kernel")]
+
+
+class NystromWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("qkv_w", "out_w", "out_b", "conv_w")]
+
+
+class TransmilDesc(C.Structure):
+    _fields_ = [("input_dim", C.c_int32), ("n_classes", C.c_int32), ("act", C.c_int32), ("attn", NystromDesc)]
+
+
+class TransmilLayerWeights(C.Structure):
+    _fields_ = [("norm_w", C.c_void_p), ("norm_b", C.c_void_p), ("attn", NystromWeights)]
+
+
+class TransmilWeights(C.Structure):
+    _fields_ = [("fc1_w", C.c_void_p), ("fc1_b", C.c_void_p), ("cls_token", C.c_void_p), ("layer", TransmilLayerWeights * 2),
+                ("pos_w", C.c_void_p * 3), ("pos_b", C.c_void_p * 3), ("norm_w", C.c_void_p), ("norm_b", C.c_void_p),
+                ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p)]
+
+
 class Bag(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("n_tokens", C.c_int64)]
 
@@ -222,6 +245,21 @@ SIGNATURES = {
                                            C.c_void_p]),
     "rrt_linear_act_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                         C.c_void_p]),
+    "rrt_nystrom_workspace_size": (C.c_int, [C.POINTER(NystromDesc), C.c_int64, C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_attention_f32": (C.c_int, [C.POINTER(NystromDesc), C.POINTER(NystromWeights), C.c_void_p, C.c_void_p,
+                                            C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_nystrom_landmarks_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_void_p]),
+    "rrt_nystrom_landmark_sim_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p]),
+    "rrt_nystrom_landmark_attn_workspace_size": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_landmark_attn_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_nystrom_pinv_workspace_size": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_pinv_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_nystrom_zav_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p]),
+    "rrt_nystrom_output_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "rrt_ppeg_side_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p]),
+    "rrt_transmil_workspace_size": (C.c_int, [C.POINTER(TransmilDesc), C.c_int64, C.POINTER(C.c_size_t)]),
+    "rrt_transmil_forward_f32": (C.c_int, [C.POINTER(TransmilDesc), C.POINTER(TransmilWeights)] + [C.c_void_p] * 3 +
+                                 [C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32X3 = 0, 1, 2, 3

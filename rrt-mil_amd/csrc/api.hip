@@ -2951,3 +2951,284 @@ int rrt_encoder_backward_f32(const rrt_encoder_desc* desc, const rrt_encoder_wei
 
 }  // extern "C"
 
+// ---- Nystrom attention and the TransMIL baseline (nystrom.hip)
+namespace {
+
+int check_nystrom_heads(int32_t heads) {
+  if (heads < 1 || heads > 16) return unsupported("nystrom: heads must be in 1..16");
+  return RRT_OK;
+}
+int check_nystrom_np(int64_t np) {
+  if (np <= 0) return RRT_E_INVALID;
+  if (np % 256) return unsupported("nystrom: n_padded must be a multiple of num_landmarks = 256");
+  if (np > 1000000 + 255) return unsupported("nystrom: n above 1e6");
+  return RRT_OK;
+}
+int check_nystrom(const rrt_nystrom_desc* d, int64_t n) {
+  if (!d || n <= 0) return RRT_E_INVALID;
+  if (d->dim_head != 64) return unsupported("nystrom: dim_head must be 64");
+  if (d->num_landmarks != 256) return unsupported("nystrom: num_landmarks must be 256");
+  if (d->residual && (d->residual_conv_kernel < 1 || d->residual_conv_kernel % 2 == 0 || d->residual_conv_kernel > 63))
+    return unsupported("nystrom: residual_conv_kernel must be odd and <= 63");
+  if (d->pinv_iterations < 1 || d->pinv_iterations > 16) return unsupported("nystrom: pinv_iterations must be in 1..16");
+  int rc = check_nystrom_heads(d->heads);
+  if (rc) return rc;
+  if (d->dim <= 0 || d->dim % 32 || d->dim > 1024) return unsupported("nystrom: dim must be a multiple of 32, at most 1024");
+  if (n > 1000000) return unsupported("nystrom: n above 1e6");
+  return RRT_OK;
+}
+
+struct NystromWs {
+  float *qkv, *ql, *kl, *a2, *z, *av, *wz, *o, *lattn, *pinv;
+  int64_t np;
+  size_t bytes;
+};
+NystromWs carve_nystrom(const rrt_nystrom_desc* d, int64_t n, char* base) {
+  NystromWs ws{};
+  const int64_t np = (n + 255) / 256 * 256;
+  const size_t hd = (size_t)d->heads * 64, lm = (size_t)d->heads * 256 * 64, mm = (size_t)d->heads * 256 * 256;
+  size_t off = 0;
+  auto take = [&](size_t floats) {
+    float* p = (float*)(base + off);
+    off += align_up(floats * sizeof(float), 256);
+    return p;
+  };
+  ws.np = np;
+  ws.qkv = take((size_t)np * 3 * hd);
+  ws.ql = take(lm);
+  ws.kl = take(lm);
+  ws.a2 = take(mm);
+  ws.z = take(mm);
+  ws.av = take(lm);
+  ws.wz = take(lm);
+  ws.o = take((size_t)np * hd);
+  ws.lattn = take(nystrom_lattn_floats((long)np, d->heads));
+  ws.pinv = take(nystrom_pinv_floats(d->heads));
+  ws.bytes = off;
+  return ws;
+}
+
+// y [n, dim] = NystromAttention(x); everything checked by the caller
+int nystrom_forward(const rrt_nystrom_desc* d, const rrt_nystrom_weights* w, const float* x, float* y, int64_t n,
+                    const NystromWs& ws, hipStream_t st) {
+  const int hd = d->heads * 64;
+  const int64_t pad = ws.np - n;
+  if (pad) RRT_TRY(hipMemsetAsync(ws.qkv, 0, (size_t)pad * 3 * hd * sizeof(float), st));
+  LinearEpilogue ep{};
+  ep.q_cols = hd;
+  ep.q_scale = 0.125f;                       // dim_head^-0.5, dim_head = 64
+  RRT_TRY(launch_linear(x, w->qkv_w, ws.qkv + (size_t)pad * 3 * hd, (int)n, 3 * hd, d->dim, ep, st));
+  RRT_TRY(launch_nystrom_landmarks(ws.qkv, ws.ql, ws.kl, (long)ws.np, d->heads, st));
+  RRT_TRY(launch_nystrom_sim2(ws.ql, ws.kl, ws.a2, d->heads, st));
+  RRT_TRY(launch_nystrom_lattn(ws.qkv, ws.ql, ws.av, ws.lattn, (long)ws.np, d->heads, st));
+  RRT_TRY(launch_nystrom_pinv(ws.a2, ws.z, ws.pinv, d->heads, d->pinv_iterations, st));
+  RRT_TRY(launch_nystrom_zav(ws.z, ws.av, ws.wz, d->heads, st));
+  RRT_TRY(launch_nystrom_output(ws.qkv, ws.kl, ws.wz, d->residual ? w->conv_w : nullptr, ws.o, (long)ws.np, d->heads,
+                                d->residual_conv_kernel, st));
+  LinearEpilogue eo{};
+  eo.bias = w->out_b;
+  RRT_TRY(launch_linear(ws.o + (size_t)pad * hd, w->out_w, y, (int)n, d->dim, hd, eo, st));
+  return RRT_OK;
+}
+
+bool nystrom_weights_ok(const rrt_nystrom_desc* d, const rrt_nystrom_weights* w) {
+  return w->qkv_w && w->out_w && w->out_b && (!d->residual || w->conv_w);
+}
+
+int ceil_sqrt_i64(int64_t n) {
+  int64_t h = (int64_t)ceil(sqrt((double)n));
+  while (h * h < n) ++h;
+  while (h > 1 && (h - 1) * (h - 1) >= n) --h;
+  return (int)h;
+}
+
+int check_transmil(const rrt_transmil_desc* d, int64_t N) {
+  if (!d || N <= 0) return RRT_E_INVALID;
+  if (N > 998001) return unsupported("transmil: n_tokens above 998001 (the 1 + H * H rows must stay within nystrom's n <= 1e6)");
+  int rc = check_nystrom(&d->attn, N);
+  if (rc) return rc;
+  if (d->input_dim <= 0 || d->input_dim % 32) return unsupported("input_dim must be a positive multiple of 32");
+  if (d->act != RRT_ACT_NONE && d->act != RRT_ACT_RELU && d->act != RRT_ACT_GELU) return unsupported("transmil: act must be none/relu/gelu");
+  if (d->n_classes < 1 || d->n_classes > 64) return unsupported("transmil: n_classes must be in 1..64");
+  return RRT_OK;
+}
+
+struct TransmilWs {
+  float *emb, *seq, *seq2, *ln, *att;
+  char* nys;
+  int64_t rows;
+  int side;
+  size_t bytes;
+};
+TransmilWs carve_transmil(const rrt_transmil_desc* d, int64_t N, char* base) {
+  TransmilWs ws{};
+  ws.side = ceil_sqrt_i64(N);
+  ws.rows = 1 + (int64_t)ws.side * ws.side;
+  const size_t D = (size_t)d->attn.dim;
+  size_t off = 0;
+  auto take = [&](size_t floats) {
+    float* p = (float*)(base + off);
+    off += align_up(floats * sizeof(float), 256);
+    return p;
+  };
+  ws.emb = take((size_t)N * D);
+  ws.seq = take((size_t)ws.rows * D);
+  ws.seq2 = take((size_t)ws.rows * D);
+  ws.ln = take((size_t)ws.rows * D);
+  ws.att = take((size_t)ws.rows * D);
+  ws.nys = base + off;
+  off += carve_nystrom(&d->attn, ws.rows, nullptr).bytes;
+  ws.bytes = off;
+  return ws;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rrt_nystrom_workspace_size(const rrt_nystrom_desc* desc, int64_t n, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_nystrom(desc, n);
+  if (rc) return rc;
+  *bytes = carve_nystrom(desc, n, nullptr).bytes;
+  return RRT_OK;
+}
+
+int rrt_nystrom_attention_f32(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w, const float* x, float* y, int64_t n,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  if (!desc || !w || !x || !y) return RRT_E_INVALID;
+  int rc = check_nystrom(desc, n);
+  if (rc) return rc;
+  if (!nystrom_weights_ok(desc, w)) return RRT_E_INVALID;
+  if (!workspace || workspace_bytes < carve_nystrom(desc, n, nullptr).bytes) return RRT_E_WORKSPACE;
+  return nystrom_forward(desc, w, x, y, n, carve_nystrom(desc, n, (char*)workspace), (hipStream_t)stream);
+}
+
+int rrt_nystrom_landmarks_f32(const float* qkv, float* ql, float* kl, int64_t n_padded, int32_t heads, void* stream) {
+  if (!qkv || !ql || !kl) return RRT_E_INVALID;
+  int rc = check_nystrom_np(n_padded);
+  if (!rc) rc = check_nystrom_heads(heads);
+  if (rc) return rc;
+  return (int)launch_nystrom_landmarks(qkv, ql, kl, (long)n_padded, heads, (hipStream_t)stream);
+}
+
+int rrt_nystrom_landmark_sim_f32(const float* ql, const float* kl, float* a2, int32_t heads, void* stream) {
+  if (!ql || !kl || !a2) return RRT_E_INVALID;
+  int rc = check_nystrom_heads(heads);
+  if (rc) return rc;
+  return (int)launch_nystrom_sim2(ql, kl, a2, heads, (hipStream_t)stream);
+}
+
+int rrt_nystrom_landmark_attn_workspace_size(int64_t n_padded, int32_t heads, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_nystrom_np(n_padded);
+  if (!rc) rc = check_nystrom_heads(heads);
+  if (rc) return rc;
+  *bytes = nystrom_lattn_floats((long)n_padded, heads) * sizeof(float);
+  return RRT_OK;
+}
+
+int rrt_nystrom_landmark_attn_f32(const float* qkv, const float* ql, float* av, int64_t n_padded, int32_t heads,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  if (!qkv || !ql || !av) return RRT_E_INVALID;
+  int rc = check_nystrom_np(n_padded);
+  if (!rc) rc = check_nystrom_heads(heads);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < nystrom_lattn_floats((long)n_padded, heads) * sizeof(float)) return RRT_E_WORKSPACE;
+  return (int)launch_nystrom_lattn(qkv, ql, av, (float*)workspace, (long)n_padded, heads, (hipStream_t)stream);
+}
+
+int rrt_nystrom_pinv_workspace_size(int32_t heads, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_nystrom_heads(heads);
+  if (rc) return rc;
+  *bytes = nystrom_pinv_floats(heads) * sizeof(float);
+  return RRT_OK;
+}
+
+int rrt_nystrom_pinv_f32(const float* a2, float* z, int32_t heads, int32_t iterations, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  if (!a2 || !z) return RRT_E_INVALID;
+  int rc = check_nystrom_heads(heads);
+  if (rc) return rc;
+  if (iterations < 1 || iterations > 16) return unsupported("nystrom: pinv_iterations must be in 1..16");
+  if (!workspace || workspace_bytes < nystrom_pinv_floats(heads) * sizeof(float)) return RRT_E_WORKSPACE;
+  return (int)launch_nystrom_pinv(a2, z, (float*)workspace, heads, iterations, (hipStream_t)stream);
+}
+
+int rrt_nystrom_zav_f32(const float* z, const float* av, float* wz, int32_t heads, void* stream) {
+  if (!z || !av || !wz) return RRT_E_INVALID;
+  int rc = check_nystrom_heads(heads);
+  if (rc) return rc;
+  return (int)launch_nystrom_zav(z, av, wz, heads, (hipStream_t)stream);
+}
+
+int rrt_nystrom_output_f32(const float* qkv, const float* kl, const float* wz, const float* conv_w, float* o, int64_t n_padded,
+                           int32_t heads, int32_t conv_k, void* stream) {
+  if (!qkv || !kl || !wz || !o) return RRT_E_INVALID;
+  int rc = check_nystrom_np(n_padded);
+  if (!rc) rc = check_nystrom_heads(heads);
+  if (rc) return rc;
+  if (conv_w && (conv_k < 1 || conv_k % 2 == 0 || conv_k > 63)) return unsupported("nystrom: residual_conv_kernel must be odd and <= 63");
+  return (int)launch_nystrom_output(qkv, kl, wz, conv_w, o, (long)n_padded, heads, conv_k, (hipStream_t)stream);
+}
+
+int rrt_ppeg_side_f32(const float* x, const float* const* w, const float* const* b, float* y, int32_t side, int32_t dim,
+                      void* stream) {
+  if (!x || !y || !w || !w[0] || !w[1] || !w[2] || side <= 0 || dim <= 0) return RRT_E_INVALID;
+  if (dim % 4) return unsupported("ppeg: dim must be a multiple of 4");
+  if (side > 1000) return unsupported("ppeg: side above 1000");
+  const float* nob[3] = {nullptr, nullptr, nullptr};
+  hipStream_t st = (hipStream_t)stream;
+  RRT_TRY(hipMemcpyAsync(y, x, (size_t)dim * sizeof(float), hipMemcpyDeviceToDevice, st));
+  return (int)launch_ppeg_side(x + dim, w, b ? b : nob, y + dim, side, dim, st);
+}
+
+int rrt_transmil_workspace_size(const rrt_transmil_desc* desc, int64_t n_tokens, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_transmil(desc, n_tokens);
+  if (rc) return rc;
+  *bytes = carve_transmil(desc, n_tokens, nullptr).bytes;
+  return RRT_OK;
+}
+
+int rrt_transmil_forward_f32(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, const float* x, float* logits,
+                             float* feat, int64_t n_tokens, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!desc || !w || !x || !logits) return RRT_E_INVALID;
+  int rc = check_transmil(desc, n_tokens);
+  if (rc) return rc;
+  if (!w->fc1_w || !w->cls_token || !w->norm_w || !w->norm_b || !w->fc2_w || !w->pos_w[0] || !w->pos_w[1] || !w->pos_w[2])
+    return RRT_E_INVALID;
+  for (int i = 0; i < 2; ++i)
+    if (!w->layer[i].norm_w || !w->layer[i].norm_b || !nystrom_weights_ok(&desc->attn, &w->layer[i].attn)) return RRT_E_INVALID;
+  if (!workspace || workspace_bytes < carve_transmil(desc, n_tokens, nullptr).bytes) return RRT_E_WORKSPACE;
+  const TransmilWs ws = carve_transmil(desc, n_tokens, (char*)workspace);
+  const NystromWs nws = carve_nystrom(&desc->attn, ws.rows, ws.nys);
+  hipStream_t st = (hipStream_t)stream;
+  const int D = desc->attn.dim, R = (int)ws.rows;
+  LinearEpilogue ep{};
+  ep.bias = w->fc1_b;
+  ep.act = desc->act;
+  RRT_TRY(launch_linear(x, w->fc1_w, ws.emb, (int)n_tokens, D, desc->input_dim, ep, st));
+  RRT_TRY(launch_transmil_assemble(ws.emb, w->cls_token, ws.seq, (int)n_tokens, R, D, st));
+  // layer 1: seq += Nystrom(LN(seq))
+  RRT_TRY(launch_layernorm(ws.seq, nullptr, w->layer[0].norm_w, w->layer[0].norm_b, ws.ln, R, D, st));
+  rc = nystrom_forward(&desc->attn, &w->layer[0].attn, ws.ln, ws.att, ws.rows, nws, st);
+  if (rc) return rc;
+  RRT_TRY(launch_add_cols(ws.seq, ws.att, (size_t)R, D, D, st));
+  // PPEG: row 0 passes through
+  RRT_TRY(hipMemcpyAsync(ws.seq2, ws.seq, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  RRT_TRY(launch_ppeg_side(ws.seq + D, w->pos_w, w->pos_b, ws.seq2 + D, ws.side, D, st));
+  // layer 2
+  RRT_TRY(launch_layernorm(ws.seq2, nullptr, w->layer[1].norm_w, w->layer[1].norm_b, ws.ln, R, D, st));
+  rc = nystrom_forward(&desc->attn, &w->layer[1].attn, ws.ln, ws.att, ws.rows, nws, st);
+  if (rc) return rc;
+  RRT_TRY(launch_add_cols(ws.seq2, ws.att, (size_t)R, D, D, st));
+  if (feat) RRT_TRY(hipMemcpyAsync(feat, ws.seq2, (size_t)R * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  // the head reads row 0 only
+  RRT_TRY(launch_layernorm(ws.seq2, nullptr, w->norm_w, w->norm_b, ws.ln, 1, D, st));
+  RRT_TRY(launch_transmil_head(ws.ln, w->fc2_w, w->fc2_b, logits, D, desc->n_classes, st));
+  return RRT_OK;
+}
+
+}  // extern "C"

@@ -350,3 +350,23 @@ hipError_t launch_peg(const float* x, const float* const* w, const float* const*
 size_t peg_bwd_workspace(int N, int C, int k, int ppeg);
 hipError_t launch_peg_backward(const float* x, const float* dy, const float* const* w, float* dx, float* const* dw,
                                float* const* db, int N, int C, int k, int conv_1d, int ppeg, void* ws, hipStream_t st);
+
+// ---- Nystrom attention and the TransMIL baseline around it (nystrom.hip; modules/nystrom_attention.py, transmil.py), inference.
+// qkv [np, 3 * heads * 64] (q scaled, the first np - n rows zero), np a multiple of 256; ql / kl / av / wz [heads, 256, 64];
+// a2 / z [heads, 256, 256]; o [np, heads * 64]
+void nystrom_chunks(long np, int* nsub, int* sub_per_chunk, int* nch);
+size_t nystrom_lattn_floats(long np, int heads);
+size_t nystrom_pinv_floats(int heads);
+hipError_t launch_nystrom_landmarks(const float* qkv, float* ql, float* kl, long np, int heads, hipStream_t st);
+hipError_t launch_nystrom_sim2(const float* ql, const float* kl, float* a2, int heads, hipStream_t st);
+hipError_t launch_nystrom_lattn(const float* qkv, const float* ql, float* av, float* ws, long np, int heads, hipStream_t st);
+hipError_t launch_nystrom_pinv(const float* a2, float* z, float* ws, int heads, int iters, hipStream_t st);
+hipError_t launch_nystrom_zav(const float* z, const float* av, float* wz, int heads, hipStream_t st);
+hipError_t launch_nystrom_output(const float* qkv, const float* kl, const float* wz, const float* conv_w, float* o, long np,
+                                 int heads, int ks, hipStream_t st);
+hipError_t launch_transmil_assemble(const float* h, const float* cls, float* seq, int N, int rows, int dim, hipStream_t st);
+hipError_t launch_transmil_head(const float* x, const float* w, const float* b, float* logits, int dim, int n_classes,
+                                hipStream_t st);
+// PPEG (k = 7, 5, 3) on a side x side grid stated by the caller: x, y [side * side, C] (peg.hip)
+hipError_t launch_ppeg_side(const float* x, const float* const* w, const float* const* b, float* y, int side, int C,
+                            hipStream_t st);

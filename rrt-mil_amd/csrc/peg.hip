@@ -111,9 +111,11 @@ constexpr size_t PEG_LDS_MAX = 160 * 1024;
 
 // w[0..2], b[0..2]: proj (k), proj1 (5), proj2 (3); PEG: only [0].  k odd <= 11.
 static hipError_t launch_peg_impl(const float* x, const float* const* w, const float* const* b, float* y, int N, int C,
-                                  int k, int conv_1d, int ppeg, int bwd, hipStream_t st) {
+                                  int k, int conv_1d, int ppeg, int bwd, hipStream_t st, int side = 0) {
+  // side > 0: the grid is exactly side x side (N = side * side, nothing wrapped, no lift to 7 x 7)
   int H0, H;
-  peg_sides(N, ppeg, &H0, &H);
+  if (side > 0) H0 = H = side;
+  else peg_sides(N, ppeg, &H0, &H);
   const int KK = ppeg ? (k > 5 ? k : 5) : k;
   const int tiles = ((H + 7) / 8) * ((H + 7) / 8);
   dim3 grid(tiles, (C + 63) / 64), block(256);
@@ -142,6 +144,13 @@ static hipError_t launch_peg_impl(const float* x, const float* const* w, const f
 hipError_t launch_peg(const float* x, const float* const* w, const float* const* b, float* y, int N, int C, int k,
                       int conv_1d, int ppeg, hipStream_t st) {
   return launch_peg_impl(x, w, b, y, N, C, k, conv_1d, ppeg, 0, st);
+}
+
+// PPEG on a grid whose side the caller states (TransMIL's pos_layer, modules/transmil.py: k = 7 with the fixed 5 and 3):
+// x, y [side * side, C]
+hipError_t launch_ppeg_side(const float* x, const float* const* w, const float* const* b, float* y, int side, int C,
+                            hipStream_t st) {
+  return launch_peg_impl(x, w, b, y, side * side, C, 7, 0, 1, 0, st, side);
 }
 
 namespace {

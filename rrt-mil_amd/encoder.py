@@ -72,7 +72,8 @@ class RegionAttntion(nn.Module):
                  **kwargs):
         super().__init__()
         if region_attn != 'native':
-            raise NotImplementedError("region_attn='ntrans' (Nystrom ablation) is out of scope")
+            raise NotImplementedError("region_attn='ntrans' is not wired into RRTEncoder; the Nystrom attention itself is "
+                                      "rrt_mil_amd.NystromAttention (rrt_mil_amd/transmil.py)")
         self.dim, self.num_heads = dim, num_heads
         self.region_size = region_size if region_size > 0 else None
         self.region_num = region_num
@@ -157,7 +158,8 @@ class TransLayer(nn.Module):
         elif attn == 'crmsa':
             self.attn = CrossRegionAttntion(crmsa_k=crmsa_k, **common, **kwargs)
         elif attn == 'ntrans':
-            raise NotImplementedError("attn='ntrans' (Nystrom ablation) is out of scope")
+            raise NotImplementedError("attn='ntrans' is not wired into RRTEncoder; the Nystrom attention itself is "
+                                      "rrt_mil_amd.NystromAttention (rrt_mil_amd/transmil.py)")
         else:
             raise NotImplementedError
         # timm's DropPath (rrt.py:102) holds no parameters: at batch size 1 it keeps or drops a whole residual

@@ -194,3 +194,60 @@ def dsmil_head_state(shapes, tag):
             fan_in = int(np.prod(shape[1:]))
             out[key] = (normal(f"dsmil/{tag}/{key}", shape) * (gain / np.sqrt(fan_in))).astype(np.float32)
     return out
+
+
+K_ALIGN, K_NOISE = 0.33, 0.4     # nystrom_state: k rows = K_ALIGN * q rows + K_NOISE * their own draw
+
+
+def nystrom_state(dim=512, heads=8, dim_head=64, residual_conv_kernel=33, gain=1.0, residual=True, tag="nys"):
+    """Closed-form parameters of NystromAttention (modules/nystrom_attention.py:54-65): ``to_qkv.weight`` (no bias),
+    ``to_out.0.{weight, bias}``, ``res_conv.weight``.  Linear weights U(+-1/sqrt(fan_in)); ``gain`` multiplies the q and the k
+    rows of ``to_qkv`` (gain 6 on LayerNorm-ed rows peaks the three softmaxes: |logit| of a few tens); the conv taps are
+    U(+-1/sqrt(k)), far from the delta a trained filter starts near, so that every tap counts."""
+    inner = heads * dim_head
+    wq = uniform(f"{tag}/to_qkv.w", (3 * inner, dim), -1, 1) / np.sqrt(dim)
+    # the k rows lean on the q rows, as trained attention does: a token's logit with itself and its neighbours has a
+    # systematic part, so that the peak |logit| depends little on how many tokens there are to take the maximum over
+    wq[inner:2 * inner] = K_ALIGN * wq[:inner] + K_NOISE * wq[inner:2 * inner]
+    wq[:2 * inner] *= gain
+    out = {"to_qkv.weight": wq.astype(np.float32),
+           "to_out.0.weight": (uniform(f"{tag}/to_out.w", (dim, inner), -1, 1) / np.sqrt(inner)).astype(np.float32),
+           "to_out.0.bias": uniform(f"{tag}/to_out.b", (dim,), -0.05, 0.05)}
+    if residual:
+        out["res_conv.weight"] = (uniform(f"{tag}/res_conv.w", (heads, 1, residual_conv_kernel, 1), -1, 1) /
+                                  np.sqrt(residual_conv_kernel)).astype(np.float32)
+    return out
+
+
+def nystrom_input(n, dim, tag="nys"):
+    """(n, dim) rows shaped like a LayerNorm output whose neighbours are correlated (a slide's patches): a per-token N(0, 1)
+    part plus a component that varies slowly along the sequence, so that the landmark means of long sequences keep a
+    magnitude comparable to single rows."""
+    t = np.arange(n, dtype=np.float64)[:, None]
+    f = uniform(f"{tag}/in.f/{dim}", (1, dim), 0.5, 3.0, np.float64)
+    ph = uniform(f"{tag}/in.p/{dim}", (1, dim), 0.0, 2 * np.pi, np.float64)
+    slow = np.sqrt(2.0) * np.sin(2 * np.pi * f * t / max(n, 256) + ph)
+    return (0.6 * normal(f"{tag}/in/{n}x{dim}", (n, dim), np.float64) + 0.8 * slow).astype(np.float32)
+
+
+def transmil_state(input_dim=1024, n_classes=2, cls_sigma=0.5, tag="transmil"):
+    """Closed-form parameters of TransMIL (modules/transmil.py:64-88), the reference's 25 state_dict keys: ``_fc1.0``,
+    ``cls_token`` (N(0, cls_sigma^2): of visible size, so that row 0 matters), ``layer{1,2}.{norm, attn}``,
+    ``pos_layer.{proj, proj1, proj2}``, ``norm``, ``_fc2``."""
+    D = 512
+    out = {"_fc1.0.weight": (uniform(f"{tag}/fc1.w", (D, input_dim), -1, 1) / np.sqrt(input_dim)).astype(np.float32),
+           "_fc1.0.bias": uniform(f"{tag}/fc1.b", (D,), -0.05, 0.05),
+           "cls_token": (normal(f"{tag}/cls", (1, 1, D)) * cls_sigma).astype(np.float32)}
+    for name in ("layer1", "layer2"):
+        out[f"{name}.norm.weight"] = 1.0 + uniform(f"{tag}/{name}.norm.w", (D,), -0.25, 0.25)
+        out[f"{name}.norm.bias"] = uniform(f"{tag}/{name}.norm.b", (D,), -0.1, 0.1)
+        for k, v in nystrom_state(D, 8, 64, 33, tag=f"{tag}/{name}").items():
+            out[f"{name}.attn.{k}"] = v
+    for name, kk in (("proj", 7), ("proj1", 5), ("proj2", 3)):
+        out[f"pos_layer.{name}.weight"] = uniform(f"{tag}/pos.{name}.w", (D, 1, kk, kk), -1.0 / kk, 1.0 / kk)
+        out[f"pos_layer.{name}.bias"] = uniform(f"{tag}/pos.{name}.b", (D,), -0.05, 0.05)
+    out["norm.weight"] = 1.0 + uniform(f"{tag}/norm.w", (D,), -0.25, 0.25)
+    out["norm.bias"] = uniform(f"{tag}/norm.b", (D,), -0.1, 0.1)
+    out["_fc2.weight"] = (uniform(f"{tag}/fc2.w", (n_classes, D), -1, 1) / np.sqrt(D)).astype(np.float32)
+    out["_fc2.bias"] = uniform(f"{tag}/fc2.b", (n_classes,), -0.05, 0.05)
+    return {k: np.asarray(v, dtype=np.float32) for k, v in out.items()}

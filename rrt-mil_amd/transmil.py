@@ -1,0 +1,264 @@
+"""TransMIL -- the transformer baseline of the reference (modules/transmil.py:26-125) and its hot path, Nystrom attention
+(modules/nystrom_attention.py:32-149), on the MI355X kernels of csrc/nystrom.hip.
+
+Same constructor signatures, module tree and parameter names as the reference (``_fc1.0``, ``cls_token``,
+``layer{1,2}.norm``, ``layer{1,2}.attn.{to_qkv, to_out.0, res_conv}``, ``pos_layer.{proj, proj1, proj2}``, ``norm``,
+``_fc2``): reference checkpoints load with ``strict=True``.
+
+Inference only.  A bag is ONE C-ABI call (rrt_transmil_forward_f32: ``forward_bag``).  There is no backward: a call that
+needs a graph, or ``train()`` with dropout, raises ``NotImplementedError`` -- use ``eval()`` under ``torch.no_grad()``.
+The arithmetic is exact fp32 on the fp32 matrix cores in every context: under ``torch.autocast`` the modules STILL compute
+in fp32 (there is no 16-bit path for the pseudo-inverse iteration, whose conditioning does not survive 8 mantissa bits).
+"""
+import ctypes as C
+
+import torch
+from torch import nn
+
+from . import _lib
+
+
+def initialize_weights(module):
+    """modules/transmil.py:6-24"""
+    for m in module.modules():
+        if isinstance(m, (nn.Conv2d, nn.Linear)):
+            nn.init.xavier_normal_(m.weight)
+            if m.bias is not None:
+                m.bias.data.zero_()
+        elif isinstance(m, nn.LayerNorm):
+            nn.init.constant_(m.bias, 0)
+            nn.init.constant_(m.weight, 1.0)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _param(t):
+    """the parameter's own fp32 storage (no copy when it is already contiguous fp32)"""
+    return t.detach().float().contiguous()
+
+
+def _no_cpu(t, who):
+    if not t.is_cuda:
+        raise _lib.RRTHipError(f"rrt_mil_amd.{who} runs on MI355X only: move the input to a 'cuda' (HIP) device; there is no "
+                               "CPU fallback")
+
+
+def _no_graph(module, x, who):
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters())):
+        raise NotImplementedError(f"rrt_mil_amd.{who} has no backward: call it in eval() under torch.no_grad()")
+
+
+class NystromAttention(nn.Module):
+    """modules/nystrom_attention.py:32-149.  ``forward(x)`` with x (1, n, dim) -> (1, n, dim); ``mask=`` and
+    ``return_attn=True`` are not implemented (the reference's mask branch names undefined variables, and TransMIL passes
+    neither).  The HIP path supports dim_head = 64, num_landmarks = 256, heads <= 16, pinv_iterations <= 16, an odd
+    residual_conv_kernel <= 63 and dim a multiple of 32 up to 1024; anything else raises NotImplementedError at the call."""
+
+    def __init__(self, dim, dim_head=64, heads=8, num_landmarks=256, pinv_iterations=6, residual=True,
+                 residual_conv_kernel=33, eps=1e-8, dropout=0.):
+        super().__init__()
+        self.eps = eps
+        inner_dim = heads * dim_head
+        self.num_landmarks = num_landmarks
+        self.pinv_iterations = pinv_iterations
+        self.heads = heads
+        self.dim, self.dim_head = dim, dim_head
+        self.scale = dim_head ** -0.5
+        self.to_qkv = nn.Linear(dim, inner_dim * 3, bias=False)
+        self.to_out = nn.Sequential(nn.Linear(inner_dim, dim), nn.Dropout(dropout))
+        self.residual = residual
+        self.residual_conv_kernel = residual_conv_kernel
+        if residual:
+            self.res_conv = nn.Conv2d(heads, heads, (residual_conv_kernel, 1), padding=(residual_conv_kernel // 2, 0),
+                                      groups=heads, bias=False)
+        self._dropout = dropout
+        self._ws = None
+
+    def __getstate__(self):          # the device workspace stays with the process (deepcopy / pickle)
+        st = dict(self.__dict__)
+        st.pop("_ws", None)
+        return st
+
+    def __setstate__(self, st):
+        self.__dict__.update(st)
+        self.__dict__.setdefault("_ws", None)
+
+    def _desc(self):
+        d = _lib.NystromDesc()
+        d.dim, d.heads, d.dim_head, d.num_landmarks = self.dim, self.heads, self.dim_head, self.num_landmarks
+        d.pinv_iterations, d.residual, d.residual_conv_kernel = self.pinv_iterations, int(bool(self.residual)), \
+            self.residual_conv_kernel
+        return d
+
+    def _weights(self, keep):
+        """(NystromWeights, ...); the fp32 tensors the pointers refer to are appended to ``keep``"""
+        w = _lib.NystromWeights()
+        ts = [_param(self.to_qkv.weight), _param(self.to_out[0].weight), _param(self.to_out[0].bias),
+              _param(self.res_conv.weight) if self.residual else None]
+        keep.extend(ts)
+        w.qkv_w, w.out_w, w.out_b, w.conv_w = (_ptr(t) for t in ts)
+        return w
+
+    def forward(self, x, mask=None, return_attn=False):
+        if mask is not None:
+            raise NotImplementedError("rrt_mil_amd.NystromAttention: mask= is not implemented (the reference's mask branch "
+                                      "names undefined variables)")
+        if return_attn:
+            raise NotImplementedError("rrt_mil_amd.NystromAttention: return_attn=True is not implemented")
+        _no_cpu(x, "NystromAttention")
+        if self.training and self._dropout > 0.:
+            raise NotImplementedError("rrt_mil_amd.NystromAttention in train() with dropout: inference only, call eval() "
+                                      "under torch.no_grad()")
+        _no_graph(self, x, "NystromAttention")
+        if x.dim() != 3 or x.shape[0] != 1:
+            raise ValueError(f"NystromAttention expects (1, n, dim) -- batch > 1 is not supported -- got {tuple(x.shape)}")
+        if x.shape[2] != self.dim:
+            raise ValueError(f"expected feature dim {self.dim}, got {x.shape[2]}")
+        lib = _lib.load()
+        x2d = x[0].float().contiguous()
+        n, dev = x2d.shape[0], x2d.device
+        d, keep = self._desc(), []
+        w = self._weights(keep)
+        need = C.c_size_t()
+        _lib.check(lib.rrt_nystrom_workspace_size(C.byref(d), n, C.byref(need)), "rrt_nystrom_workspace_size")
+        if self._ws is None or self._ws.device != dev or self._ws.numel() < need.value:
+            self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        y = torch.empty((n, self.dim), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.rrt_nystrom_attention_f32(C.byref(d), C.byref(w), x2d.data_ptr(), y.data_ptr(), n,
+                                                     self._ws.data_ptr(), self._ws.numel(), st), "rrt_nystrom_attention_f32")
+        return y.unsqueeze(0)
+
+
+class _NystromLayer(nn.Module):
+    """modules/transmil.py:26-44 (its TransLayer): x + attn(norm(x)).  Parameter holder; TransMIL's forward is one call."""
+
+    def __init__(self, norm_layer=nn.LayerNorm, dim=512):
+        super().__init__()
+        self.norm = norm_layer(dim)
+        self.attn = NystromAttention(dim=dim, dim_head=dim // 8, heads=8, num_landmarks=dim // 2, pinv_iterations=6,
+                                     residual=True, dropout=0.1)
+
+
+class PPEG(nn.Module):
+    """modules/transmil.py:47-61.  Parameter holder (three depth-wise convs); TransMIL's forward is one call."""
+
+    def __init__(self, dim=512):
+        super().__init__()
+        self.proj = nn.Conv2d(dim, dim, 7, 1, 7 // 2, groups=dim)
+        self.proj1 = nn.Conv2d(dim, dim, 5, 1, 5 // 2, groups=dim)
+        self.proj2 = nn.Conv2d(dim, dim, 3, 1, 3 // 2, groups=dim)
+
+
+class TransMIL(nn.Module):
+    """modules/transmil.py:64-125.  ``model(x)`` with x (1, N, input_dim) or (N, input_dim) -> logits (1, n_classes)."""
+
+    def __init__(self, input_dim, n_classes, dropout, act):
+        super().__init__()
+        self.pos_layer = PPEG(dim=512)
+        fc1 = [nn.Linear(input_dim, 512)]
+        if act.lower() == 'relu':
+            fc1 += [nn.ReLU()]
+        elif act.lower() == 'gelu':
+            fc1 += [nn.GELU()]
+        if dropout:
+            fc1 += [nn.Dropout(0.25)]
+        self._fc1 = nn.Sequential(*fc1)
+        self.cls_token = nn.Parameter(torch.randn(1, 1, 512))
+        nn.init.normal_(self.cls_token, std=1e-6)
+        self.n_classes = n_classes
+        self.layer1 = _NystromLayer(dim=512)
+        self.layer2 = _NystromLayer(dim=512)
+        self.norm = nn.LayerNorm(512)
+        self._fc2 = nn.Linear(512, self.n_classes)
+        self.apply(initialize_weights)
+        self._act = {"relu": _lib.ACT_RELU, "gelu": _lib.ACT_GELU}.get(act.lower(), _lib.ACT_NONE)
+        self._ws = None
+
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        st.pop("_ws", None)
+        return st
+
+    def __setstate__(self, st):
+        self.__dict__.update(st)
+        self.__dict__.setdefault("_ws", None)
+
+    def _desc_weights(self, keep):
+        d, w = _lib.TransmilDesc(), _lib.TransmilWeights()
+        d.input_dim, d.n_classes, d.act = self._fc1[0].in_features, self.n_classes, self._act
+        d.attn = self.layer1.attn._desc()
+
+        def p(t):
+            t = _param(t)
+            keep.append(t)
+            return t.data_ptr()
+
+        w.fc1_w, w.fc1_b, w.cls_token = p(self._fc1[0].weight), p(self._fc1[0].bias), p(self.cls_token)
+        for i, layer in enumerate((self.layer1, self.layer2)):
+            w.layer[i].norm_w, w.layer[i].norm_b = p(layer.norm.weight), p(layer.norm.bias)
+            w.layer[i].attn = layer.attn._weights(keep)
+        for i, conv in enumerate((self.pos_layer.proj, self.pos_layer.proj1, self.pos_layer.proj2)):
+            w.pos_w[i], w.pos_b[i] = p(conv.weight), p(conv.bias)
+        w.norm_w, w.norm_b = p(self.norm.weight), p(self.norm.bias)
+        w.fc2_w, w.fc2_b = p(self._fc2.weight), p(self._fc2.bias)
+        return d, w
+
+    def forward_bag(self, x2d, return_features=False):
+        """One bag: x2d (N, input_dim) device tensor -> logits (1, n_classes) through ONE rrt_transmil_forward_f32 call
+        (with ``return_features`` also the (1 + H*H, 512) rows before the last LayerNorm)."""
+        _no_cpu(x2d, "TransMIL")
+        if self.training and any(isinstance(m, nn.Dropout) and m.p > 0. for m in self.modules()):
+            raise NotImplementedError("rrt_mil_amd.TransMIL in train() with dropout: inference only, call eval() under "
+                                      "torch.no_grad()")
+        _no_graph(self, x2d, "TransMIL")
+        if x2d.dim() != 2:
+            raise ValueError(f"forward_bag expects (N, input_dim), got {tuple(x2d.shape)}")
+        n, in_dim = x2d.shape
+        if in_dim != self._fc1[0].in_features:
+            raise ValueError(f"expected feature dim {self._fc1[0].in_features}, got {in_dim}")
+        lib = _lib.load()
+        x2d = x2d.float().contiguous()
+        keep = []
+        d, w = self._desc_weights(keep)
+        need = C.c_size_t()
+        _lib.check(lib.rrt_transmil_workspace_size(C.byref(d), n, C.byref(need)), "rrt_transmil_workspace_size")
+        dev = x2d.device
+        if self._ws is None or self._ws.device != dev or self._ws.numel() < need.value:
+            self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        logits = torch.empty((1, self.n_classes), dtype=torch.float32, device=dev)
+        feat = None
+        if return_features:
+            side = _ceil_sqrt(n)
+            feat = torch.empty((1 + side * side, 512), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.rrt_transmil_forward_f32(C.byref(d), C.byref(w), x2d.data_ptr(), logits.data_ptr(), _ptr(feat), n,
+                                                    self._ws.data_ptr(), self._ws.numel(), st), "rrt_transmil_forward_f32")
+        return (logits, feat) if return_features else logits
+
+    def forward_bags(self, bags):
+        """A list of independent slides (each (N_i, input_dim) or (1, N_i, input_dim)) -> list of logits: a plain loop of
+        forward_bag on the caller's stream."""
+        return [self.forward(b) for b in bags]
+
+    def forward(self, x):
+        _no_cpu(x, "TransMIL")
+        if x.dim() == 3:
+            if x.shape[0] != 1:
+                raise ValueError(f"TransMIL expects one bag, (1, N, input_dim) or (N, input_dim) -- batch > 1 is not "
+                                 f"supported -- got {tuple(x.shape)}")
+            x = x[0]
+        return self.forward_bag(x)
+
+
+def _ceil_sqrt(n):
+    h = int(n ** 0.5)
+    while h * h < n:
+        h += 1
+    while h > 1 and (h - 1) * (h - 1) >= n:
+        h -= 1
+    return h

@@ -169,12 +169,23 @@ int rrt_encoder_workspace_size(const rrt_encoder_desc *desc, int64_t n_tokens, s
 #define RRT_PLAN_ATTN_HD    32  /* qkv linear + the MFMA attention forward at a head dim other than 64 (set alone; see
                                    rrt_region_attention_hd_supported) */
 int rrt_encoder_plan(const rrt_encoder_desc *desc, int64_t n_tokens, int32_t *flags);
+/* host-only: the form of the two streaming stages around the R-MSA layers (LayerNorm + partition; dispatch + final LayerNorm)
+ * in the same forward.  *w = 0: one wave per token row; 1 .. 3: the row-looping kernels on a fixed grid of w waves per SIMD
+ * (rrt_ln_partition_rows_f32, rrt_crmsa_dispatch_ln_rows_f32).  Same output bits either way. */
+int rrt_encoder_plan_rows(const rrt_encoder_desc *desc, int64_t n_tokens, int32_t *w);
 
 /* Whole path: RRTEncoder.forward, modules/rrt.py:165-202 (eval mode, one bag).
  * x [n_tokens, dim] -> y [n_tokens, dim]; x is not modified; y may not alias x. */
 int rrt_encoder_forward_f32(const rrt_encoder_desc *desc, const rrt_encoder_weights *w,
                             const float *x, float *y, int64_t n_tokens,
                             void *workspace, size_t workspace_bytes, void *stream);
+
+/* Test hook (tests/test_rows_kernels_gpu.py): the same forward with the form of its two streaming stages chosen by the caller
+ * instead of the plan -- rows_w = 0: one wave per token row, 1 .. 3: the row-looping kernels at that width (see
+ * rrt_encoder_plan_rows).  Every choice gives the same output bits. */
+int rrt_debug_encoder_forward_rows_f32(const rrt_encoder_desc *desc, const rrt_encoder_weights *w,
+                                       const float *x, float *y, int64_t n_tokens,
+                                       void *workspace, size_t workspace_bytes, void *stream, int32_t rows_w);
 
 /* Same call, recording caller-owned hipEvent_t's at stage boundaries on `stream` (for
  * measurement: bench.py times the dominant kernel with these).  events[RRT_EV_COUNT], any
@@ -226,6 +237,13 @@ int rrt_encoder_forward_batch_f32(const rrt_encoder_desc *desc, const rrt_encode
  * (rmsa.py:28-39): x [L, dim] -> u [H*H, dim] in region-major order, pad rows = 0. */
 int rrt_ln_partition_f32(const float *x, const float *gamma, const float *beta, float *u,
                          int64_t L, int32_t dim, const rrt_grid *g, void *stream);
+
+/* The same stage in its row-looping form: a fixed grid of (device CUs x w) four-wave blocks, w = 1 .. 3 waves per SIMD, each
+ * wave looping over token rows; u is bit-identical to rrt_ln_partition_f32's.  w = 0 runs the one-wave-per-row kernel.
+ * zero / n_zero (may be NULL / 0): n_zero ints set to 0 as a side job, as the encoder uses it for arrival counters. */
+int rrt_ln_partition_rows_f32(const float *x, const float *gamma, const float *beta, float *u,
+                              int64_t L, int32_t dim, const rrt_grid *g, int32_t w,
+                              int32_t *zero, int32_t n_zero, void *stream);
 
 /* nn.Linear (rmsa.py:100, :131): C[M,N] = A[M,K] . B[N,K]^T + bias[N] (bias may be NULL).
  * q_cols>0: columns [0,q_cols) are multiplied by q_scale after the bias (rmsa.py:103). */
@@ -404,6 +422,14 @@ int rrt_crmsa_dispatch_ln_f32(const float *x1, const float *x0, const float *wdi
                               const float *rep2, const float *gamma,
                               const float *beta, float *y, int64_t L, int32_t dim, int32_t k,
                               const rrt_grid *g8, void *stream);
+/* rrt_crmsa_dispatch_ln_f32 in its row-looping form (w = 1 .. 3 as rrt_ln_partition_rows_f32; w = 0: the one-wave-per-row
+ * kernel): y is bit-identical.  y16 (may be NULL): the output rows once more as 16-bit values, prec16 = RRT_COMPUTE_BF16 /
+ * RRT_COMPUTE_F16 (the slide classifier's side output).  k = 0 with wdisp = rep2 = y16 = NULL (g8 ignored): the plain
+ * LayerNorm of x1 (+ x0) that rrt_layernorm_f32 runs, in the chosen form. */
+int rrt_crmsa_dispatch_ln_rows_f32(const float *x1, const float *x0, const float *wdisp,
+                                   const float *rep2, const float *gamma,
+                                   const float *beta, float *y, int64_t L, int32_t dim, int32_t k,
+                                   const rrt_grid *g8, int32_t w, uint16_t *y16, int32_t prec16, void *stream);
 /* crmsa_mlp logits (rmsa.py:248-252, :305): logits[r, n] = sum_j tanh(hid[r, j]) * w2[n, j] */
 int rrt_crmsa_mlp_logits_f32(const float *hid, const float *w2, float *logits, int64_t rows,
                              int32_t hdim, int32_t k, void *stream);

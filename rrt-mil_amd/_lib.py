@@ -127,8 +127,11 @@ SIGNATURES = {
     "rrt_region_grid": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(Grid)]),
     "rrt_encoder_workspace_size": (C.c_int, [C.POINTER(EncoderDesc), C.c_int64, C.POINTER(C.c_size_t)]),
     "rrt_encoder_plan": (C.c_int, [C.POINTER(EncoderDesc), C.c_int64, C.POINTER(C.c_int32)]),
+    "rrt_encoder_plan_rows": (C.c_int, [C.POINTER(EncoderDesc), C.c_int64, C.POINTER(C.c_int32)]),
     "rrt_encoder_forward_f32": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderWeights), C.c_void_p,
                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_debug_encoder_forward_rows_f32": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderWeights), C.c_void_p,
+                                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32]),
     "rrt_encoder_forward_events_f32": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderWeights), C.c_void_p,
                                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p,
                                                  C.POINTER(C.c_void_p)]),
@@ -142,6 +145,8 @@ SIGNATURES = {
                                                 C.c_void_p, C.POINTER(C.c_void_p)]),
     "rrt_ln_partition_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_int32, C.POINTER(Grid), C.c_void_p]),
+    "rrt_ln_partition_rows_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                            C.c_int32, C.POINTER(Grid), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "rrt_linear_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                  C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),
     "rrt_linear_unpartition_residual_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -181,6 +186,8 @@ SIGNATURES = {
                                                          C.c_size_t, C.c_void_p]),
     "rrt_crmsa_dispatch_ln_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_int32, C.c_int32,
                                                               C.POINTER(Grid), C.c_void_p]),
+    "rrt_crmsa_dispatch_ln_rows_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_int32, C.c_int32,
+                                                                   C.POINTER(Grid), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "rrt_crmsa_mlp_logits_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "rrt_layernorm_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_void_p]),
     "rrt_peg_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int64] + [C.c_int32] * 4 + [C.c_void_p]),

@@ -225,7 +225,15 @@ struct EncoderPlan {
   CastKind casts;    // the R-MSA layers' weight images this call writes
   bool inner16;      // CR-MSA's inner MSA on the 16-bit kernels (its weight images ride with the cast launch)
   FrontKind front;   // CR-MSA's first pass: logits + combine
+  int rows_w;        // > 0: LayerNorm + partition (K1) and dispatch + final LayerNorm (K7) take their row-looping forms on a
+                     // grid of rows_w waves per SIMD (ln_partition.hip, crmsa.hip); 0: a wave per row
+  bool rows_ln1;     // ... K1 as well (the exact fp32 layers; the 16-bit modes have their own LayerNorm + partition)
 };
+
+// Waves per SIMD of the row-looping K1 / K7 (ROWS_W_MAX = 3).  Default bench (N = 9000, fp32, four bags in flight), one box,
+// five rounds alternating, medians in slides/s: a wave per row 5350 (parent commit) / 5350 (tuning build, RRT_ROWS_W=0),
+// w = 1 5431, w = 2 5410, w = 3 5389; the parent's own spread was 13 (profiles/rows_in_flight_ab.txt).
+constexpr int ROWS_W_DEFAULT = 1;
 
 // smallest CR-MSA region (tokens) that takes crmsa_stream4_kernel instead of crmsa_region4_kernel (A/B builds:
 // -DRRT_STREAM4_MIN_P=16)
@@ -247,6 +255,24 @@ EncoderPlan plan_encoder(const rrt_encoder_desc& d, const rrt_grid& g, const rrt
   // CR-MSA's inner MSA over the 64 k representatives on the same 16-bit kernels (one fused launch + one GEMM instead
   // of GEMM + attention + GEMM on fp32 data): head dim 64 only (crmsa_heads = dim / 64)
   p.inner16 = d.cr_msa && lowp && rmsa_fused16_supported(64, D, d.crmsa_heads, 0);
+  // K1 / K7 with bags in flight (exact fp32, solo = 0): the row-looping forms -- a launch that is resident at once beside
+  // another bag's fused R-MSA blocks and sends the dispatcher no further waves.  dim <= 512 and crmsa_k <= 3 only: the other
+  // instantiations need more than the 72 VGPRs two such waves have beside two fused waves of a SIMD (90 / 111 at k <= 5 / 8).
+  // One bag in flight keeps a wave per row (latency-optimal there).  The 16-bit modes keep it too (their K1 is another
+  // kernel; K7 alone in the row-looping form was measured with RRT_ROWS_LOWP: the bf16 lines of profiles/rows_in_flight_ab.txt).
+  // Tuning build: RRT_ROWS_W = 0 (a wave per row everywhere) .. 3; RRT_ROWS_LOWP: K7 of the 16-bit modes as well.
+  {
+    static const char* rows_env = rrt_tune_env("RRT_ROWS_W");
+    static const bool rows_lowp = rrt_tune_env("RRT_ROWS_LOWP") != nullptr;
+    int w = ROWS_W_DEFAULT;
+    if (rows_env != nullptr && atoi(rows_env) >= 0 && atoi(rows_env) <= ROWS_W_MAX) w = atoi(rows_env);
+    const bool exact = d.compute == RRT_COMPUTE_F32;
+    const bool fits = D <= 512 && (!d.cr_msa || d.crmsa_k <= 3);
+    if (!d.solo && fits && (exact || (rows_lowp && lowp))) {
+      p.rows_w = w;
+      p.rows_ln1 = exact && w > 0;
+    }
+  }
   if (d.n_rmsa_layers > 0) {
     const GridDev gd = to_dev(g);
     const int R = gd.rs * gd.rs, heads = d.n_heads, ek = d.epeg ? d.epeg_k : 0;
@@ -430,6 +456,18 @@ int rrt_encoder_plan(const rrt_encoder_desc* desc, int64_t n_tokens, int32_t* fl
   return RRT_OK;
 }
 
+// ... and for the two streaming stages around them (its own entry point: the flag word above is compared for equality by its
+// users, bench.py among them)
+int rrt_encoder_plan_rows(const rrt_encoder_desc* desc, int64_t n_tokens, int32_t* w) {
+  if (!w) return RRT_E_INVALID;
+  *w = 0;
+  rrt_grid g{}, g8{};
+  int rc = resolve_grids(desc, n_tokens, &g, &g8);
+  if (rc) return rc;
+  *w = plan_encoder(*desc, g, g8, false).rows_w;
+  return RRT_OK;
+}
+
 // Serialises the MFMA-bound R-MSA core (fused kernel, or qkv linear + attention) of forwards that run
 // concurrently on different streams: two of them co-running just time-slice the matrix pipes (each takes
 // twice as long), while one of them next to another bag's memory- and latency-bound kernels overlaps well.
@@ -457,7 +495,8 @@ static int ffn_apply(const rrt_encoder_desc* desc, const rrt_attn_weights& lw, c
 static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_weights* w, const float* x,
                            float* y, int64_t n_tokens, void* workspace, size_t workspace_bytes,
                            void* stream, void** events, rrt_phase_gate* gate = nullptr, float* rmsa_out = nullptr,
-                           uint16_t* y16 = nullptr, bool* y16_done = nullptr) {
+                           uint16_t* y16 = nullptr, bool* y16_done = nullptr, int rows_w_forced = -1) {
+  // rows_w_forced >= 0 (rrt_debug_encoder_forward_rows_f32): the width of the row-looping K1 / K7 instead of the plan's
   // y16 / y16_done (the slide classifier, 16-bit modes): where the forward's last kernel is CR-MSA's dispatch + LayerNorm it
   // also leaves the output rows as 16-bit values there and sets the flag
   if (y16_done) *y16_done = false;
@@ -478,7 +517,11 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
   Workspace ws = carve(*desc, N, g, g8, nullptr);
   if (!workspace || workspace_bytes < ws.bytes) return RRT_E_WORKSPACE;
   ws = carve(*desc, N, g, g8, (char*)workspace);
-  const EncoderPlan plan = plan_encoder(*desc_in, g, g8, rmsa_out != nullptr);
+  EncoderPlan plan = plan_encoder(*desc_in, g, g8, rmsa_out != nullptr);
+  if (rows_w_forced >= 0) {
+    plan.rows_w = rows_w_forced;
+    plan.rows_ln1 = rows_w_forced > 0 && desc_in->compute == RRT_COMPUTE_F32;
+  }
 
   // optional stage-boundary events (bench.py / profiling): events[i] recorded after stage i-1
   auto mark = [&](int i) -> hipError_t {
@@ -622,7 +665,7 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
       }
       case LayerKind::FusedProj: {
         // one launch per layer; its arrival counters are zeroed by LayerNorm + partition
-        RRT_TRY(launch_ln_partition(xin, lw.norm_w, lw.norm_b, ws.uo, D, gd, st, ws.proj_cnt, R));
+        RRT_TRY(launch_ln_partition(xin, lw.norm_w, lw.norm_b, ws.uo, D, gd, st, ws.proj_cnt, R, plan.rows_ln1 ? plan.rows_w : 0));
         RRT_TRY(core_begin(marks));
         FusedProj pj{};
         pj.Wp = lw.proj_w;
@@ -647,7 +690,7 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
       }
       case LayerKind::Fused: {
         // O goes to the qkv workspace (first Np*D floats), u stays in uo
-        RRT_TRY(launch_ln_partition(xin, lw.norm_w, lw.norm_b, ws.uo, D, gd, st));
+        RRT_TRY(launch_ln_partition(xin, lw.norm_w, lw.norm_b, ws.uo, D, gd, st, nullptr, 0, plan.rows_ln1 ? plan.rows_w : 0));
         RRT_TRY(core_begin(marks));
         RRT_TRY(launch_rmsa_fused(ws.uo, lw.qkv_w, lw.qkv_b, pe_w, ws.qkv, R, gd.P, D, desc->n_heads, ek, desc->compute, st));
         RRT_TRY(core_end(marks, !gate_proj));
@@ -656,7 +699,7 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
         break;
       }
       case LayerKind::Unfused: {
-        RRT_TRY(launch_ln_partition(xin, lw.norm_w, lw.norm_b, ws.uo, D, gd, st));
+        RRT_TRY(launch_ln_partition(xin, lw.norm_w, lw.norm_b, ws.uo, D, gd, st, nullptr, 0, plan.rows_ln1 ? plan.rows_w : 0));
         RRT_TRY(core_begin(marks));
         RRT_TRY(launch_linear(ws.uo, lw.qkv_w, ws.qkv, gd.Np, 3 * D, D, qkv_epilogue(lw.qkv_b, D, desc->n_heads, desc->compute), st));
         if (marks) RRT_TRY(mark(RRT_EV_QKV));
@@ -699,7 +742,7 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
   const float* x0 = desc->all_shortcut ? x : nullptr;
   if (!w->norm_w || !w->norm_b) return RRT_E_INVALID;
   if (!desc->cr_msa) {
-    RRT_TRY(launch_layernorm(xin, x0, w->norm_w, w->norm_b, y, (int)N, D, st));
+    RRT_TRY(launch_layernorm(xin, x0, w->norm_w, w->norm_b, y, (int)N, D, st, plan.rows_w));
     RRT_TRY(mark(RRT_EV_END));
     return RRT_OK;
   }
@@ -783,16 +826,16 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
   if (desc->ffn) {
     // x2 = x1 + dispatch (no LayerNorm yet) -> FFN -> (+ shortcut) -> final LayerNorm.  xin is xb or the
     // caller's x: xa is free for x2, and xin is dead once the dispatch has read it.
-    RRT_TRY(launch_crmsa_dispatch_ln(xin, nullptr, ws.wdisp, ws.rep2, nullptr, nullptr, ws.xa, D, k, gd8, st));
+    RRT_TRY(launch_crmsa_dispatch_ln(xin, nullptr, ws.wdisp, ws.rep2, nullptr, nullptr, ws.xa, D, k, gd8, st, nullptr, 0, plan.rows_w));
     rc = ffn_block(cw, ws.xa, ws.xb);
     if (rc) return rc;
-    RRT_TRY(launch_layernorm(ws.xb, x0, w->norm_w, w->norm_b, y, (int)N, D, st));
+    RRT_TRY(launch_layernorm(ws.xb, x0, w->norm_w, w->norm_b, y, (int)N, D, st, plan.rows_w));
     RRT_TRY(mark(RRT_EV_END));
     return RRT_OK;
   }
   const bool want16 = y16 != nullptr && (desc->compute == RRT_COMPUTE_BF16 || desc->compute == RRT_COMPUTE_F16) && D % 4 == 0;
   RRT_TRY(launch_crmsa_dispatch_ln(xin, x0, ws.wdisp, ws.rep2, w->norm_w, w->norm_b, y, D, k,
-                                   gd8, st, want16 ? y16 : nullptr, want16 ? desc->compute : 0));
+                                   gd8, st, want16 ? y16 : nullptr, want16 ? desc->compute : 0, plan.rows_w));
   if (want16 && y16_done) *y16_done = true;
   RRT_TRY(mark(RRT_EV_END));
   return RRT_OK;
@@ -802,6 +845,13 @@ int rrt_encoder_forward_f32(const rrt_encoder_desc* desc, const rrt_encoder_weig
                             float* y, int64_t n_tokens, void* workspace, size_t workspace_bytes,
                             void* stream) {
   return encoder_forward(desc, w, x, y, n_tokens, workspace, workspace_bytes, stream, nullptr);
+}
+
+int rrt_debug_encoder_forward_rows_f32(const rrt_encoder_desc* desc, const rrt_encoder_weights* w, const float* x, float* y,
+                                       int64_t n_tokens, void* workspace, size_t workspace_bytes, void* stream, int32_t rows_w) {
+  if (rows_w < 0 || rows_w > ROWS_W_MAX) return RRT_E_INVALID;
+  return encoder_forward(desc, w, x, y, n_tokens, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, nullptr,
+                         rows_w);
 }
 
 int rrt_phase_gate_create(rrt_phase_gate** out) {
@@ -981,6 +1031,14 @@ int rrt_ln_partition_f32(const float* x, const float* gamma, const float* beta, 
   if (!x || !gamma || !beta || !u || !g || L != g->L || dim <= 0 || dim % 4) return RRT_E_INVALID;
   if (dim > 2048) return unsupported("dim > 2048");
   return (int)launch_ln_partition(x, gamma, beta, u, dim, to_dev(*g), (hipStream_t)stream);
+}
+
+int rrt_ln_partition_rows_f32(const float* x, const float* gamma, const float* beta, float* u, int64_t L,
+                              int32_t dim, const rrt_grid* g, int32_t w, int32_t* zero, int32_t n_zero, void* stream) {
+  if (!x || !gamma || !beta || !u || !g || L != g->L || dim <= 0 || dim % 4) return RRT_E_INVALID;
+  if (w < 0 || w > ROWS_W_MAX || n_zero < 0 || (n_zero > 0 && !zero)) return RRT_E_INVALID;
+  if (dim > 2048) return unsupported("dim > 2048");
+  return (int)launch_ln_partition(x, gamma, beta, u, dim, to_dev(*g), (hipStream_t)stream, n_zero > 0 ? zero : nullptr, n_zero, w);
 }
 
 int rrt_linear_f32(const float* A, const float* B, const float* bias, float* C, int64_t M, int32_t N,
@@ -1290,6 +1348,22 @@ int rrt_crmsa_dispatch_ln_f32(const float* x1, const float* x0, const float* wdi
   if (k <= 0 || k > RRT_MAX_CRMSA_K || dim % 4 || dim > 2048) return unsupported("crmsa: k in [1,8], dim%4==0, dim<=2048");
   return (int)launch_crmsa_dispatch_ln(x1, x0, wdisp, rep2, gamma, beta, y, dim, k, to_dev(*g8),
                                        (hipStream_t)stream);
+}
+
+int rrt_crmsa_dispatch_ln_rows_f32(const float* x1, const float* x0, const float* wdisp, const float* rep2, const float* gamma,
+                                   const float* beta, float* y, int64_t L, int32_t dim, int32_t k, const rrt_grid* g8, int32_t w,
+                                   uint16_t* y16, int32_t prec16, void* stream) {
+  if (!x1 || !gamma || !beta || !y || L <= 0 || L > INT32_MAX || dim <= 0 || w < 0 || w > ROWS_W_MAX) return RRT_E_INVALID;
+  if (dim % 4 || dim > 2048) return unsupported("dim % 4 == 0, dim <= 2048");
+  if (y16 != nullptr && prec16 != RRT_COMPUTE_BF16 && prec16 != RRT_COMPUTE_F16) return RRT_E_INVALID;
+  if (k == 0) {      // plain LayerNorm of x1 (+ x0): what rrt_layernorm_f32 runs
+    if (wdisp || rep2 || y16) return RRT_E_INVALID;
+    return (int)launch_layernorm(x1, x0, gamma, beta, y, (int)L, dim, (hipStream_t)stream, w);
+  }
+  if (!wdisp || !rep2 || !g8 || L != g8->L) return RRT_E_INVALID;
+  if (k < 0 || k > RRT_MAX_CRMSA_K) return unsupported("crmsa: k in [1,8]");
+  return (int)launch_crmsa_dispatch_ln(x1, x0, wdisp, rep2, gamma, beta, y, dim, k, to_dev(*g8), (hipStream_t)stream, y16,
+                                       y16 ? prec16 : 0, w);
 }
 
 int rrt_crmsa_mlp_logits_f32(const float* hid, const float* w2, float* logits, int64_t rows, int32_t hdim,

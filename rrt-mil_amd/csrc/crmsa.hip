@@ -17,6 +17,7 @@
 //                            statistics from Lg, the per-token dispatch weights M*Dk [Np8, k],
 //                            then the weighted row sum over the region's P tokens.
 //   crmsa_dispatch_ln_kernel: 2 tokens / wave.  k-term axpy + residual (+shortcut) + LayerNorm.
+//   crmsa_dispatch_ln_rows_kernel: the same on a fixed grid whose waves loop over the tokens (bags in flight).
 #include "internal.h"
 
 namespace {
@@ -2160,6 +2161,218 @@ __global__ __launch_bounds__(256) void crmsa_dispatch_ln_kernel(
   }
 }
 
+// ---- row-looping form of crmsa_dispatch_ln_kernel (bags in flight; the scheme and its reasons: ln_partition_rows_kernel)
+// A fixed grid of device CUs x w four-wave blocks; wave gw takes the tokens gw, gw + W, ...  gamma / beta are fetched once per
+// wave, ahead of the rows.  A trip requests this token's shortcut row, dispatch weights and KB representative rows, behind
+// them the NEXT token's row of x1 (the HBM stream; loads return in order, so the waits for this token's data leave it in
+// flight: s_waitcnt vmcnt(2) at the last use in the disassembly), and only then reduces this token: the arithmetic of a row is
+// crmsa_dispatch_ln_kernel's, statement by statement (same summation order, same reduction helper): y and y16 are
+// bit-identical.  The next row's request is unconditional (a token past the end re-reads the last one and is dropped).  The
+// non-temporal hints on x1 and y stay.  Only x1 is requested a row ahead: a second row of shortcut and weights in registers puts
+// the k <= 3 form at 82 VGPRs, over the 72 that leave room for two such waves beside two fused R-MSA waves of a SIMD.
+// Resources (gfx950, kernel-resource-usage; VGPRs / SGPRs, no LDS, no scratch): <2, true, true, 3> 70 / 81 (the one-wave-per-row
+// kernel: 52 / 37), <2, true, true, 5> 90 / 94, <2, true, true, 8> 111 / 106, <2, false, true> (plain LayerNorm) 53 / 45.  The
+// budget is 72 VGPRs -- two such waves beside two fused R-MSA waves (2 x 184) of a SIMD: the k <= 3 and LayerNorm forms fit,
+// k <= 5 / 8 do not, and plan_encoder keeps crmsa_k > 3 on the one-wave-per-row kernel.
+
+// A stream's base pointer, made opaque (in SGPRs) once per token: left to itself the compiler hoists (base + lane offset) of
+// every stream out of the row loop as a 64-bit per-lane pointer -- two VGPRs each for x1, x0, rep2, y and y16 -- where
+// (scalar row base + 32-bit lane offset) costs none.  The opaque value no longer says "global memory", so the row accesses
+// below say it themselves (a generic pointer would make them flat_load / flat_store).
+template <typename T>
+__device__ __forceinline__ T* rows_base(T* p) {
+  asm volatile("" : "+s"(p));
+  return p;
+}
+typedef __attribute__((address_space(1))) f32x4 rows_gvec;
+typedef unsigned rows_u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) rows_u32x2 rows_gu2;
+template <bool NT> __device__ __forceinline__ float4 rows_ld(const float* p) {
+  const rows_gvec* gp = (const rows_gvec*)p;
+  f32x4 v;
+  if constexpr (NT) v = __builtin_nontemporal_load(gp); else v = *gp;
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+template <bool NT> __device__ __forceinline__ void rows_st(float* p, const float4 v) {
+  const f32x4 w = {v.x, v.y, v.z, v.w};
+  rows_gvec* gp = (rows_gvec*)p;
+  if constexpr (NT) __builtin_nontemporal_store(w, gp); else *gp = w;
+}
+template <int NV, bool FULL>
+__device__ __forceinline__ void dispatch_rows_request(const float* __restrict__ x1, int t, int dim, int lane, float4 (&r)[NV]) {
+  const float* src = rows_base(x1) + (size_t)t * dim;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    int c = (v * 64 + lane) * 4;
+    r[v] = (FULL || c < dim) ? rows_ld<NT_DISPATCH>(src + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// one token t whose row of x1 is in r (requested a trip ago): the rest of its requests, behind them (they are waited for
+// first, and the loads come back in order) the request of row t_next of x1 into r_next, then residual + dispatch + LayerNorm
+template <int NV, bool CRMSA, bool FULL, int KB>
+__device__ __forceinline__ void dispatch_rows_token(float4 (&r)[NV], float4 (&r_next)[NV], int t_next,
+                                                    const float4 (&gm)[NV], const float4 (&bt)[NV], int t,
+                                                    const float* __restrict__ x1, const float* __restrict__ x0,
+                                                    const float* __restrict__ wdisp, const float* __restrict__ rep2, const float* gamma, float* __restrict__ y,
+                                                    int dim, int k, int lane, float inv_d, const GridDev& g,
+                                                    uint16_t* __restrict__ y16, int prec16) {
+  constexpr int KQ = KB > 0 ? KB : 1;
+  const int R = g.Rt;
+  {
+    float4 s[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) s[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (x0) {
+      const float* sp = rows_base(x0) + (size_t)t * dim;
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        int c = (v * 64 + lane) * 4;
+        if (FULL || c < dim) s[v] = rows_ld<false>(sp + c);
+      }
+    }
+    float w[KQ];
+    float4 q[KQ][NV];
+    if constexpr (CRMSA && KB > 0) {
+      // this token's dispatch weights and representative rows (n >= k: fetched clamped, weighted 0)
+      // (t is wave-uniform, and so are slot and region -- said out loud, or the float reciprocals of the index maps leave
+      // them in VGPRs and every representative row is addressed through a 64-bit per-lane pointer)
+      const int slot = __builtin_amdgcn_readfirstlane(token_to_slot(t, g));
+      const int reg = __builtin_amdgcn_readfirstlane(fdiv(slot, g.P, g.inv_P));
+      const float* wd = wdisp + (size_t)slot * k;
+      const float* const rep2u = rows_base(rep2);
+#pragma unroll
+      for (int n = 0; n < KB; ++n) w[n] = wd[n < k ? n : k - 1];
+#pragma unroll
+      for (int n = 0; n < KB; ++n) {
+        const int nn = n < k ? n : k - 1;
+        const float* rp = rep2u + ((size_t)nn * R + reg) * dim;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+          const int c = (v * 64 + lane) * 4;
+          q[n][v] = (FULL || c < dim) ? rows_ld<false>(rp + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+      }
+    }
+    dispatch_rows_request<NV, FULL>(x1, t_next, dim, lane, r_next);
+    // every request is out before the first use waits: the empty asm pins the loads above it when the instructions are
+    // selected (nothing else orders a load against the scheduling barrier), the barrier pins them in the scheduler
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    if (x0) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        int c = (v * 64 + lane) * 4;
+        if (FULL || c < dim) { r[v].x += s[v].x; r[v].y += s[v].y; r[v].z += s[v].z; r[v].w += s[v].w; }
+      }
+    }
+    if constexpr (CRMSA && KB > 0) {
+#pragma unroll
+      for (int n = 0; n < KB; ++n) {
+        const float wv = n < k ? w[n] : 0.f;            // branch-free; same summation order as the loop form
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+          r[v].x += wv * q[n][v].x; r[v].y += wv * q[n][v].y; r[v].z += wv * q[n][v].z; r[v].w += wv * q[n][v].w;
+        }
+      }
+    } else if constexpr (CRMSA) {
+      const int slot = token_to_slot(t, g);
+      const int rg = fdiv(slot, g.P, g.inv_P);
+      const float* wd = wdisp + (size_t)slot * k;
+#pragma unroll
+      for (int n = 0; n < KMAX; ++n)
+        if (n < k) {
+          const float wv = wd[n];
+          const float* rp = rep2 + ((size_t)n * R + rg) * dim;
+#pragma unroll
+          for (int v = 0; v < NV; ++v) {
+            int c = (v * 64 + lane) * 4;
+            if (FULL || c < dim) {
+              const float4 qq = *(const float4*)(rp + c);
+              r[v].x += wv * qq.x; r[v].y += wv * qq.y; r[v].z += wv * qq.z; r[v].w += wv * qq.w;
+            }
+          }
+        }
+    }
+    float* const yr = rows_base(y) + (size_t)t * dim;
+    uint16_t* const yr16 = rows_base(y16) + (size_t)t * dim;       // (not formed into an access when y16 is null)
+    if (gamma == nullptr) {              // no LayerNorm: an FFN follows (ffn = 1), rows go out as they are
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        int c = (v * 64 + lane) * 4;
+        if (FULL || c < dim) rows_st<false>(yr + c, r[v]);
+      }
+    } else {
+      float sum = 0.f;
+#pragma unroll
+      for (int v = 0; v < NV; ++v) sum += (r[v].x + r[v].y) + (r[v].z + r[v].w);
+      const float mean = wave_sum(sum) * inv_d;
+      float sq = 0.f;
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        int c = (v * 64 + lane) * 4;
+        if (FULL || c < dim) {
+          float a = r[v].x - mean, b = r[v].y - mean, cc = r[v].z - mean, d = r[v].w - mean;
+          sq += (a * a + b * b) + (cc * cc + d * d);
+        }
+      }
+      const float rstd = 1.0f / sqrtf(wave_sum(sq) * inv_d + LN_EPS);
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        int c = (v * 64 + lane) * 4;
+        if (FULL || c < dim) {
+          float4 o;
+          o.x = (r[v].x - mean) * rstd * gm[v].x + bt[v].x;
+          o.y = (r[v].y - mean) * rstd * gm[v].y + bt[v].y;
+          o.z = (r[v].z - mean) * rstd * gm[v].z + bt[v].z;
+          o.w = (r[v].w - mean) * rstd * gm[v].w + bt[v].w;
+          rows_st<NT_DISPATCH>(yr + c, o);
+          if (y16 != nullptr)
+          {
+            const uint2 h = prec16 == 2 ? r4_pack4<2>(o) : r4_pack4<1>(o);
+            const rows_u32x2 hv = {h.x, h.y};
+            *(rows_gu2*)(yr16 + c) = hv;
+          }
+        }
+      }
+    }
+  }
+}
+
+template <int NV, bool CRMSA, bool FULL, int KB = 0>
+__global__ __launch_bounds__(256) void crmsa_dispatch_ln_rows_kernel(
+    const float* __restrict__ x1, const float* __restrict__ x0, const float* __restrict__ wdisp,
+    const float* __restrict__ rep2, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float* __restrict__ y, int L, int dim, int k, GridDev g,
+    uint16_t* __restrict__ y16, int prec16) {
+  const int lane = threadIdx.x & 63;
+  const int W = gridDim.x * 4;
+  int t = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));   // wave-uniform: scalar index math
+  if (t >= L) return;
+  const int last = L - 1;
+  float4 gm[NV], bt[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const int c = (v * 64 + lane) * 4;
+    gm[v] = (gamma != nullptr && (FULL || c < dim)) ? *(const float4*)(gamma + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    bt[v] = (gamma != nullptr && (FULL || c < dim)) ? *(const float4*)(beta + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const float inv_d = 1.0f / (float)dim;
+  // two row buffers taking turns (a copy "row = next row" would wait for the request it was meant to leave in flight)
+  float4 ra[NV], rb[NV];
+  dispatch_rows_request<NV, FULL>(x1, t, dim, lane, ra);
+  for (;;) {
+    const int tn = t + W;
+    dispatch_rows_token<NV, CRMSA, FULL, KB>(ra, rb, tn < L ? tn : last, gm, bt, t, x1, x0, wdisp, rep2, gamma, y, dim, k, lane,
+                                             inv_d, g, y16, prec16);
+    if (tn >= L) break;
+    t = tn + W;
+    dispatch_rows_token<NV, CRMSA, FULL, KB>(rb, ra, t < L ? t : last, gm, bt, tn, x1, x0, wdisp, rep2, gamma, y, dim, k, lane,
+                                             inv_d, g, y16, prec16);
+    if (t >= L) break;
+  }
+}
+
 // crmsa_mlp logits (rmsa.py:248-252, :305): logits[row][n] = sum_j tanh(hid[row][j]) * W2[n][j].
 // One wave per row of hid [rows, hdim]; zero pad rows give zero logits by themselves.
 __global__ __launch_bounds__(256) void crmsa_mlp_logits_kernel(const float* __restrict__ hid,
@@ -2194,7 +2407,33 @@ constexpr bool DISPATCH_KB5 = true;
 template <bool CRMSA>
 hipError_t launch_dispatch(const float* x1, const float* x0, const float* wdisp,
                            const float* rep2, const float* gamma, const float* beta, float* y, int L,
-                           int dim, int k, const GridDev& g, hipStream_t st, uint16_t* y16 = nullptr, int prec16 = 0) {
+                           int dim, int k, const GridDev& g, hipStream_t st, uint16_t* y16 = nullptr, int prec16 = 0,
+                           int rows_w = 0) {
+  if (rows_w > 0) {      // the row-looping form: the same choice of instantiation on a fixed grid
+    if (rows_w > ROWS_W_MAX) return hipErrorInvalidValue;
+    const int row_blocks = (L + 3) / 4, fixed = device_cu_count() * rows_w;
+    dim3 grid(row_blocks < fixed ? row_blocks : fixed), block(256);
+#define RRT_DISPATCH_ROWS(NV)                                                                                    \
+  do {                                                                                                           \
+    if (RRT_ALLOW_FULL && dim == NV * 256) {                                                                     \
+      if (NV <= 2 && CRMSA && k <= 3)                                                                            \
+        crmsa_dispatch_ln_rows_kernel<NV, CRMSA, true, (NV <= 2 ? 3 : 0)><<<grid, block, 0, st>>>(x1, x0, wdisp, rep2, gamma, beta, y, L, dim, k, g, y16, prec16); \
+      else if (NV <= 2 && CRMSA && DISPATCH_KB5 && k <= 5)                                                       \
+        crmsa_dispatch_ln_rows_kernel<NV, CRMSA, true, (NV <= 2 ? 5 : 0)><<<grid, block, 0, st>>>(x1, x0, wdisp, rep2, gamma, beta, y, L, dim, k, g, y16, prec16); \
+      else if (NV <= 2 && CRMSA)                                                                                 \
+        crmsa_dispatch_ln_rows_kernel<NV, CRMSA, true, (NV <= 2 ? 8 : 0)><<<grid, block, 0, st>>>(x1, x0, wdisp, rep2, gamma, beta, y, L, dim, k, g, y16, prec16); \
+      else                                                                                                       \
+        crmsa_dispatch_ln_rows_kernel<NV, CRMSA, true><<<grid, block, 0, st>>>(x1, x0, wdisp, rep2, gamma, beta, y, L, dim, k, g, y16, prec16);  \
+    } else                                                                                                       \
+      crmsa_dispatch_ln_rows_kernel<NV, CRMSA, false><<<grid, block, 0, st>>>(x1, x0, wdisp, rep2, gamma, beta, y, L, dim, k, g, y16, prec16); \
+  } while (0)
+    if (dim <= 256) RRT_DISPATCH_ROWS(1);
+    else if (dim <= 512) RRT_DISPATCH_ROWS(2);
+    else if (dim <= 1024) RRT_DISPATCH_ROWS(4);
+    else RRT_DISPATCH_ROWS(8);
+#undef RRT_DISPATCH_ROWS
+    return hipGetLastError();
+  }
   dim3 grid((L + 4 * RW_DISPATCH - 1) / (4 * RW_DISPATCH)), block(256);
 #define RRT_DISPATCH(NV)                                                                                         \
   do {                                                                                                           \
@@ -2462,15 +2701,15 @@ hipError_t launch_crmsa_mlp_logits(const float* hid, const float* w2, float* log
 hipError_t launch_crmsa_dispatch_ln(const float* x1, const float* x0, const float* wdisp,
                                     const float* rep2, const float* gamma,
                                     const float* beta, float* y, int dim, int k, const GridDev& g8,
-                                    hipStream_t st, uint16_t* y16, int prec16) {
+                                    hipStream_t st, uint16_t* y16, int prec16, int rows_w) {
   if (y16 != nullptr && (gamma == nullptr || (prec16 != 1 && prec16 != 2) || dim % 4 != 0)) return hipErrorInvalidValue;
-  return launch_dispatch<true>(x1, x0, wdisp, rep2, gamma, beta, y, g8.L, dim, k, g8, st, y16, prec16);
+  return launch_dispatch<true>(x1, x0, wdisp, rep2, gamma, beta, y, g8.L, dim, k, g8, st, y16, prec16, rows_w);
 }
 
 hipError_t launch_layernorm(const float* x1, const float* x0, const float* gamma,
-                            const float* beta, float* y, int L, int dim, hipStream_t st) {
+                            const float* beta, float* y, int L, int dim, hipStream_t st, int rows_w) {
   GridDev g{};
   g.L = L;
   g.H = g.s = g.rs = g.P = 1;
-  return launch_dispatch<false>(x1, x0, nullptr, nullptr, gamma, beta, y, L, dim, 0, g, st);
+  return launch_dispatch<false>(x1, x0, nullptr, nullptr, gamma, beta, y, L, dim, 0, g, st, nullptr, 0, rows_w);
 }

@@ -30,9 +30,14 @@ struct OncePerDevice {
   }
 };
 
+// Row-looping forms of the LayerNorm-type streaming kernels (ln_partition.hip, crmsa.hip): rows_w = 0 takes the one-wave-per-row
+// kernels, rows_w = 1 .. ROWS_W_MAX a fixed grid of device CUs x rows_w four-wave blocks (rows_w waves per SIMD) whose waves
+// loop over the rows.  Same bits either way.  plan_encoder decides (EncoderPlan.rows_w).
+constexpr int ROWS_W_MAX = 3;
+int device_cu_count();
 // zero / n_zero: side job of block 0 -- n_zero ints set to 0 (arrival counters of a later kernel of the same forward)
 hipError_t launch_ln_partition(const float* x, const float* gamma, const float* beta, float* u,
-                               int dim, const GridDev& g, hipStream_t st, int* zero = nullptr, int n_zero = 0);
+                               int dim, const GridDev& g, hipStream_t st, int* zero = nullptr, int n_zero = 0, int rows_w = 0);
 
 struct LinearEpilogue {
   int prec;              // MFMA operand precision: 0 f32 (exact), 1 bf16, 2 f16 (fp32 accumulate)
@@ -220,9 +225,10 @@ hipError_t launch_crmsa_mlp_logits(const float* hid, const float* w2, float* log
 hipError_t launch_crmsa_dispatch_ln(const float* x1, const float* x0, const float* wdisp,
                                     const float* rep2, const float* gamma,
                                     const float* beta, float* y, int dim, int k, const GridDev& g8,
-                                    hipStream_t st, uint16_t* y16 = nullptr, int prec16 = 0);   // y16: the rows also in 16 bits
+                                    hipStream_t st, uint16_t* y16 = nullptr, int prec16 = 0,    // y16: the rows also in 16 bits
+                                    int rows_w = 0);
 hipError_t launch_layernorm(const float* x1, const float* x0, const float* gamma,
-                            const float* beta, float* y, int L, int dim, hipStream_t st);
+                            const float* beta, float* y, int L, int dim, hipStream_t st, int rows_w = 0);
 
 // ABMIL attention pooling behind the encoder (modules/datten.py:28-38,69-83) + predictor (rrt.py:241):
 // per-chunk scores and online-softmax partials, then one merge block

@@ -18,6 +18,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
+from ._head import HeadState, head_compute
 from .encoder import RRTEncoder
 from .mil import lib_linear
 
@@ -171,7 +172,7 @@ class _BranchPool(torch.autograd.Function):
         return dy, dha, dhb, dcw, dcb
 
 
-class CLAM_SB(nn.Module):
+class CLAM_SB(HeadState, nn.Module):
     """modules/clam.py:88-218.  ``rrt``: an rrt_mil_amd.RRTEncoder of width 512, or None.
 
     ``forward(h, label=None, instance_eval=True, return_features=False, attention_only=False)`` returns what the reference
@@ -220,16 +221,8 @@ class CLAM_SB(nn.Module):
         self._ws = None
         self.last_features = None
 
-    def __getstate__(self):          # device workspaces and their validity keys stay with the process (deepcopy / pickle)
-        st = dict(self.__dict__)
-        for k in ("_ws", "_slots", "_w16_key", "last_features", "_cls_pack"):
-            st.pop(k, None)
-        return st
-
-    def __setstate__(self, st):
-        self.__dict__.update(st)
-        self.__dict__.setdefault("_ws", None)
-        self.__dict__.setdefault("last_features", None)
+    _TRANSIENT = HeadState._TRANSIENT + ("last_features", "_cls_pack")
+    _RESET = HeadState._RESET + ("last_features",)
 
     def relocate(self):
         return self.to(torch.device("cuda" if torch.cuda.is_available() else "cpu"))
@@ -250,13 +243,7 @@ class CLAM_SB(nn.Module):
         return mods[:-1], None, mods[-1]
 
     def _compute(self):
-        enc = self.rrt
-        if enc is not None:
-            return enc._compute_mode()
-        if torch.is_autocast_enabled("cuda"):
-            return {torch.bfloat16: _lib.COMPUTE_BF16, torch.float16: _lib.COMPUTE_F16}.get(torch.get_autocast_dtype("cuda"),
-                                                                                             _lib.COMPUTE_F32)
-        return _lib.COMPUTE_F32
+        return head_compute(self.rrt)
 
     def _cls_packed(self):
         """bag classifier rows as [n_classes, 512] + [n_classes] (CLAM_MB: its n_classes Linear(512, 1) packed)"""
@@ -308,7 +295,6 @@ class CLAM_SB(nn.Module):
         rrt_clam_forward_f32 call.  ``attention_only``: A_raw (K, N) instead.  With any of ``return_features`` /
         ``return_attn`` / ``return_topk`` a dict {logits, features (K, 512), attn (K, N), topk (K, 2, k_sample)} of what was
         asked for.  ``solo``: the slide has the GPU to itself (forward_bags passes False with several slides in flight)."""
-        lib = _lib.load()
         if not x2d.is_cuda:
             raise _lib.RRTHipError("rrt_mil_amd.CLAM runs on MI355X only: move the bag to a 'cuda' (HIP) device; there is "
                                    "no CPU fallback")
@@ -320,11 +306,7 @@ class CLAM_SB(nn.Module):
             raise ValueError(f"expected feature dim {self.attention_net[0].in_features}, got {in_dim}")
         x2d = x2d.float().contiguous()
         d, w, _keep = self._desc_weights(in_dim, solo)
-        need = C.c_size_t()
-        _lib.check(lib.rrt_clam_workspace_size(C.byref(d), n, C.byref(need)), "rrt_clam_workspace_size")
         dev = x2d.device
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < need.value:
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
         K = self.n_classes if self._per_branch else 1
         new = lambda *s, dt=torch.float32: torch.empty(s, dtype=dt, device=dev)   # noqa: E731
         logits = new(1, self.n_classes)
@@ -333,17 +315,8 @@ class CLAM_SB(nn.Module):
         feat = new(K, 512) if return_features else None
         topk = new(K, 2, self.k_sample, dt=torch.int64) if return_topk else None
         p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            # reduced-precision modes: are the encoder's 16-bit weight images inside this workspace still those of these
-            # weights?  (rrt_encoder_desc.weights16_valid, see RRTMIL.forward_bag)
-            key = (self._ws.data_ptr(), d.enc.compute, w.enc.version, stream, n)
-            lowp = d.enc.compute != _lib.COMPUTE_F32 and d.has_rrt
-            d.enc.weights16_valid = int(lowp and key == self.__dict__.get("_w16_key"))
-            rc = lib.rrt_clam_forward_f32(C.byref(d), C.byref(w), x2d.data_ptr(), logits.data_ptr(), p(a_raw), p(attn), p(feat),
-                                          p(topk), n, self._ws.data_ptr(), self._ws.numel(), stream)
-            self.__dict__["_w16_key"] = key if rc == 0 and lowp else None
-        _lib.check(rc, "rrt_clam_forward_f32")
+        self._head_forward("clam", d, w, x2d, (logits.data_ptr(), p(a_raw), p(attn), p(feat), p(topk)),
+                           d.enc.compute != _lib.COMPUTE_F32 and d.has_rrt)
         if feat is not None:
             self.last_features = feat
         if attention_only:
@@ -355,44 +328,16 @@ class CLAM_SB(nn.Module):
     @torch.no_grad()
     def forward_bags(self, bags, streams=4, **kw):
         """A batch of independent slides (each (N_i, input_dim) or (1, N_i, input_dim)) -> list of forward_bag results, with
-        ``streams`` slides in flight on the process's bag streams: exactly RRTMIL.forward_bags (one rrt_clam_forward_f32
-        call per slide with its own workspace; the call blocks the host; one call at a time per module)."""
+        ``streams`` slides in flight on the heads' bag scheduler (HeadState._schedule_bags: one rrt_clam_forward_f32 call
+        per slide with its own workspace; the call blocks the host; one call at a time per module)."""
         if not bags:
             return []
         if not bags[0].is_cuda:
             raise _lib.RRTHipError("rrt_mil_amd.CLAM runs on MI355X only; there is no CPU fallback")
         if self._stochastic():
             raise NotImplementedError("forward_bags is an inference entry; in train() call the module itself")
-        from .encoder import _BAG_STREAMS
-        dev = bags[0].device
-        S = max(1, min(int(streams), 4, len(bags)))
-        pool = _BAG_STREAMS.setdefault(dev, [])
-        while len(pool) < S:
-            pool.append(torch.cuda.Stream(dev))
-        slots = self.__dict__.setdefault("_slots", {})
-        cur = torch.cuda.current_stream(dev)
-        order = sorted(range(len(bags)), key=lambda i: -bags[i].shape[-2])        # big slides first, least loaded stream
-        load, outs = [0] * S, [None] * len(bags)
-        for st in pool[:S]:
-            st.wait_stream(cur)
-        ws_was, key_was = self._ws, self.__dict__.get("_w16_key")
-        try:
-            for i in order:
-                s_ = min(range(S), key=lambda t: load[t])
-                load[s_] += bags[i].shape[-2]
-                b = bags[i]
-                self._ws, self.__dict__["_w16_key"] = slots.get((dev, s_), (None, None))
-                with torch.cuda.stream(pool[s_]):
-                    o = self.forward_bag(b[0] if b.dim() == 3 else b, solo=(S == 1), **kw)
-                slots[(dev, s_)] = (self._ws, self.__dict__.get("_w16_key"))
-                for t_ in (o.values() if isinstance(o, dict) else (o,)):
-                    t_.record_stream(cur)        # allocated under the bag stream, consumed on the caller's
-                outs[i] = o
-        finally:
-            self._ws, self.__dict__["_w16_key"] = ws_was, key_was
-            for st in pool[:S]:
-                st.synchronize()
-        return outs
+        return self._schedule_bags(bags, streams, lambda x2, solo: self.forward_bag(x2, solo=solo, **kw),
+                                   lambda o: o.values() if isinstance(o, dict) else (o,))
 
     # ------------------------------------------------------------------ the layer path (graph, dropout, eager comparison)
     def _embed_encode(self, h2d):

@@ -24,6 +24,21 @@ int64_t ceil_sqrt(int64_t n) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The one bump allocator behind every workspace carve.  A carve function states its layout once, as a sequence of take()s,
+// and serves both the size query (base = null: every pointer is null, only bytes() counts) and the real carve, so a size can
+// never disagree with the pointers handed out.  Every piece starts on a 256-byte boundary.
+struct Arena {
+  char* base;
+  size_t off = 0;
+  template <typename T = float>
+  T* take(size_t count) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off = align_up(off + count * sizeof(T), 256);
+    return p;
+  }
+  size_t bytes() const { return off; }
+};
+
 // a failed launch (or any other HIP call) ends the entry point with the HIP error as its return code
 #define RRT_TRY(call)                     \
   do {                                    \
@@ -49,62 +64,57 @@ struct Workspace {
 // One carve function used for both the size query (base = null) and the real carve.
 Workspace carve(const rrt_encoder_desc& d, int64_t N, const rrt_grid& g, const rrt_grid& g8, char* base) {
   Workspace w{};
-  size_t off = 0;
-  auto take = [&](size_t nfloat) {
-    float* p = base ? (float*)(base + off) : nullptr;
-    off = align_up(off + nfloat * sizeof(float), 256);
-    return p;
-  };
+  Arena a{base};
   const size_t D = d.dim;
   const size_t Np = (size_t)g.H * g.H, Np8 = (size_t)g8.H * g8.H;
   const size_t R8 = (size_t)g8.regions_side * g8.regions_side;
   // the weight images first, so that their place does not depend on n_tokens (desc.weights16_valid)
-  if (d.n_rmsa_layers > 0) w.w16 = (uint16_t*)take((size_t)d.n_rmsa_layers * 4 * D * D);     // (F32X3: (hi, lo) pairs = 4 bytes per weight)
-  if (d.cr_msa) w.wcr16 = (uint16_t*)take(2 * D * D);                                         // 4 D^2 16-bit weights
+  if (d.n_rmsa_layers > 0) w.w16 = (uint16_t*)a.take((size_t)d.n_rmsa_layers * 4 * D * D);     // (F32X3: (hi, lo) pairs = 4 bytes per weight)
+  if (d.cr_msa) w.wcr16 = (uint16_t*)a.take(2 * D * D);                                         // 4 D^2 16-bit weights
   if (d.n_rmsa_layers > 0) {
     // w16: its place does not depend on n_tokens (desc.weights16_valid); carved in every mode (4 D^2 floats
     // = 4 MiB per layer at D = 512): the size must not depend on desc.compute, which callers flip between calls on one
     // workspace
-    w.uo = take(Np * D);
-    w.qkv = take(Np * 3 * D);
-    w.xa = take((size_t)N * D);
-    if (d.n_rmsa_layers > 1 || d.ffn) w.xb = take((size_t)N * D);
-    w.proj_cnt = (int*)take((size_t)g.regions_side * g.regions_side);
-    if (d.epeg && d.epeg_type != RRT_EPEG_ATTN) w.pe_out = take(Np * D);
+    w.uo = a.take(Np * D);
+    w.qkv = a.take(Np * 3 * D);
+    w.xa = a.take((size_t)N * D);
+    if (d.n_rmsa_layers > 1 || d.ffn) w.xb = a.take((size_t)N * D);
+    w.proj_cnt = (int*)a.take((size_t)g.regions_side * g.regions_side);
+    if (d.epeg && d.epeg_type != RRT_EPEG_ATTN) w.pe_out = a.take(Np * D);
     if (d.epeg && d.epeg_2d && d.epeg_type == RRT_EPEG_ATTN) {
       const size_t sm = attn_scoremap_scratch_floats(g.regions_side * g.regions_side, g.s * g.s, d.n_heads, d.epeg_k, 1);
-      if (sm) w.smap = take(sm);
+      if (sm) w.smap = a.take(sm);
     }
   }
   if (d.ffn) {
-    if (!w.xa) w.xa = take((size_t)N * D);
-    if (!w.xb) w.xb = take((size_t)N * D);
-    w.ffn_ln = take((size_t)N * D);
-    w.ffn_hid = take((size_t)N * d.ffn_hidden);
+    if (!w.xa) w.xa = a.take((size_t)N * D);
+    if (!w.xb) w.xb = a.take((size_t)N * D);
+    w.ffn_ln = a.take((size_t)N * D);
+    w.ffn_hid = a.take((size_t)N * d.ffn_hidden);
   }
   if (d.cr_msa) {
     const size_t k = d.crmsa_k;
-    w.mean_rstd = take((size_t)N * 2);
-    w.logits = take(Np8 * k);
-    w.wdisp = take(Np8 * k);
-    w.rep = take(k * R8 * D);
-    w.rep_qkv = take(k * R8 * 3 * D);
-    w.rep_o = take(k * R8 * D);
-    w.rep2 = take(k * R8 * D);
-    w.rep16 = (uint16_t*)take(k * R8 * D / 2);
-    w.repo16 = (uint16_t*)take(k * R8 * D / 2);
+    w.mean_rstd = a.take((size_t)N * 2);
+    w.logits = a.take(Np8 * k);
+    w.wdisp = a.take(Np8 * k);
+    w.rep = a.take(k * R8 * D);
+    w.rep_qkv = a.take(k * R8 * 3 * D);
+    w.rep_o = a.take(k * R8 * D);
+    w.rep2 = a.take(k * R8 * D);
+    w.rep16 = (uint16_t*)a.take(k * R8 * D / 2);
+    w.repo16 = (uint16_t*)a.take(k * R8 * D / 2);
     if (d.n_rmsa_layers > 0) {
-      w.cr_part = take(crmsa_region4_scratch_floats(to_dev(g8), d.crmsa_k));
-      w.cr_cnt = (int*)take(64);
-      if (D % 64 == 0) w.cr_pstat = take(crmsa_parts_floats(N, (int)D, d.crmsa_k));
+      w.cr_part = a.take(crmsa_region4_scratch_floats(to_dev(g8), d.crmsa_k));
+      w.cr_cnt = (int*)a.take(64);
+      if (D % 64 == 0) w.cr_pstat = a.take(crmsa_parts_floats(N, (int)D, d.crmsa_k));
     }
     if (d.crmsa_mlp) {
-      w.v8 = take(Np8 * D);
-      w.hid = take(Np8 * (D / 4));
+      w.v8 = a.take(Np8 * D);
+      w.hid = a.take(Np8 * (D / 4));
     }
   }
-  if (d.pos) w.xp = take((size_t)N * D);
-  w.bytes = off ? off : 256;
+  if (d.pos) w.xp = a.take((size_t)N * D);
+  w.bytes = a.bytes() ? a.bytes() : 256;
   return w;
 }
 
@@ -904,25 +914,20 @@ BatchWs carve_batch(const rrt_encoder_desc& d, int64_t B, int64_t N, const rrt_g
   // (the single-bag carve is sized by its QUERY form: with ffn = 1 the query counts xa / xb twice -- a null pointer does not
   //  tell it they are taken -- so the queried size, which encoder_forward checks against, exceeds what the real carve uses)
   w.one_bytes = carve(d, N, g, g8, nullptr).bytes;
-  w.one = carve(d, N, g, g8, base);
-  size_t off = align_up(w.one_bytes, 256);
-  auto take = [&](size_t nfloat) {
-    float* p = base ? (float*)(base + off) : nullptr;
-    off = align_up(off + nfloat * sizeof(float), 256);
-    return p;
-  };
+  Arena a{base};
+  w.one = carve(d, N, g, g8, a.take<char>(w.one_bytes));
   const size_t D = d.dim, Np8 = (size_t)g8.H * g8.H, R8 = (size_t)g8.regions_side * g8.regions_side, k = d.crmsa_k;
-  w.x1 = take((size_t)B * N * D);
+  w.x1 = a.take((size_t)B * N * D);
   if (d.cr_msa) {
-    w.mean_rstd = take((size_t)B * N * 2);
-    w.logits = take((size_t)B * Np8 * k);
-    w.wdisp = take((size_t)B * Np8 * k);
-    w.rep = take(k * R8 * B * D);
-    w.rep_qkv = take(k * R8 * B * 3 * D);
-    w.rep_o = take(k * R8 * B * D);
-    w.rep2 = take(k * R8 * B * D);
+    w.mean_rstd = a.take((size_t)B * N * 2);
+    w.logits = a.take((size_t)B * Np8 * k);
+    w.wdisp = a.take((size_t)B * Np8 * k);
+    w.rep = a.take(k * R8 * B * D);
+    w.rep_qkv = a.take(k * R8 * B * 3 * D);
+    w.rep_o = a.take(k * R8 * B * D);
+    w.rep2 = a.take(k * R8 * B * D);
   }
-  w.bytes = off;
+  w.bytes = a.bytes();
   return w;
 }
 }  // namespace
@@ -1385,24 +1390,145 @@ int rrt_layernorm_f32(const float* x1, const float* x0, const float* gamma, cons
 // ------------------------------------------------------------------ row f1: RRTMIL around the encoder
 namespace {
 
+// ---- the front every head around the encoder shares: patch_to_emb (Linear + activation in the GEMM epilogue) -> the
+// encoder, where the head has one.  rrt_mil_desc / rrt_clam_desc / rrt_dsmil_desc each hold these fields.
+struct HeadFront {
+  const rrt_encoder_desc* enc;   // (enc->dim is the embedding width whether or not there is an encoder)
+  int input_dim, emb_act, has_rrt;
+  int input16;                   // RRTMIL: the caller's features ARE the 16-bit operand (RRT_COMPUTE_BF16 / F16), else 0
+};
+HeadFront head_front(const rrt_mil_desc* d) { return HeadFront{&d->enc, d->input_dim, d->emb_act, 1, d->input16}; }
+HeadFront head_front(const rrt_clam_desc* d) { return HeadFront{&d->enc, d->input_dim, d->emb_act, d->has_rrt, 0}; }
+HeadFront head_front(const rrt_dsmil_desc* d) { return HeadFront{&d->enc, d->input_dim, d->emb_act, d->has_rrt, 0}; }
+
+// F32X3 concerns the R-MSA layers' big products only (encoder_forward): the GEMMs around the encoder are exact fp32
+int gemm_precision(int compute) { return compute == RRT_COMPUTE_F32X3 ? RRT_COMPUTE_F32 : compute; }
+
+int check_head_front(const HeadFront& f, int64_t N) {
+  if (N <= 0) return RRT_E_INVALID;
+  if (f.has_rrt) {
+    int rc = check_desc(f.enc, N);
+    if (rc) return rc;
+  }
+  if (f.input_dim <= 0 || f.input_dim % 32) return unsupported("input_dim must be a positive multiple of 32");
+  if (f.emb_act != RRT_ACT_NONE && f.emb_act != RRT_ACT_RELU && f.emb_act != RRT_ACT_GELU)
+    return unsupported("emb_act must be none/relu/gelu");
+  if (f.enc->compute < 0 || f.enc->compute > RRT_COMPUTE_F32X3) return unsupported("compute must be RRT_COMPUTE_*");
+  return RRT_OK;
+}
+
+// The workspace of a head's one-call forward: embedding, encoder output, the encoder's own workspace, the head's scratch
+// (head_bytes, carved by the head) and the 16-bit images of the reduced-precision modes -- the feature matrix and
+// patch_to_emb's weight and, with pool16_hidden > 0, the encoder's output rows and two [pool16_hidden, dim] weights of the
+// head's first Linears (0: the head keeps fp32 operands, DSMIL).  The images are part of the size in every mode, so that a
+// workspace sized once serves a module that switches modes.
+struct HeadWs {
+  float *emb, *y;      // (y == emb without an encoder)
+  char *enc_ws, *head;
+  size_t enc_bytes;
+  uint16_t *x16, *w16, *y16, *pa16, *pb16;
+  size_t bytes;
+};
+int carve_head(const HeadFront& f, int64_t N, size_t head_bytes, int pool16_hidden, char* base, HeadWs* out) {
+  HeadWs w{};
+  if (f.has_rrt) {
+    int rc = rrt_encoder_workspace_size(f.enc, N, &w.enc_bytes);
+    if (rc) return rc;
+  }
+  const size_t D = f.enc->dim;
+  Arena a{base};
+  w.emb = a.take((size_t)N * D);
+  w.y = a.take((size_t)N * D);
+  if (!f.has_rrt) w.y = w.emb;
+  w.enc_ws = a.take<char>(w.enc_bytes);
+  w.head = a.take<char>(head_bytes);
+  w.x16 = a.take<uint16_t>((size_t)N * f.input_dim);
+  w.w16 = a.take<uint16_t>(D * f.input_dim);
+  if (pool16_hidden > 0) {
+    w.y16 = a.take<uint16_t>((size_t)N * D);
+    w.pa16 = a.take<uint16_t>((size_t)pool16_hidden * D);
+    w.pb16 = a.take<uint16_t>((size_t)pool16_hidden * D);
+  }
+  w.bytes = a.bytes();
+  *out = w;
+  return RRT_OK;
+}
+
+// patch_to_emb and the encoder of one bag; everything checked by the caller.  pool_a_w / pool_b_w (b may be null): the
+// head's first Linears [pool_hidden, dim], whose 16-bit images ride in the one cast launch where the encoder leaves its
+// output rows in 16 bits as a by-product (*p16: ws.y16 / pa16 / pb16 are then valid operands); null for a head that keeps
+// fp32 operands.  y_out: the caller's buffer for the encoder's output rows instead of ws.y.  tuning: honour the
+// RRT_NO_FC16 / RRT_NO_POOL16 tuning variables (RRTMIL).
+int head_front_forward(const HeadFront& f, const HeadWs& ws, const float* x, const float* emb_w, const float* emb_b,
+                       const rrt_encoder_weights* enc_w, const float* pool_a_w, const float* pool_b_w, int pool_hidden,
+                       float* y_out, bool tuning, int64_t N, void* stream, bool* p16) {
+  static const bool env_no_fc16 = rrt_tune_env("RRT_NO_FC16") != nullptr;
+  static const bool env_no_pool16 = rrt_tune_env("RRT_NO_POOL16") != nullptr;
+  const int D = f.enc->dim;
+  hipStream_t st = (hipStream_t)stream;
+  const int gemm_prec = gemm_precision(f.enc->compute);
+  LinearEpilogue ep{};
+  ep.prec = gemm_prec;
+  ep.bias = emb_b;
+  ep.act = f.emb_act;
+  // Reduced-precision modes (round 5): the features and the weight are cast to 16 bits by one streaming launch and the GEMM
+  // runs on 16-bit operands through LDS-DMA.  The fp32-operand kernel rounds the same values to the same 16-bit numbers,
+  // but after staging them in LDS as fp32: twice the DMA bytes through a path that is issue-bound (41 us at
+  // N = 9000 x 1024 against ~10 + ~13 here).
+  const bool fc16 = !(tuning && env_no_fc16) && (gemm_prec == RRT_COMPUTE_BF16 || gemm_prec == RRT_COMPUTE_F16) &&
+                    f.input_dim % 64 == 0;
+  if (f.input16 != 0 && (f.input16 != gemm_prec || !fc16))
+    return unsupported("rrt_mil_forward: 16-bit features (input16) need enc.compute == input16 (bf16 / f16) and input_dim % 64 == 0");
+  bool pool16 = false, y16_done = false;
+  hipError_t e;
+  if (fc16) {
+    const uint16_t* x16 = ws.x16;
+    Cast16Jobs cj{};
+    if (f.input16) {                 // the caller's features ARE the 16-bit operand: only the weight is cast
+      x16 = (const uint16_t*)x;
+    } else {
+      cj.src[0] = x; cj.dst[0] = ws.x16; cj.n4[0] = (size_t)N * f.input_dim / 4;
+      cj.count = 1;
+    }
+    cj.src[cj.count] = emb_w; cj.dst[cj.count] = ws.w16; cj.n4[cj.count++] = (size_t)D * f.input_dim / 4;
+    // the head's first Linears' weights in the same launch (their 16-bit-operand product reads the encoder's y16)
+    pool16 = pool_a_w && ws.y16 && !(tuning && env_no_pool16) && f.has_rrt && D % 64 == 0 &&
+             ((size_t)pool_hidden * D) % 4 == 0 && cj.count + 2 <= CAST16_MAX_JOBS;
+    if (pool16) {
+      cj.src[cj.count] = pool_a_w; cj.dst[cj.count] = ws.pa16; cj.n4[cj.count++] = (size_t)pool_hidden * D / 4;
+      if (pool_b_w) {
+        cj.src[cj.count] = pool_b_w; cj.dst[cj.count] = ws.pb16; cj.n4[cj.count++] = (size_t)pool_hidden * D / 4;
+      }
+    }
+    e = launch_cast16(cj, gemm_prec, st);
+    if (e != hipSuccess) return (int)e;
+    e = launch_linear16(x16, ws.w16, ws.emb, (int)N, D, f.input_dim, ep, st);
+  } else {
+    e = launch_linear(x, emb_w, ws.emb, (int)N, D, f.input_dim, ep, st);
+  }
+  if (e != hipSuccess) return (int)e;
+  if (f.has_rrt) {
+    int rc = encoder_forward(f.enc, enc_w, ws.emb, y_out ? y_out : ws.y, N, ws.enc_ws, ws.enc_bytes, stream, nullptr, nullptr,
+                             nullptr, pool16 ? ws.y16 : nullptr, &y16_done);
+    if (rc) return rc;
+  }
+  *p16 = pool16 && y16_done;
+  return RRT_OK;
+}
+
 struct PoolWs {
   float *hid_a, *hid_b, *a_raw, *part;
   size_t bytes;
 };
 PoolWs carve_pool(int64_t N, int dim, int hidden, int gated, char* base) {
   PoolWs w{};
-  size_t off = 0;
-  auto take = [&](size_t nfloat) {
-    float* p = base ? (float*)(base + off) : nullptr;
-    off = align_up(off + nfloat * sizeof(float), 256);
-    return p;
-  };
+  Arena a{base};
   const size_t nb = (size_t)(N + POOL_CHUNK - 1) / POOL_CHUNK;
-  w.hid_a = take((size_t)N * hidden);
-  if (gated) w.hid_b = take((size_t)N * hidden);
-  w.a_raw = take((size_t)N);
-  w.part = take(nb * ((size_t)dim + 4));
-  w.bytes = off;
+  w.hid_a = a.take((size_t)N * hidden);
+  if (gated) w.hid_b = a.take((size_t)N * hidden);
+  w.a_raw = a.take((size_t)N);
+  w.part = a.take(nb * ((size_t)dim + 4));
+  w.bytes = a.bytes();
   return w;
 }
 
@@ -1452,12 +1578,17 @@ int pool_predict(const float* y, const float* a_w, const float* a_b, const float
 
 int check_mil(const rrt_mil_desc* d, int64_t N) {
   if (!d) return RRT_E_INVALID;
-  int rc = check_desc(&d->enc, N);
+  int rc = check_head_front(head_front(d), N);
   if (rc) return rc;
-  if (d->input_dim <= 0 || d->input_dim % 32) return unsupported("input_dim must be a positive multiple of 32");
-  if (d->emb_act != RRT_ACT_NONE && d->emb_act != RRT_ACT_RELU && d->emb_act != RRT_ACT_GELU)
-    return unsupported("emb_act must be none/relu/gelu");
   return check_pool(N, d->enc.dim, d->pool_hidden, d->pool_act, d->n_classes);
+}
+
+// RRTMIL's workspace: the shared head layout around carve_pool's scratch
+int carve_mil(const rrt_mil_desc* d, int64_t N, char* base, HeadWs* hw, PoolWs* pws) {
+  int rc = carve_head(head_front(d), N, carve_pool(N, d->enc.dim, d->pool_hidden, d->pool_gated, nullptr).bytes, d->pool_hidden,
+                      base, hw);
+  if (rc == RRT_OK && pws) *pws = carve_pool(N, d->enc.dim, d->pool_hidden, d->pool_gated, hw->head);
+  return rc;
 }
 
 // ---- CLAM heads (clam_pool.hip)
@@ -1483,37 +1614,33 @@ struct ClamWs {
 };
 ClamWs carve_clam(int64_t N, int dim, int hidden, int gated, int K, char* base) {
   ClamWs w{};
-  size_t off = 0;
-  auto take = [&](size_t nfloat) {
-    float* p = base ? (float*)(base + off) : nullptr;
-    off = align_up(off + nfloat * sizeof(float), 256);
-    return p;
-  };
-  w.hid_a = take((size_t)N * hidden);
-  if (gated) w.hid_b = take((size_t)N * hidden);
-  w.a_raw = take((size_t)K * N);
-  w.attn = take((size_t)K * N);
-  w.pooled = take((size_t)K * dim);
-  w.part = take(branch_pool_part_floats((int)N, dim, K));
-  w.bytes = off;
+  Arena a{base};
+  w.hid_a = a.take((size_t)N * hidden);
+  if (gated) w.hid_b = a.take((size_t)N * hidden);
+  w.a_raw = a.take((size_t)K * N);
+  w.attn = a.take((size_t)K * N);
+  w.pooled = a.take((size_t)K * dim);
+  w.part = a.take(branch_pool_part_floats((int)N, dim, K));
+  w.bytes = a.bytes();
   return w;
 }
 
 int check_clam(const rrt_clam_desc* d, int64_t N) {
-  if (!d || N <= 0) return RRT_E_INVALID;
-  if (d->has_rrt) {
-    int rc = check_desc(&d->enc, N);
-    if (rc) return rc;
-  }
-  if (d->input_dim <= 0 || d->input_dim % 32) return unsupported("input_dim must be a positive multiple of 32");
-  if (d->emb_act != RRT_ACT_NONE && d->emb_act != RRT_ACT_RELU && d->emb_act != RRT_ACT_GELU)
-    return unsupported("emb_act must be none/relu/gelu");
-  if (d->enc.compute < 0 || d->enc.compute > RRT_COMPUTE_F32X3) return unsupported("compute must be RRT_COMPUTE_*");
+  if (!d) return RRT_E_INVALID;
+  int rc = check_head_front(head_front(d), N);
+  if (rc) return rc;
   if (d->n_classes <= 0) return RRT_E_INVALID;
   if (d->per_branch && d->n_classes > 8) return unsupported("CLAM_MB: n_classes <= 8 (one attention branch per class)");
   return check_branch_pool(N, d->enc.dim, d->hidden, d->per_branch ? d->n_classes : 1);
 }
 
+// the CLAM heads' workspace: the shared head layout around carve_clam's scratch
+int carve_clam_head(const rrt_clam_desc* d, int64_t N, char* base, HeadWs* hw, ClamWs* cws) {
+  const int K = d->per_branch ? d->n_classes : 1;
+  int rc = carve_head(head_front(d), N, carve_clam(N, d->enc.dim, d->hidden, d->gated, K, nullptr).bytes, d->hidden, base, hw);
+  if (rc == RRT_OK && cws) *cws = carve_clam(N, d->enc.dim, d->hidden, d->gated, K, hw->head);
+  return rc;
+}
 
 // ---- DSMIL head (dsmil_pool.hip)
 int check_instance_max(int64_t N, int dim, int C) {
@@ -1532,10 +1659,11 @@ struct IMaxWs {
 };
 IMaxWs carve_imax(int64_t N, int C, char* base) {
   IMaxWs w{};
-  const size_t rec = align_up(instance_max_part_records((int)N) * C * sizeof(float), 256);
-  w.pv = base ? (float*)base : nullptr;
-  w.pi = base ? (int*)(base + rec) : nullptr;
-  w.bytes = 2 * rec;
+  Arena a{base};
+  const size_t rec = (size_t)instance_max_part_records((int)N) * C;
+  w.pv = a.take(rec);
+  w.pi = a.take<int>(rec);
+  w.bytes = a.bytes();
   return w;
 }
 
@@ -1556,34 +1684,49 @@ struct DsmilWs {
 };
 DsmilWs carve_dsmil_pool(int64_t N, int dim, int C, char* base) {
   DsmilWs w{};
-  size_t off = 0;
-  auto take = [&](size_t nfloat) {
-    float* p = base ? (float*)(base + off) : nullptr;
-    off = align_up(off + nfloat * sizeof(float), 256);
-    return p;
-  };
-  w.v = take((size_t)C * dim);
-  w.vb = take(16);
-  w.lpart = take(64);
-  w.raw = take((size_t)N * C);
-  w.part = take(dsmil_pool_part_floats((int)N, dim, C));
-  w.bytes = off;
+  Arena a{base};
+  w.v = a.take((size_t)C * dim);
+  w.vb = a.take(16);
+  w.lpart = a.take(64);
+  w.raw = a.take((size_t)N * C);
+  w.part = a.take(dsmil_pool_part_floats((int)N, dim, C));
+  w.bytes = a.bytes();
   return w;
 }
 
 int check_dsmil(const rrt_dsmil_desc* d, int64_t N) {
-  if (!d || N <= 0) return RRT_E_INVALID;
-  if (d->has_rrt) {
-    int rc = check_desc(&d->enc, N);
-    if (rc) return rc;
-  }
-  if (d->input_dim <= 0 || d->input_dim % 32) return unsupported("input_dim must be a positive multiple of 32");
-  if (d->emb_act != RRT_ACT_NONE && d->emb_act != RRT_ACT_RELU && d->emb_act != RRT_ACT_GELU)
-    return unsupported("emb_act must be none/relu/gelu");
-  if (d->enc.compute < 0 || d->enc.compute > RRT_COMPUTE_F32X3) return unsupported("compute must be RRT_COMPUTE_*");
-  int rc = check_instance_max(N, d->enc.dim, d->n_classes);
+  if (!d) return RRT_E_INVALID;
+  int rc = check_head_front(head_front(d), N);
+  if (rc) return rc;
+  rc = check_instance_max(N, d->enc.dim, d->n_classes);
   if (rc) return rc;
   return check_dsmil_pool(N, d->enc.dim, d->q_dim, d->n_classes);
+}
+
+// MILNet's workspace: the shared head layout (no 16-bit images behind the encoder) around the two streams' scratch and one
+// 256-byte piece for the critical instances [8] and the class maxima [8] of a caller that does not ask for them
+struct DsmilHeadWs {
+  IMaxWs imax;
+  DsmilWs pool;
+  long long* argmax;
+  float* cmax;
+  size_t bytes;
+};
+DsmilHeadWs carve_dsmil_scratch(int64_t N, int dim, int C, char* base) {
+  DsmilHeadWs w{};
+  Arena a{base};
+  w.imax = carve_imax(N, C, a.take<char>(carve_imax(N, C, nullptr).bytes));
+  w.pool = carve_dsmil_pool(N, dim, C, a.take<char>(carve_dsmil_pool(N, dim, C, nullptr).bytes));
+  char* tail = a.take<char>(256);
+  w.argmax = (long long*)tail;
+  w.cmax = tail ? (float*)(tail + 64) : nullptr;
+  w.bytes = a.bytes();
+  return w;
+}
+int carve_dsmil_head(const rrt_dsmil_desc* d, int64_t N, char* base, HeadWs* hw, DsmilHeadWs* dws) {
+  int rc = carve_head(head_front(d), N, carve_dsmil_scratch(N, d->enc.dim, d->n_classes, nullptr).bytes, 0, base, hw);
+  if (rc == RRT_OK && dws) *dws = carve_dsmil_scratch(N, d->enc.dim, d->n_classes, hw->head);
+  return rc;
 }
 
 }  // namespace
@@ -1674,17 +1817,10 @@ int rrt_mil_workspace_size(const rrt_mil_desc* desc, int64_t n_tokens, size_t* b
   if (!bytes) return RRT_E_INVALID;
   int rc = check_mil(desc, n_tokens);
   if (rc) return rc;
-  size_t enc = 0;
-  rc = rrt_encoder_workspace_size(&desc->enc, n_tokens, &enc);
+  HeadWs hw;
+  rc = carve_mil(desc, n_tokens, nullptr, &hw, nullptr);
   if (rc) return rc;
-  const size_t act = align_up((size_t)n_tokens * desc->enc.dim * sizeof(float), 256);
-  // (+ the 16-bit images of the feature matrix and of patch_to_emb's weight for the reduced-precision modes: the same size
-  // in every mode, so that a workspace sized once serves a module that switches modes)
-  *bytes = 2 * act + align_up(enc, 256) +
-           align_up(carve_pool(n_tokens, desc->enc.dim, desc->pool_hidden, desc->pool_gated, nullptr).bytes, 256) +
-           align_up((size_t)n_tokens * desc->input_dim * 2, 256) + align_up((size_t)desc->enc.dim * desc->input_dim * 2, 256) +
-           // (round 6) the encoder's output rows in 16 bits + the pooling Linears' 16-bit weight images
-           align_up((size_t)n_tokens * desc->enc.dim * 2, 256) + 2 * align_up((size_t)desc->pool_hidden * desc->enc.dim * 2, 256);
+  *bytes = hw.bytes;
   return RRT_OK;
 }
 
@@ -1696,79 +1832,21 @@ int rrt_mil_forward_f32(const rrt_mil_desc* desc, const rrt_mil_weights* w, cons
   if (rc) return rc;
   if (!w->emb_w || !w->pool_a_w || !w->pool_c_w || !w->pred_w || (desc->pool_gated && !w->pool_b_w))
     return RRT_E_INVALID;
-  size_t need = 0, enc_bytes = 0;
-  rc = rrt_mil_workspace_size(desc, n_tokens, &need);
+  HeadWs hw;
+  PoolWs pws;
+  rc = carve_mil(desc, n_tokens, (char*)workspace, &hw, &pws);
   if (rc) return rc;
-  if (!workspace || workspace_bytes < need) return RRT_E_WORKSPACE;
-  rc = rrt_encoder_workspace_size(&desc->enc, n_tokens, &enc_bytes);
+  if (!workspace || workspace_bytes < hw.bytes) return RRT_E_WORKSPACE;
+  const float* pool_b_w = desc->pool_gated ? w->pool_b_w : nullptr;
+  float* y = feat ? feat : hw.y;
+  bool p16 = false;
+  rc = head_front_forward(head_front(desc), hw, x, w->emb_w, w->emb_b, &w->enc, w->pool_a_w, pool_b_w, desc->pool_hidden, y,
+                          /*tuning=*/true, n_tokens, stream, &p16);
   if (rc) return rc;
-  const int D = desc->enc.dim;
-  const size_t act = align_up((size_t)n_tokens * D * sizeof(float), 256);
-  char* base = (char*)workspace;
-  float* emb = (float*)base;
-  float* y = feat ? feat : (float*)(base + act);
-  char* enc_ws = base + 2 * act;
-  PoolWs pws = carve_pool(n_tokens, D, desc->pool_hidden, desc->pool_gated, enc_ws + align_up(enc_bytes, 256));
-  hipStream_t st = (hipStream_t)stream;
-
-  // F32X3 concerns the R-MSA layers' big products only (encoder_forward): the GEMMs around the encoder are exact fp32
-  const int gemm_prec = desc->enc.compute == RRT_COMPUTE_F32X3 ? RRT_COMPUTE_F32 : desc->enc.compute;
-  LinearEpilogue ep{};
-  ep.prec = gemm_prec;
-  ep.bias = w->emb_b;
-  ep.act = desc->emb_act;
-  // Reduced-precision modes (round 5): the features and the weight are cast to 16 bits by one streaming launch and the GEMM
-  // runs on 16-bit operands through LDS-DMA.  The fp32-operand kernel rounds the same values to the same 16-bit numbers,
-  // but after staging them in LDS as fp32: twice the DMA bytes through a path that is issue-bound (41 us at
-  // N = 9000 x 1024 against ~10 + ~13 here).
-  static const bool no_fc16 = rrt_tune_env("RRT_NO_FC16") != nullptr;
-  static const bool no_pool16 = rrt_tune_env("RRT_NO_POOL16") != nullptr;
-  uint16_t *y16 = nullptr, *pa16 = nullptr, *pb16 = nullptr;
-  bool pool16 = false, y16_done = false;
-  hipError_t e;
-  if (desc->input16 != 0 && (desc->input16 != gemm_prec || (gemm_prec != RRT_COMPUTE_BF16 && gemm_prec != RRT_COMPUTE_F16) ||
-                             desc->input_dim % 64 != 0 || no_fc16))
-    return unsupported("rrt_mil_forward: 16-bit features (input16) need enc.compute == input16 (bf16 / f16) and input_dim % 64 == 0");
-  if (!no_fc16 && (gemm_prec == RRT_COMPUTE_BF16 || gemm_prec == RRT_COMPUTE_F16) && desc->input_dim % 64 == 0) {
-    char* tail = enc_ws + align_up(enc_bytes, 256) + align_up(pws.bytes, 256);
-    uint16_t* x16 = (uint16_t*)tail;
-    uint16_t* w16 = (uint16_t*)(tail + align_up((size_t)n_tokens * desc->input_dim * 2, 256));
-    y16 = (uint16_t*)((char*)w16 + align_up((size_t)D * desc->input_dim * 2, 256));
-    pa16 = (uint16_t*)((char*)y16 + align_up((size_t)n_tokens * D * 2, 256));
-    pb16 = (uint16_t*)((char*)pa16 + align_up((size_t)desc->pool_hidden * D * 2, 256));
-    Cast16Jobs cj{};
-    if (desc->input16) {                 // the caller's features ARE the 16-bit operand: only the weight is cast
-      x16 = (uint16_t*)x;
-      cj.src[0] = w->emb_w; cj.dst[0] = w16; cj.n4[0] = (size_t)D * desc->input_dim / 4;
-      cj.count = 1;
-    } else {
-      cj.src[0] = x; cj.dst[0] = x16; cj.n4[0] = (size_t)n_tokens * desc->input_dim / 4;
-      cj.src[1] = w->emb_w; cj.dst[1] = w16; cj.n4[1] = (size_t)D * desc->input_dim / 4;
-      cj.count = 2;
-    }
-    // the pooling Linears' weights in the same launch (their 16-bit-operand product reads the encoder's y16, below)
-    pool16 = !no_pool16 && D % 64 == 0 && ((size_t)desc->pool_hidden * D) % 4 == 0 && cj.count + 2 <= CAST16_MAX_JOBS;
-    if (pool16) {
-      cj.src[cj.count] = w->pool_a_w; cj.dst[cj.count] = pa16; cj.n4[cj.count++] = (size_t)desc->pool_hidden * D / 4;
-      if (desc->pool_gated) {
-        cj.src[cj.count] = w->pool_b_w; cj.dst[cj.count] = pb16; cj.n4[cj.count++] = (size_t)desc->pool_hidden * D / 4;
-      }
-    }
-    e = launch_cast16(cj, gemm_prec, st);
-    if (e != hipSuccess) return (int)e;
-    e = launch_linear16(x16, w16, emb, (int)n_tokens, D, desc->input_dim, ep, st);
-  } else {
-    e = launch_linear(x, w->emb_w, emb, (int)n_tokens, D, desc->input_dim, ep, st);
-  }
-  if (e != hipSuccess) return (int)e;
-  rc = encoder_forward(&desc->enc, &w->enc, emb, y, n_tokens, enc_ws, enc_bytes, stream, nullptr, nullptr, nullptr,
-                       pool16 ? y16 : nullptr, &y16_done);
-  if (rc) return rc;
-  const bool p16 = pool16 && y16_done;
-  return pool_predict(y, w->pool_a_w, w->pool_a_b, desc->pool_gated ? w->pool_b_w : nullptr, w->pool_b_b,
-                      w->pool_c_w, w->pool_c_b, w->pred_w, w->pred_b, nullptr, logits, attn, no_norm, n_tokens,
-                      D, desc->pool_hidden, desc->pool_act, desc->n_classes, gemm_prec, pws, st, p16 ? y16 : nullptr,
-                      p16 ? pa16 : nullptr, (p16 && desc->pool_gated) ? pb16 : nullptr);
+  return pool_predict(y, w->pool_a_w, w->pool_a_b, pool_b_w, w->pool_b_b, w->pool_c_w, w->pool_c_b, w->pred_w, w->pred_b,
+                      nullptr, logits, attn, no_norm, n_tokens, desc->enc.dim, desc->pool_hidden, desc->pool_act,
+                      desc->n_classes, gemm_precision(desc->enc.compute), pws, (hipStream_t)stream, p16 ? hw.y16 : nullptr,
+                      p16 ? hw.pa16 : nullptr, (p16 && pool_b_w) ? hw.pb16 : nullptr);
 }
 
 // ---- CLAM heads: the branch pool alone (forward, backward), top-k of rows, and the one-call CLAM_SB / CLAM_MB forward
@@ -1815,23 +1893,14 @@ int rrt_topk_rows_f32(const float* x, int64_t* idx, int32_t n_rows, int64_t n, i
   return (int)launch_topk_rows(x, (long long*)idx, n_rows, (int)n, k, (hipStream_t)stream);
 }
 
-static size_t clam_act_bytes(const rrt_clam_desc* d, int64_t N) { return align_up((size_t)N * d->enc.dim * sizeof(float), 256); }
-
 int rrt_clam_workspace_size(const rrt_clam_desc* desc, int64_t n_tokens, size_t* bytes) {
   if (!bytes) return RRT_E_INVALID;
   int rc = check_clam(desc, n_tokens);
   if (rc) return rc;
-  size_t enc = 0;
-  if (desc->has_rrt) {
-    rc = rrt_encoder_workspace_size(&desc->enc, n_tokens, &enc);
-    if (rc) return rc;
-  }
-  const int D = desc->enc.dim, K = desc->per_branch ? desc->n_classes : 1;
-  // (as rrt_mil_workspace_size: the 16-bit images of the reduced-precision modes are part of the size in every mode)
-  *bytes = 2 * clam_act_bytes(desc, n_tokens) + align_up(enc, 256) +
-           align_up(carve_clam(n_tokens, D, desc->hidden, desc->gated, K, nullptr).bytes, 256) +
-           align_up((size_t)n_tokens * desc->input_dim * 2, 256) + align_up((size_t)D * desc->input_dim * 2, 256) +
-           align_up((size_t)n_tokens * D * 2, 256) + 2 * align_up((size_t)desc->hidden * D * 2, 256);
+  HeadWs hw;
+  rc = carve_clam_head(desc, n_tokens, nullptr, &hw, nullptr);
+  if (rc) return rc;
+  *bytes = hw.bytes;
   return RRT_OK;
 }
 
@@ -1848,73 +1917,30 @@ int rrt_clam_forward_f32(const rrt_clam_desc* desc, const rrt_clam_weights* w, c
     if (n_tokens < desc->k_sample) return RRT_E_INVALID;
   }
   if (branch_pool_merge_lds((int)n_tokens, desc->enc.dim) > 150 * 1024) return unsupported("branch pool: bag too large for the merge block");
-  size_t need = 0, enc_bytes = 0;
-  rc = rrt_clam_workspace_size(desc, n_tokens, &need);
+  HeadWs hw;
+  ClamWs cws;
+  rc = carve_clam_head(desc, n_tokens, (char*)workspace, &hw, &cws);
   if (rc) return rc;
-  if (!workspace || workspace_bytes < need) return RRT_E_WORKSPACE;
-  if (desc->has_rrt) {
-    rc = rrt_encoder_workspace_size(&desc->enc, n_tokens, &enc_bytes);
-    if (rc) return rc;
-  }
+  if (!workspace || workspace_bytes < hw.bytes) return RRT_E_WORKSPACE;
   const int D = desc->enc.dim, K = desc->per_branch ? desc->n_classes : 1, H = desc->hidden;
-  const size_t act = clam_act_bytes(desc, n_tokens);
-  char* base = (char*)workspace;
-  float* emb = (float*)base;
-  float* y = desc->has_rrt ? (float*)(base + act) : emb;
-  char* enc_ws = base + 2 * act;
-  ClamWs cws = carve_clam(n_tokens, D, H, desc->gated, K, enc_ws + align_up(enc_bytes, 256));
   hipStream_t st = (hipStream_t)stream;
-
-  // the GEMMs around the encoder follow enc.compute exactly as in rrt_mil_forward_f32 (F32X3: exact fp32 here)
-  const int gemm_prec = desc->enc.compute == RRT_COMPUTE_F32X3 ? RRT_COMPUTE_F32 : desc->enc.compute;
+  const float* y = hw.y;
+  bool p16 = false;
+  rc = head_front_forward(head_front(desc), hw, x, w->emb_w, w->emb_b, &w->enc, w->a_w, desc->gated ? w->b_w : nullptr, H,
+                          nullptr, /*tuning=*/false, n_tokens, stream, &p16);
+  if (rc) return rc;
+  // the gate Linears: on the encoder's 16-bit rows and the weight images of the front's cast launch where it left them
   LinearEpilogue ep{};
-  ep.prec = gemm_prec;
-  ep.bias = w->emb_b;
-  ep.act = desc->emb_act;
-  uint16_t *y16 = nullptr, *pa16 = nullptr, *pb16 = nullptr;
-  bool pool16 = false, y16_done = false;
-  hipError_t e;
-  if ((gemm_prec == RRT_COMPUTE_BF16 || gemm_prec == RRT_COMPUTE_F16) && desc->input_dim % 64 == 0) {
-    char* tail = enc_ws + align_up(enc_bytes, 256) + align_up(cws.bytes, 256);
-    uint16_t* x16 = (uint16_t*)tail;
-    uint16_t* w16 = (uint16_t*)(tail + align_up((size_t)n_tokens * desc->input_dim * 2, 256));
-    y16 = (uint16_t*)((char*)w16 + align_up((size_t)D * desc->input_dim * 2, 256));
-    pa16 = (uint16_t*)((char*)y16 + align_up((size_t)n_tokens * D * 2, 256));
-    pb16 = (uint16_t*)((char*)pa16 + align_up((size_t)H * D * 2, 256));
-    Cast16Jobs cj{};
-    cj.src[0] = x; cj.dst[0] = x16; cj.n4[0] = (size_t)n_tokens * desc->input_dim / 4;
-    cj.src[1] = w->emb_w; cj.dst[1] = w16; cj.n4[1] = (size_t)D * desc->input_dim / 4;
-    cj.count = 2;
-    // the gate Linears' weights in the same launch: their 16-bit-operand product reads the encoder's y16
-    pool16 = desc->has_rrt && D % 64 == 0 && ((size_t)H * D) % 4 == 0;
-    if (pool16) {
-      cj.src[cj.count] = w->a_w; cj.dst[cj.count] = pa16; cj.n4[cj.count++] = (size_t)H * D / 4;
-      if (desc->gated) {
-        cj.src[cj.count] = w->b_w; cj.dst[cj.count] = pb16; cj.n4[cj.count++] = (size_t)H * D / 4;
-      }
-    }
-    e = launch_cast16(cj, gemm_prec, st);
-    if (e != hipSuccess) return (int)e;
-    e = launch_linear16(x16, w16, emb, (int)n_tokens, D, desc->input_dim, ep, st);
-  } else {
-    e = launch_linear(x, w->emb_w, emb, (int)n_tokens, D, desc->input_dim, ep, st);
-  }
-  if (e != hipSuccess) return (int)e;
-  if (desc->has_rrt) {
-    rc = encoder_forward(&desc->enc, &w->enc, emb, y, n_tokens, enc_ws, enc_bytes, stream, nullptr, nullptr, nullptr,
-                         pool16 ? y16 : nullptr, &y16_done);
-    if (rc) return rc;
-  }
-  const bool p16 = pool16 && y16_done;
+  ep.prec = gemm_precision(desc->enc.compute);
   ep.bias = w->a_b;
   ep.act = RRT_ACT_TANH;
-  e = p16 ? launch_linear16(y16, pa16, cws.hid_a, (int)n_tokens, H, D, ep, st)
-          : launch_linear(y, w->a_w, cws.hid_a, (int)n_tokens, H, D, ep, st);
+  hipError_t e = p16 ? launch_linear16(hw.y16, hw.pa16, cws.hid_a, (int)n_tokens, H, D, ep, st)
+                     : launch_linear(y, w->a_w, cws.hid_a, (int)n_tokens, H, D, ep, st);
   if (e != hipSuccess) return (int)e;
   if (desc->gated) {
     ep.bias = w->b_b;
     ep.act = RRT_ACT_SIGMOID;
-    e = p16 ? launch_linear16(y16, pb16, cws.hid_b, (int)n_tokens, H, D, ep, st)
+    e = p16 ? launch_linear16(hw.y16, hw.pb16, cws.hid_b, (int)n_tokens, H, D, ep, st)
             : launch_linear(y, w->b_w, cws.hid_b, (int)n_tokens, H, D, ep, st);
     if (e != hipSuccess) return (int)e;
   }
@@ -1969,22 +1995,14 @@ int rrt_dsmil_pool_f32(const float* feats, const int64_t* argmax, const float* q
                                 ws.v, ws.vb, ws.lpart, ws.part, (int)n_tokens, dim, q_dim, n_classes, (hipStream_t)stream);
 }
 
-static size_t dsmil_act_bytes(const rrt_dsmil_desc* d, int64_t N) { return align_up((size_t)N * d->enc.dim * sizeof(float), 256); }
-
 int rrt_dsmil_workspace_size(const rrt_dsmil_desc* desc, int64_t n_tokens, size_t* bytes) {
   if (!bytes) return RRT_E_INVALID;
   int rc = check_dsmil(desc, n_tokens);
   if (rc) return rc;
-  size_t enc = 0;
-  if (desc->has_rrt) {
-    rc = rrt_encoder_workspace_size(&desc->enc, n_tokens, &enc);
-    if (rc) return rc;
-  }
-  const int D = desc->enc.dim, K = desc->n_classes;
-  // (the 16-bit images of patch_to_emb's operands are part of the size in every mode, as in rrt_clam_workspace_size)
-  *bytes = 2 * dsmil_act_bytes(desc, n_tokens) + align_up(enc, 256) + align_up(carve_imax(n_tokens, K, nullptr).bytes, 256) +
-           align_up(carve_dsmil_pool(n_tokens, D, K, nullptr).bytes, 256) + 256 /* arg-max [8] + class maxima [8] */ +
-           align_up((size_t)n_tokens * desc->input_dim * 2, 256) + align_up((size_t)D * desc->input_dim * 2, 256);
+  HeadWs hw;
+  rc = carve_dsmil_head(desc, n_tokens, nullptr, &hw, nullptr);
+  if (rc) return rc;
+  *bytes = hw.bytes;
   return RRT_OK;
 }
 
@@ -1995,61 +2013,26 @@ int rrt_dsmil_forward_f32(const rrt_dsmil_desc* desc, const rrt_dsmil_weights* w
   int rc = check_dsmil(desc, n_tokens);
   if (rc) return rc;
   if (!w->emb_w || !w->icls_w || !w->q_w || !w->fcc_w) return RRT_E_INVALID;
-  size_t need = 0, enc_bytes = 0;
-  rc = rrt_dsmil_workspace_size(desc, n_tokens, &need);
+  HeadWs hw;
+  DsmilHeadWs ds;
+  rc = carve_dsmil_head(desc, n_tokens, (char*)workspace, &hw, &ds);
   if (rc) return rc;
-  if (!workspace || workspace_bytes < need) return RRT_E_WORKSPACE;
-  if (desc->has_rrt) {
-    rc = rrt_encoder_workspace_size(&desc->enc, n_tokens, &enc_bytes);
-    if (rc) return rc;
-  }
+  if (!workspace || workspace_bytes < hw.bytes) return RRT_E_WORKSPACE;
   const int D = desc->enc.dim, K = desc->n_classes;
-  const size_t act = dsmil_act_bytes(desc, n_tokens);
-  char* base = (char*)workspace;
-  float* emb = (float*)base;                                   // feats: the bag stream reads it AFTER the encoder has run
-  float* y = desc->has_rrt ? (float*)(base + act) : emb;
-  char* enc_ws = base + 2 * act;
-  char* p = enc_ws + align_up(enc_bytes, 256);
-  IMaxWs iws = carve_imax(n_tokens, K, p);
-  p += align_up(iws.bytes, 256);
-  DsmilWs dws = carve_dsmil_pool(n_tokens, D, K, p);
-  p += align_up(dws.bytes, 256);
-  long long* am = argmax ? (long long*)argmax : (long long*)p;
-  float* cm = classes_max ? classes_max : (float*)(p + 64);
-  p += 256;
+  long long* am = argmax ? (long long*)argmax : ds.argmax;
+  float* cm = classes_max ? classes_max : ds.cmax;
   hipStream_t st = (hipStream_t)stream;
-
-  // patch_to_emb follows enc.compute exactly as in rrt_clam_forward_f32 (F32X3: exact fp32 here); everything behind the
-  // encoder -- instance classifier, q, scores, softmax, pooling, fcc -- is fp32 in every mode: a 16-bit instance score
-  // could pick another critical instance
-  const int gemm_prec = desc->enc.compute == RRT_COMPUTE_F32X3 ? RRT_COMPUTE_F32 : desc->enc.compute;
-  LinearEpilogue ep{};
-  ep.prec = gemm_prec;
-  ep.bias = w->emb_b;
-  ep.act = desc->emb_act;
-  hipError_t e;
-  if ((gemm_prec == RRT_COMPUTE_BF16 || gemm_prec == RRT_COMPUTE_F16) && desc->input_dim % 64 == 0) {
-    uint16_t* x16 = (uint16_t*)p;
-    uint16_t* w16 = (uint16_t*)(p + align_up((size_t)n_tokens * desc->input_dim * 2, 256));
-    Cast16Jobs cj{};
-    cj.src[0] = x; cj.dst[0] = x16; cj.n4[0] = (size_t)n_tokens * desc->input_dim / 4;
-    cj.src[1] = w->emb_w; cj.dst[1] = w16; cj.n4[1] = (size_t)D * desc->input_dim / 4;
-    cj.count = 2;
-    e = launch_cast16(cj, gemm_prec, st);
-    if (e != hipSuccess) return (int)e;
-    e = launch_linear16(x16, w16, emb, (int)n_tokens, D, desc->input_dim, ep, st);
-  } else {
-    e = launch_linear(x, w->emb_w, emb, (int)n_tokens, D, desc->input_dim, ep, st);
-  }
+  // patch_to_emb follows enc.compute; everything behind the encoder -- instance classifier, q, scores, softmax, pooling,
+  // fcc -- is fp32 in every mode: a 16-bit instance score could pick another critical instance
+  bool p16 = false;
+  rc = head_front_forward(head_front(desc), hw, x, w->emb_w, w->emb_b, &w->enc, nullptr, nullptr, 0, nullptr, /*tuning=*/false,
+                          n_tokens, stream, &p16);
+  if (rc) return rc;
+  hipError_t e = launch_instance_max(hw.y, w->icls_w, w->icls_b, nullptr, cm, am, ds.imax.pv, ds.imax.pi, (int)n_tokens, D, K, st);
   if (e != hipSuccess) return (int)e;
-  if (desc->has_rrt) {
-    rc = encoder_forward(&desc->enc, &w->enc, emb, y, n_tokens, enc_ws, enc_bytes, stream, nullptr);
-    if (rc) return rc;
-  }
-  e = launch_instance_max(y, w->icls_w, w->icls_b, nullptr, cm, am, iws.pv, iws.pi, (int)n_tokens, D, K, st);
-  if (e != hipSuccess) return (int)e;
-  return (int)launch_dsmil_pool(emb, am, w->q_w, w->q_b, w->fcc_w, w->fcc_b, logits, A, B, dws.raw, dws.v, dws.vb, dws.lpart,
-                                dws.part, (int)n_tokens, D, desc->q_dim, K, st);
+  // (feats = the embedding: the bag stream reads it AFTER the encoder has run)
+  return (int)launch_dsmil_pool(hw.emb, am, w->q_w, w->q_b, w->fcc_w, w->fcc_b, logits, A, B, ds.pool.raw, ds.pool.v, ds.pool.vb,
+                                ds.pool.lpart, ds.pool.part, (int)n_tokens, D, desc->q_dim, K, st);
 }
 
 }  // extern "C"
@@ -2449,52 +2432,47 @@ struct Stash {
 
 Stash carve_stash(const rrt_encoder_desc& d, int64_t N, const rrt_grid& g, const rrt_grid& g8, char* base) {
   Stash s{};
-  size_t off = 0;
-  auto take = [&](size_t nfloat) {
-    float* p = base ? (float*)(base + off) : nullptr;
-    off = align_up(off + nfloat * sizeof(float), 256);
-    return p;
-  };
+  Arena a{base};
   const size_t D = d.dim, Np = (size_t)g.H * g.H, Np8 = (size_t)g8.H * g8.H;
   const size_t R8 = (size_t)g8.regions_side * g8.regions_side, k = d.crmsa_k;
   for (int l = 0; l < d.n_rmsa_layers; ++l) {
-    s.u[l] = take(Np * D);
-    s.qkv[l] = take(Np * 3 * D);
-    s.o[l] = take(Np * D);
-    s.xout[l] = take((size_t)N * D);
-    if (d.epeg && d.epeg_type != RRT_EPEG_ATTN) s.pe[l] = take(Np * D);
+    s.u[l] = a.take(Np * D);
+    s.qkv[l] = a.take(Np * 3 * D);
+    s.o[l] = a.take(Np * D);
+    s.xout[l] = a.take((size_t)N * D);
+    if (d.epeg && d.epeg_type != RRT_EPEG_ATTN) s.pe[l] = a.take(Np * D);
   }
   if (d.n_rmsa_layers > 0 && d.epeg && d.epeg_2d && d.epeg_type == RRT_EPEG_ATTN) {
     const size_t sm = attn_scoremap_scratch_floats(g.regions_side * g.regions_side, g.s * g.s, d.n_heads, d.epeg_k, 1);
-    if (sm) s.smap = take(sm);
+    if (sm) s.smap = a.take(sm);
   }
   if (d.cr_msa) {
-    s.mean_rstd = take((size_t)N * 2);
-    s.logits = take(Np8 * k);
-    s.wdisp = take(Np8 * k);
-    s.rep = take(k * R8 * D);
-    s.rep_qkv = take(k * R8 * 3 * D);
-    s.rep_o = take(k * R8 * D);
-    s.rep2 = take(k * R8 * D);
+    s.mean_rstd = a.take((size_t)N * 2);
+    s.logits = a.take(Np8 * k);
+    s.wdisp = a.take(Np8 * k);
+    s.rep = a.take(k * R8 * D);
+    s.rep_qkv = a.take(k * R8 * 3 * D);
+    s.rep_o = a.take(k * R8 * D);
+    s.rep2 = a.take(k * R8 * D);
     if (d.crmsa_mlp) {
-      s.v8 = take(Np8 * D);
-      s.hid = take(Np8 * (D / 4));
+      s.v8 = a.take(Np8 * D);
+      s.hid = a.take(Np8 * (D / 4));
     }
   }
-  s.x2 = take((size_t)N * D);
+  s.x2 = a.take((size_t)N * D);
   if (d.ffn) {
     const int nl = d.n_rmsa_layers + (d.cr_msa ? 1 : 0);
     for (int l = 0; l < nl; ++l) {
       const int idx = l < d.n_rmsa_layers ? l : RRT_MAX_RMSA_LAYERS;
-      s.ffn_u[idx] = take((size_t)N * D);
-      s.ffn_hpre[idx] = take((size_t)N * d.ffn_hidden);
-      s.xf[idx] = take((size_t)N * D);
+      s.ffn_u[idx] = a.take((size_t)N * D);
+      s.ffn_hpre[idx] = a.take((size_t)N * d.ffn_hidden);
+      s.xf[idx] = a.take((size_t)N * D);
     }
-    if (d.cr_msa) s.xcr = take((size_t)N * D);
-    s.hscr = take((size_t)N * d.ffn_hidden);
+    if (d.cr_msa) s.xcr = a.take((size_t)N * D);
+    s.hscr = a.take((size_t)N * d.ffn_hidden);
   }
-  if (d.pos) s.xp = take((size_t)N * D);
-  s.bytes = off;
+  if (d.pos) s.xp = a.take((size_t)N * D);
+  s.bytes = a.bytes();
   return s;
 }
 
@@ -2510,85 +2488,79 @@ struct BwdWs {
 
 BwdWs carve_bwd(const rrt_encoder_desc& d, int64_t N, const rrt_grid& g, const rrt_grid& g8, char* base) {
   BwdWs w{};
-  size_t off = 0;
-  auto takeb = [&](size_t nbytes) {
-    char* p = base ? base + off : nullptr;
-    off = align_up(off + nbytes, 256);
-    return p;
-  };
-  auto take = [&](size_t nfloat) { return (float*)takeb(nfloat * sizeof(float)); };
+  Arena a{base};
   const size_t D = d.dim, Np = (size_t)g.H * g.H, Np8 = (size_t)g8.H * g8.H;
   const size_t R8 = (size_t)g8.regions_side * g8.regions_side, k = d.crmsa_k;
-  w.dx2 = take((size_t)N * D);
-  w.dxa = take((size_t)N * D);
-  w.dxb = take((size_t)N * D);
+  w.dx2 = a.take((size_t)N * D);
+  w.dxa = a.take((size_t)N * D);
+  w.dxb = a.take((size_t)N * D);
   w.lnpart_stride = align_up(ln_bwd_workspace((int)D), 256) / sizeof(float);
-  w.lnpart = take(w.lnpart_stride * (size_t)(2 * (d.n_rmsa_layers + 1) + 1));      // final + (norm, norm2) per layer + CR-MSA's norm2
+  w.lnpart = a.take(w.lnpart_stride * (size_t)(2 * (d.n_rmsa_layers + 1) + 1));      // final + (norm, norm2) per layer + CR-MSA's norm2
   size_t lin = 0;
   if (d.n_rmsa_layers > 0) {
-    w.dz = take(Np * D);
-    w.dO = take(Np * D);
-    w.dqkv = take(Np * 3 * D);
+    w.dz = a.take(Np * D);
+    w.dO = a.take(Np * D);
+    w.dqkv = a.take(Np * 3 * D);
     const int R = g.regions_side * g.regions_side;
     const bool e2d = d.epeg && d.epeg_2d && d.epeg_type == RRT_EPEG_ATTN, evalue = d.epeg && d.epeg_type != RRT_EPEG_ATTN;
     if (e2d) {       // 2-D 'attn' EPEG: its own backward kernel (three [P, P] maps per (region, head) + the tap partials)
-      w.smap = take(attn_scoremap_scratch_floats(R, g.s * g.s, d.n_heads, d.epeg_k, 3) + (size_t)R * d.n_heads * d.epeg_k * d.epeg_k);
-      w.attnpart = take(64);
+      w.smap = a.take(attn_scoremap_scratch_floats(R, g.s * g.s, d.n_heads, d.epeg_k, 3) + (size_t)R * d.n_heads * d.epeg_k * d.epeg_k);
+      w.attnpart = a.take(64);
     } else {
-      w.attnpart = take(attn_bwd_workspace(R, g.s * g.s, (int)D, d.n_heads, (d.epeg && !evalue) ? d.epeg_k : 0) / sizeof(float));
+      w.attnpart = a.take(attn_bwd_workspace(R, g.s * g.s, (int)D, d.n_heads, (d.epeg && !evalue) ? d.epeg_k : 0) / sizeof(float));
       if (d.epeg && !evalue)
-        for (int li = 0; li < d.n_rmsa_layers; ++li) w.tappart[li] = take((size_t)R * d.n_heads * d.epeg_k);
+        for (int li = 0; li < d.n_rmsa_layers; ++li) w.tappart[li] = a.take((size_t)R * d.n_heads * d.epeg_k);
     }
-    if (evalue) w.dpe = take(Np * D);
+    if (evalue) w.dpe = a.take(Np * D);
     lin = linear_bwd_workspace((int)Np, 3 * (int)D, (int)D);
     const size_t l2 = linear_bwd_workspace((int)Np, (int)D, (int)D);
     if (l2 > lin) lin = l2;
   }
   if (d.cr_msa) {
-    w.dWd = take(Np8 * k);
-    w.dC = take(Np8 * k);
-    w.dlg = take(Np8 * k);
-    w.Cw = take(Np8 * k);
-    w.d_rep2 = take(k * R8 * D);
-    w.d_rep_o = take(k * R8 * D);
-    w.d_rep_qkv = take(k * R8 * 3 * D);
-    w.d_rep = take(k * R8 * D);
-    w.rows = take((2 + k) * D);
-    w.dxpart = take(crmsa_bwd_dx_workspace((int)D, (int)k) / sizeof(float));
+    w.dWd = a.take(Np8 * k);
+    w.dC = a.take(Np8 * k);
+    w.dlg = a.take(Np8 * k);
+    w.Cw = a.take(Np8 * k);
+    w.d_rep2 = a.take(k * R8 * D);
+    w.d_rep_o = a.take(k * R8 * D);
+    w.d_rep_qkv = a.take(k * R8 * 3 * D);
+    w.d_rep = a.take(k * R8 * D);
+    w.rows = a.take((2 + k) * D);
+    w.dxpart = a.take(crmsa_bwd_dx_workspace((int)D, (int)k) / sizeof(float));
     if (d.crmsa_mlp) {
-      w.th = take(Np8 * (D / 4));
-      w.dhid = take(Np8 * (D / 4));
-      w.dvphi = take(Np8 * D);
-      w.w1t = take(D * (D / 4));
+      w.th = a.take(Np8 * (D / 4));
+      w.dhid = a.take(Np8 * (D / 4));
+      w.dvphi = a.take(Np8 * D);
+      w.w1t = a.take(D * (D / 4));
       const size_t a1 = linear_bwd_workspace((int)Np8, (int)(D / 4), (int)D);     // dW1 partials dominate
       const size_t a2 = linear_bwd_workspace((int)Np8, (int)k, (int)(D / 4));
-      w.tnscratch = take((a1 > a2 ? a1 : a2) / sizeof(float));
+      w.tnscratch = a.take((a1 > a2 ? a1 : a2) / sizeof(float));
     }
     // attnpart is shared by the R-MSA layers' and CR-MSA's attention backward: the larger of the two geometries
     // (a small bag's R-MSA partials can be smaller than what CR-MSA's 64-token regions need)
-    w.attnpart_cr = take(attn_bwd_workspace((int)k, (int)R8, (int)D, d.crmsa_heads, 0) / sizeof(float));
+    w.attnpart_cr = a.take(attn_bwd_workspace((int)k, (int)R8, (int)D, d.crmsa_heads, 0) / sizeof(float));
     const size_t l3 = linear_bwd_workspace((int)(k * R8), 3 * (int)D, (int)D);
     if (l3 > lin) lin = l3;
   }
   if (d.ffn) {
-    w.fh = take((size_t)N * d.ffn_hidden);
-    w.fdh = take((size_t)N * d.ffn_hidden);
-    w.fdu = take((size_t)N * D);
+    w.fh = a.take((size_t)N * d.ffn_hidden);
+    w.fdh = a.take((size_t)N * d.ffn_hidden);
+    w.fdu = a.take((size_t)N * D);
     const size_t f1 = linear_bwd_workspace((int)N, (int)D, d.ffn_hidden), f2 = linear_bwd_workspace((int)N, d.ffn_hidden, (int)D);
     if (f1 > lin) lin = f1;
     if (f2 > lin) lin = f2;
   }
-  w.lin = takeb(lin ? lin : 256);
-  if (d.pos) w.pegws = takeb(peg_bwd_workspace((int)N, (int)D, d.peg_k, d.pos == RRT_POS_PPEG));
+  w.lin = a.take<char>(lin ? lin : 256);
+  if (d.pos) w.pegws = a.take<char>(peg_bwd_workspace((int)N, (int)D, d.peg_k, d.pos == RRT_POS_PPEG));
   for (int li = 0; li < d.n_rmsa_layers; ++li) {
-    w.wt_qkv[li] = take(3 * D * D);
-    w.wt_proj[li] = take(D * D);
+    w.wt_qkv[li] = a.take(3 * D * D);
+    w.wt_proj[li] = a.take(D * D);
   }
   if (d.cr_msa) {
-    w.wt_cr_qkv = take(3 * D * D);
-    w.wt_cr_proj = take(D * D);
+    w.wt_cr_qkv = a.take(3 * D * D);
+    w.wt_cr_proj = a.take(D * D);
   }
-  w.bytes = off;
+  w.bytes = a.bytes();
   return w;
 }
 
@@ -3061,24 +3033,19 @@ NystromWs carve_nystrom(const rrt_nystrom_desc* d, int64_t n, char* base) {
   NystromWs ws{};
   const int64_t np = (n + 255) / 256 * 256;
   const size_t hd = (size_t)d->heads * 64, lm = (size_t)d->heads * 256 * 64, mm = (size_t)d->heads * 256 * 256;
-  size_t off = 0;
-  auto take = [&](size_t floats) {
-    float* p = (float*)(base + off);
-    off += align_up(floats * sizeof(float), 256);
-    return p;
-  };
+  Arena a{base};
   ws.np = np;
-  ws.qkv = take((size_t)np * 3 * hd);
-  ws.ql = take(lm);
-  ws.kl = take(lm);
-  ws.a2 = take(mm);
-  ws.z = take(mm);
-  ws.av = take(lm);
-  ws.wz = take(lm);
-  ws.o = take((size_t)np * hd);
-  ws.lattn = take(nystrom_lattn_floats((long)np, d->heads));
-  ws.pinv = take(nystrom_pinv_floats(d->heads));
-  ws.bytes = off;
+  ws.qkv = a.take((size_t)np * 3 * hd);
+  ws.ql = a.take(lm);
+  ws.kl = a.take(lm);
+  ws.a2 = a.take(mm);
+  ws.z = a.take(mm);
+  ws.av = a.take(lm);
+  ws.wz = a.take(lm);
+  ws.o = a.take((size_t)np * hd);
+  ws.lattn = a.take(nystrom_lattn_floats((long)np, d->heads));
+  ws.pinv = a.take(nystrom_pinv_floats(d->heads));
+  ws.bytes = a.bytes();
   return ws;
 }
 
@@ -3139,20 +3106,14 @@ TransmilWs carve_transmil(const rrt_transmil_desc* d, int64_t N, char* base) {
   ws.side = ceil_sqrt_i64(N);
   ws.rows = 1 + (int64_t)ws.side * ws.side;
   const size_t D = (size_t)d->attn.dim;
-  size_t off = 0;
-  auto take = [&](size_t floats) {
-    float* p = (float*)(base + off);
-    off += align_up(floats * sizeof(float), 256);
-    return p;
-  };
-  ws.emb = take((size_t)N * D);
-  ws.seq = take((size_t)ws.rows * D);
-  ws.seq2 = take((size_t)ws.rows * D);
-  ws.ln = take((size_t)ws.rows * D);
-  ws.att = take((size_t)ws.rows * D);
-  ws.nys = base + off;
-  off += carve_nystrom(&d->attn, ws.rows, nullptr).bytes;
-  ws.bytes = off;
+  Arena a{base};
+  ws.emb = a.take((size_t)N * D);
+  ws.seq = a.take((size_t)ws.rows * D);
+  ws.seq2 = a.take((size_t)ws.rows * D);
+  ws.ln = a.take((size_t)ws.rows * D);
+  ws.att = a.take((size_t)ws.rows * D);
+  ws.nys = a.take<char>(carve_nystrom(&d->attn, ws.rows, nullptr).bytes);
+  ws.bytes = a.bytes();
   return ws;
 }
 

@@ -24,7 +24,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from .clam import CLAM_SB, _BranchPool
+from ._head import HeadState, head_compute
+from .clam import _BranchPool
 from .encoder import RRTEncoder
 from .mil import lib_linear
 
@@ -110,7 +111,7 @@ class _InstanceMax(torch.autograd.Function):
         return dy, d_cmax[:, None] * ym, (d_cmax if ctx.has_bias else None)
 
 
-class MILNet(nn.Module):
+class MILNet(HeadState, nn.Module):
     """modules/dsmil.py:96-135.  ``rrt``: an rrt_mil_amd.RRTEncoder of width 512, or None.
 
     ``forward(x, label=None, loss=None)`` returns what the reference returns: ``(prediction_bag [1, C], classes_max [C])`` in
@@ -141,28 +142,12 @@ class MILNet(nn.Module):
         self._has_dropout = dropout > 0.
         self._ws = None
 
-    def __getstate__(self):          # device workspaces and their validity keys stay with the process (deepcopy / pickle)
-        st = dict(self.__dict__)
-        for k in ("_ws", "_slots", "_w16_key"):
-            st.pop(k, None)
-        return st
-
-    def __setstate__(self, st):
-        self.__dict__.update(st)
-        self.__dict__.setdefault("_ws", None)
-
     # ------------------------------------------------------------------ pieces
     def _enc(self):
         return self.rrt if isinstance(self.rrt, RRTEncoder) else None
 
     def _compute(self):
-        enc = self._enc()
-        if enc is not None:
-            return enc._compute_mode()
-        if torch.is_autocast_enabled("cuda"):
-            return {torch.bfloat16: _lib.COMPUTE_BF16, torch.float16: _lib.COMPUTE_F16}.get(torch.get_autocast_dtype("cuda"),
-                                                                                             _lib.COMPUTE_F32)
-        return _lib.COMPUTE_F32
+        return head_compute(self._enc())
 
     def _stochastic(self):
         enc = self._enc()
@@ -192,7 +177,6 @@ class MILNet(nn.Module):
         rrt_dsmil_forward_f32 call, plus what was asked for: attn (N, C) (the reference's A), features (C, 512) (its B),
         critical (C,) int64 (the critical instances).  ``solo``: the slide has the GPU to itself (forward_bags passes False
         with several slides in flight)."""
-        lib = _lib.load()
         if not x2d.is_cuda:
             raise _lib.RRTHipError("rrt_mil_amd.MILNet runs on MI355X only: move the bag to a 'cuda' (HIP) device; there is "
                                    "no CPU fallback")
@@ -204,11 +188,7 @@ class MILNet(nn.Module):
             raise ValueError(f"expected feature dim {self.patch_to_emb[0].in_features}, got {in_dim}")
         x2d = x2d.float().contiguous()
         d, w = self._desc_weights(in_dim, solo)
-        need = C.c_size_t()
-        _lib.check(lib.rrt_dsmil_workspace_size(C.byref(d), n, C.byref(need)), "rrt_dsmil_workspace_size")
         dev = x2d.device
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < need.value:
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
         nc = self.n_classes
         new = lambda *s, dt=torch.float32: torch.empty(s, dtype=dt, device=dev)   # noqa: E731
         logits, cmax = new(1, nc), new(nc)
@@ -216,27 +196,22 @@ class MILNet(nn.Module):
         feat = new(nc, 512) if return_features else None
         crit = new(nc, dt=torch.int64) if return_critical else None
         p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            # reduced-precision modes: are the encoder's 16-bit weight images inside this workspace still those of these
-            # weights?  (rrt_encoder_desc.weights16_valid, see RRTMIL.forward_bag)
-            key = (self._ws.data_ptr(), d.enc.compute, w.enc.version, stream, n)
-            lowp = d.enc.compute != _lib.COMPUTE_F32 and d.has_rrt
-            d.enc.weights16_valid = int(lowp and key == self.__dict__.get("_w16_key"))
-            rc = lib.rrt_dsmil_forward_f32(C.byref(d), C.byref(w), x2d.data_ptr(), logits.data_ptr(), cmax.data_ptr(), p(attn),
-                                           p(feat), p(crit), n, self._ws.data_ptr(), self._ws.numel(), stream)
-            self.__dict__["_w16_key"] = key if rc == 0 and lowp else None
-        _lib.check(rc, "rrt_dsmil_forward_f32")
+        self._head_forward("dsmil", d, w, x2d, (logits.data_ptr(), cmax.data_ptr(), p(attn), p(feat), p(crit)),
+                           d.enc.compute != _lib.COMPUTE_F32 and d.has_rrt)
         return {k: v for k, v in (("logits", logits), ("classes_max", cmax), ("attn", attn), ("features", feat),
                                   ("critical", crit)) if v is not None}
 
     def forward_bags(self, bags, streams=4, **kw):
         """A batch of independent slides (each (N_i, input_dim) or (1, N_i, input_dim)) -> list of forward_bag results, with
-        ``streams`` slides in flight on the process's bag streams: the CLAM heads' scheduler (one rrt_dsmil_forward_f32 call
+        ``streams`` slides in flight on the heads' bag scheduler (HeadState._schedule_bags: one rrt_dsmil_forward_f32 call
         per slide with its own workspace), bit for bit forward_bag(..., solo=False) per bag."""
-        if bags and not bags[0].is_cuda:
+        if not bags:
+            return []
+        if not bags[0].is_cuda:
             raise _lib.RRTHipError("rrt_mil_amd.MILNet runs on MI355X only; there is no CPU fallback")
-        return CLAM_SB.forward_bags(self, bags, streams=streams, **kw)
+        if self._stochastic():
+            raise NotImplementedError("forward_bags is an inference entry; in train() call the module itself")
+        return self._schedule_bags(bags, streams, lambda x2, solo: self.forward_bag(x2, solo=solo, **kw), lambda o: o.values())
 
     # ------------------------------------------------------------------ the layer path (graph, dropout, eager comparison)
     def _embed(self, x2d):

@@ -19,6 +19,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
+from ._head import HeadState
 from .encoder import RRTEncoder, initialize_weights
 
 
@@ -224,7 +225,7 @@ class DAttention(nn.Module):
         return (x.squeeze(1), attn.squeeze(1)) if return_attn else x.squeeze(1)
 
 
-class RRTMIL(nn.Module):
+class RRTMIL(HeadState, nn.Module):
     def __init__(self, input_dim=1024, mlp_dim=512, act='relu', n_classes=2, dropout=0.25, pos_pos=0,
                  pos='none', peg_k=7, attn='rmsa', pool='attn', region_num=8, n_layers=2, n_heads=8,
                  drop_path=0., da_act='relu', trans_dropout=0.1, ffn=False, ffn_act='gelu', mlp_ratio=4.,
@@ -258,16 +259,6 @@ class RRTMIL(nn.Module):
         self._act_name = act.lower() if act.lower() in ("relu", "gelu") else "none"
         self._da_act = da_act
         self._ws = None
-
-    def __getstate__(self):          # device workspaces and their validity keys stay with the process (deepcopy / pickle)
-        st = dict(self.__dict__)
-        for k in ("_ws", "_slots", "_w16_key"):
-            st.pop(k, None)
-        return st
-
-    def __setstate__(self, st):
-        self.__dict__.update(st)
-        self.__dict__.setdefault("_ws", None)
 
     # ------------------------------------------------------------------ the one-call HIP path
     def _mil_desc(self, input_dim, solo=True):
@@ -313,58 +304,25 @@ class RRTMIL(nn.Module):
         """A batch of independent slides (each (N_i, input_dim) or (1, N_i, input_dim), any mix of sizes) -> list of logits
         [(n_classes,) or (1, n_classes)] (and attention rows with return_attn): the reference's validation loop
         ``for bag in loader: model(bag)`` (main.py:466-467) with ``streams`` slides in flight -- each slide is one
-        rrt_mil_forward_f32 call with its own workspace on one of the process's bag streams (the same list
-        RRTEncoder.forward_bags uses; at most four: the chip schedules four hardware queues).  Ordered like one op of the
-        caller's stream: the bag streams wait for it, and the host waits for them before the call returns (the call BLOCKS
-        the host; it swaps the module's workspace per stream slot while it runs, so one call at a time per module: not
-        re-entrant, not thread-safe)."""
+        rrt_mil_forward_f32 call on the heads' bag scheduler (HeadState._schedule_bags: the call BLOCKS the host; one call at
+        a time per module)."""
         if not bags:
             return []
         if self.training and (isinstance(self.dp, nn.Dropout) or self.online_encoder._stochastic()):
             return [self(b if b.dim() == 3 else b.unsqueeze(0), return_attn=return_attn, no_norm=no_norm) for b in bags]
-        from .encoder import _BAG_STREAMS
-        dev = bags[0].device
         if not bags[0].is_cuda:
             raise _lib.RRTHipError("rrt_mil_amd.RRTMIL runs on MI355X only; there is no CPU fallback")
-        S = max(1, min(int(streams), 4, len(bags)))
-        pool = _BAG_STREAMS.setdefault(dev, [])
-        while len(pool) < S:
-            pool.append(torch.cuda.Stream(dev))
-        slots = self.__dict__.setdefault("_slots", {})
-        cur = torch.cuda.current_stream(dev)
-        order = sorted(range(len(bags)), key=lambda i: -bags[i].shape[-2])        # big slides first, least loaded stream
-        load, outs = [0] * S, [None] * len(bags)
-        for st in pool[:S]:
-            st.wait_stream(cur)
-        ws_was, key_was = self._ws, self.__dict__.get("_w16_key")
-        try:
-            for i in order:
-                s_ = min(range(S), key=lambda t: load[t])
-                load[s_] += bags[i].shape[-2]
-                b = bags[i]
-                x2 = b[0] if b.dim() == 3 else b
-                self._ws, self.__dict__["_w16_key"] = slots.get((dev, s_), (None, None))
-                with torch.cuda.stream(pool[s_]):
-                    o = self.forward_bag(x2, return_attn=return_attn, no_norm=no_norm, solo=(S == 1))
-                slots[(dev, s_)] = (self._ws, self.__dict__.get("_w16_key"))
-                # the outputs were allocated under the bag stream (the caching allocator ties a block to the stream it was
-                # taken on) and are consumed on the caller's: tell the allocator, so that a freed logits / attention row
-                # is not handed out again on the bag stream while the caller's stream still reads it
-                for t_ in (o if return_attn else (o,)):
-                    t_.record_stream(cur)
-                if b.dim() == 3:
-                    o = tuple(t.unsqueeze(0) for t in o) if return_attn else o.unsqueeze(0)
-                outs[i] = o
-        finally:
-            self._ws, self.__dict__["_w16_key"] = ws_was, key_was
-            for st in pool[:S]:
-                st.synchronize()      # host wait: nothing is parked on the caller's stream (INTEGRATION.md section 4)
+        outs = self._schedule_bags(bags, streams,
+                                   lambda x2, solo: self.forward_bag(x2, return_attn=return_attn, no_norm=no_norm, solo=solo),
+                                   (lambda o: o) if return_attn else (lambda o: (o,)))
+        for i, b in enumerate(bags):
+            if b.dim() == 3:
+                outs[i] = tuple(t.unsqueeze(0) for t in outs[i]) if return_attn else outs[i].unsqueeze(0)
         return outs
 
     def forward_bag(self, x2d, return_attn=False, no_norm=False, solo=True):
         """One bag: x2d (N, input_dim) fp32 (or bf16 / fp16) device tensor -> logits (n_classes,) [, attention (N,)].
         ``solo``: the slide has the GPU to itself (forward_bags passes False when it keeps several slides in flight)."""
-        lib = _lib.load()
         if not x2d.is_cuda:
             raise _lib.RRTHipError("rrt_mil_amd.RRTMIL runs on MI355X only: move the bag to a 'cuda' (HIP) "
                                    "device; there is no CPU fallback")
@@ -389,24 +347,10 @@ class RRTMIL(nn.Module):
             raise NotImplementedError(f"unsupported bag dtype {x2d.dtype}")
         x2d = x2d.contiguous()
         w = self._mil_weights()
-        need = C.c_size_t()
-        _lib.check(lib.rrt_mil_workspace_size(C.byref(d), n, C.byref(need)), "rrt_mil_workspace_size")
-        if self._ws is None or self._ws.device != x2d.device or self._ws.numel() < need.value:
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=x2d.device)
         logits = torch.empty(d.n_classes, dtype=torch.float32, device=x2d.device)
         attn = torch.empty(n, dtype=torch.float32, device=x2d.device) if return_attn else None
-        with torch.cuda.device(x2d.device):      # kernels launch on the bag's device, whatever the current one is
-            stream = torch.cuda.current_stream(x2d.device).cuda_stream
-            # reduced-precision modes: the encoder's 16-bit weight images inside this workspace (their place depends on
-            # n) are still those of these weights?  (rrt_encoder_desc.weights16_valid, see RRTEncoder.forward_bag)
-            key = (self._ws.data_ptr(), d.enc.compute, w.enc.version, stream, n)
-            lowp = d.enc.compute != _lib.COMPUTE_F32
-            d.enc.weights16_valid = int(lowp and key == getattr(self, "_w16_key", None))
-            rc = lib.rrt_mil_forward_f32(C.byref(d), C.byref(w), x2d.data_ptr(), logits.data_ptr(),
-                                         attn.data_ptr() if return_attn else None, int(bool(no_norm)), None, n,
-                                         self._ws.data_ptr(), self._ws.numel(), stream)
-            self._w16_key = key if rc == 0 and lowp else None
-        _lib.check(rc, "rrt_mil_forward_f32")
+        self._head_forward("mil", d, w, x2d, (logits.data_ptr(), attn.data_ptr() if return_attn else None,
+                                              int(bool(no_norm)), None), d.enc.compute != _lib.COMPUTE_F32)
         return (logits, attn) if return_attn else logits
 
     def forward(self, x, return_attn=False, no_norm=False):

@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._head import HeadState
 
 
 def initialize_weights(module):
@@ -50,7 +51,7 @@ def _no_graph(module, x, who):
         raise NotImplementedError(f"rrt_mil_amd.{who} has no backward: call it in eval() under torch.no_grad()")
 
 
-class NystromAttention(nn.Module):
+class NystromAttention(HeadState, nn.Module):
     """modules/nystrom_attention.py:32-149.  ``forward(x)`` with x (1, n, dim) -> (1, n, dim); ``mask=`` and
     ``return_attn=True`` are not implemented (the reference's mask branch names undefined variables, and TransMIL passes
     neither).  The HIP path supports dim_head = 64, num_landmarks = 256, heads <= 16, pinv_iterations <= 16, an odd
@@ -75,15 +76,6 @@ class NystromAttention(nn.Module):
                                       groups=heads, bias=False)
         self._dropout = dropout
         self._ws = None
-
-    def __getstate__(self):          # the device workspace stays with the process (deepcopy / pickle)
-        st = dict(self.__dict__)
-        st.pop("_ws", None)
-        return st
-
-    def __setstate__(self, st):
-        self.__dict__.update(st)
-        self.__dict__.setdefault("_ws", None)
 
     def _desc(self):
         d = _lib.NystromDesc()
@@ -123,13 +115,12 @@ class NystromAttention(nn.Module):
         w = self._weights(keep)
         need = C.c_size_t()
         _lib.check(lib.rrt_nystrom_workspace_size(C.byref(d), n, C.byref(need)), "rrt_nystrom_workspace_size")
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < need.value:
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        ws = self._workspace(need.value, dev)
         y = torch.empty((n, self.dim), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(lib.rrt_nystrom_attention_f32(C.byref(d), C.byref(w), x2d.data_ptr(), y.data_ptr(), n,
-                                                     self._ws.data_ptr(), self._ws.numel(), st), "rrt_nystrom_attention_f32")
+                                                     ws.data_ptr(), ws.numel(), st), "rrt_nystrom_attention_f32")
         return y.unsqueeze(0)
 
 
@@ -153,7 +144,7 @@ class PPEG(nn.Module):
         self.proj2 = nn.Conv2d(dim, dim, 3, 1, 3 // 2, groups=dim)
 
 
-class TransMIL(nn.Module):
+class TransMIL(HeadState, nn.Module):
     """modules/transmil.py:64-125.  ``model(x)`` with x (1, N, input_dim) or (N, input_dim) -> logits (1, n_classes)."""
 
     def __init__(self, input_dim, n_classes, dropout, act):
@@ -177,15 +168,6 @@ class TransMIL(nn.Module):
         self.apply(initialize_weights)
         self._act = {"relu": _lib.ACT_RELU, "gelu": _lib.ACT_GELU}.get(act.lower(), _lib.ACT_NONE)
         self._ws = None
-
-    def __getstate__(self):
-        st = dict(self.__dict__)
-        st.pop("_ws", None)
-        return st
-
-    def __setstate__(self, st):
-        self.__dict__.update(st)
-        self.__dict__.setdefault("_ws", None)
 
     def _desc_weights(self, keep):
         d, w = _lib.TransmilDesc(), _lib.TransmilWeights()
@@ -227,9 +209,8 @@ class TransMIL(nn.Module):
         need = C.c_size_t()
         _lib.check(lib.rrt_transmil_workspace_size(C.byref(d), n, C.byref(need)), "rrt_transmil_workspace_size")
         dev = x2d.device
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < need.value:
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-        logits = torch.empty((1, self.n_classes), dtype=torch.float32, device=dev)
+        ws = self._workspace(need.value, dev)
+        logits =torch.empty((1, self.n_classes), dtype=torch.float32, device=dev)
         feat = None
         if return_features:
             side = _ceil_sqrt(n)
@@ -237,7 +218,7 @@ class TransMIL(nn.Module):
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(lib.rrt_transmil_forward_f32(C.byref(d), C.byref(w), x2d.data_ptr(), logits.data_ptr(), _ptr(feat), n,
-                                                    self._ws.data_ptr(), self._ws.numel(), st), "rrt_transmil_forward_f32")
+                                                    ws.data_ptr(), ws.numel(), st), "rrt_transmil_forward_f32")
         return (logits, feat) if return_features else logits
 
     def forward_bags(self, bags):

@@ -448,6 +448,31 @@ def test_clam_autocast_bf16():
     assert torch.equal(lo, lo2)
 
 
+@pytest.mark.parametrize("N", [33, 300])
+def test_clam_no_encoder_autocast_bf16(N):
+    """rrt=None under bf16 autocast: the heads' shared front runs the 16-bit embedding (cast launch + 16-bit-operand GEMM),
+    there is no encoder and the head reads the embedding itself (y == emb), its gate Linears on fp32 rows.  The one-call
+    forward against the reference's op sequence for the head (fp32 torch ops) behind the layer path's embedding, within
+    test_clam_autocast_bf16's bound; two calls give the same bits."""
+    torch.manual_seed(7)
+    m = CLAM_SB(input_dim=128, rrt=None).to(DEV).eval()
+    x = torch.from_numpy(synth.bag(N, 128, tag=f"clam/no_rrt_bf16/{N}", nonneg=True)).to(DEV)
+    with torch.no_grad():
+        f32 = m.forward_bag(x)
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            lo = m.forward_bag(x, return_features=True, return_attn=True)
+            lo2 = m.forward_bag(x, return_features=True, return_attn=True)
+            y = m._embed_encode(x)
+        eager, _M, _A, _raw = m._eager_head(y)
+    torch.cuda.synchronize()
+    assert lo["logits"].shape == (1, 2) and lo["attn"].shape == (1, N) and lo["features"].shape == (1, 512)
+    err = float((lo["logits"] - eager).abs().max())
+    print(f"N={N}: bf16 logits err vs eager head {err:.3e}; distance to the fp32 run {float((lo['logits'] - f32).abs().max()):.3e}")
+    assert err <= 2e-2
+    for k in lo:
+        assert torch.equal(lo[k], lo2[k]), k
+
+
 def test_clam_fails_loudly():
     m = CLAM_SB(64).to(DEV).eval()
     with pytest.raises(ValueError):

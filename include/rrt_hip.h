@@ -629,6 +629,80 @@ int rrt_dsmil_forward_f32(const rrt_dsmil_desc *desc, const rrt_dsmil_weights *w
                           float *classes_max, float *A, float *B, int64_t *argmax, int64_t n_tokens, void *workspace,
                           size_t workspace_bytes, void *stream);
 
+/* ---- ABMIL / gated ABMIL / IBMIL / MeanMIL / MaxMIL heads (modules/attmil.py, attmil_ibmil.py, mean_max.py with rrt=;
+ * exports added under ABI 29, no existing struct touched) ----
+ * Mean pool (mean_max.py:49-52, Linear(y).mean(1); the mean commutes with the Linear, so [N, C] never exists):
+ *     colmean[d] = (1/N) sum_n y[n, d]   [dim] (optional output, may be NULL; training stashes it),
+ *     logits[j] = w[j] . colmean + b[j]  [C].
+ * y [N, dim], w [C, dim], b [C] or NULL.  One pass over y, block partials merged in a fixed order (the same inputs give the
+ * same bits); a NaN propagates.  1 <= C <= 8, dim % 32 == 0, dim <= 2048, N <= 1e6, otherwise RRT_E_UNSUPPORTED.
+ * workspace: rrt_bag_mean_workspace_size bytes (one partial row per 32 rows of y, one per 64 of those). */
+int rrt_bag_mean_workspace_size(int64_t n_tokens, int32_t dim, int32_t n_classes, size_t *bytes);
+int rrt_bag_mean_f32(const float *y, const float *w, const float *b, float *logits, float *colmean, int64_t n_tokens,
+                     int32_t dim, int32_t n_classes, void *workspace, size_t workspace_bytes, void *stream);
+/* Its adjoint, from d_logits [C] and the stashed colmean [dim]: dy[n, :] = (1/N) sum_j d_logits[j] w[j] (one row, stored N
+ * times: the rows are bit-identical), dW[j] = d_logits[j] colmean, db = d_logits.  Any of dy / dW / db may be NULL
+ * (colmean is read for dW only).  The same limits; no workspace. */
+int rrt_bag_mean_backward_f32(const float *d_logits, const float *colmean, const float *w, float *dy, float *dW, float *db,
+                              int64_t n_tokens, int32_t dim, int32_t n_classes, void *stream);
+
+/* IBMIL's deconfounder tail (attmil_ibmil.py:90-101) on a pooled bag embedding that lives in device memory:
+ *     q = W_q pooled + b_q [J],  k_i = W_k conf_i + b_k [J],  a = softmax_i(k_i . q / sqrt(J)) over the K confounders,
+ *     cf = sum_i a_i conf_i [V],  logits = head [pooled | cf] + head_b [C].
+ * The scores are computed folded, k_i . q = conf_i . (W_k^T q) + b_k . q: k [K, J] is never formed.  pooled [dim],
+ * conf [K, V], q_w [J, dim], k_w [J, V], head_w [C, dim + V]; q_b, k_b, head_b may be NULL.  Optional outputs (NULL: not
+ * wanted): a [K], cf [V].  One block, fixed order.  1 <= K <= 64, dim and V multiples of 32 up to 2048 (512 in the
+ * reference), J % 4 == 0, J <= 512, C >= 1, otherwise RRT_E_UNSUPPORTED. */
+int rrt_deconf_head_f32(const float *pooled, const float *conf, const float *q_w, const float *q_b, const float *k_w,
+                        const float *k_b, const float *head_w, const float *head_b, float *logits, float *a, float *cf,
+                        int32_t dim, int32_t n_conf, int32_t conf_dim, int32_t joint_dim, int32_t n_classes, void *stream);
+
+/* One descriptor for the five heads: x [n_tokens, input_dim] -> Linear(input_dim, dim) + act (enc.compute's arithmetic, as
+ * CLAM's embedding) -> RRTEncoder (has_rrt) -> the pool -> logits [n_classes].
+ *   RRT_BAGPOOL_MEAN         logits = classifier(y).mean over the bag (rrt_bag_mean_f32)
+ *   RRT_BAGPOOL_MAX          logits[j] = max_n classifier(y)[n, j] (rrt_instance_max_f32: lowest index on ties, NaN never selected)
+ *   RRT_BAGPOOL_ATTN         ABMIL: Linear(dim, pool_hidden) + tanh -> Linear(pool_hidden, 1) -> softmax over the bag -> classifier
+ *   RRT_BAGPOOL_ATTN_GATED   the gated form: (Linear + pool_act) * (Linear + sigmoid) -> Linear(pool_hidden, 1) -> ...
+ *   RRT_BAGPOOL_ATTN_DECONF  ABMIL's pooled embedding -> rrt_deconf_head_f32 (cls_w is then [n_classes, dim + deconf_v])
+ * The mean and max tails are fp32 in every compute mode (a 16-bit instance score could select another instance); the
+ * attention tails follow enc.compute like rrt_mil_forward_f32. */
+enum { RRT_BAGPOOL_MEAN = 0, RRT_BAGPOOL_MAX = 1, RRT_BAGPOOL_ATTN = 2, RRT_BAGPOOL_ATTN_GATED = 3, RRT_BAGPOOL_ATTN_DECONF = 4 };
+
+typedef struct rrt_bagmil_desc {
+  rrt_encoder_desc enc;    /* has_rrt = 0: only dim (= 512 in the reference) and compute are read */
+  int32_t input_dim;       /* patch feature width (multiple of 32) */
+  int32_t emb_act;         /* RRT_ACT_NONE / RRT_ACT_RELU / RRT_ACT_GELU */
+  int32_t has_rrt;         /* 1: the encoder sits between the embedding and the pool */
+  int32_t n_classes;       /* MEAN / MAX: 1..8 */
+  int32_t pool;            /* RRT_BAGPOOL_* */
+  int32_t pool_hidden;     /* attention pools: 128 in the reference (multiple of 4) */
+  int32_t pool_act;        /* ATTN_GATED: RRT_ACT_NONE / RELU / GELU / TANH of attention_a; ATTN, ATTN_DECONF: tanh whatever is set */
+  int32_t deconf_k;        /* ATTN_DECONF: confounders K (1..64), their width V, the joint space J (128 in the reference) */
+  int32_t deconf_v;
+  int32_t deconf_j;
+} rrt_bagmil_desc;
+
+typedef struct rrt_bagmil_weights {
+  rrt_encoder_weights enc;
+  const float *emb_w, *emb_b;         /* the embedding Linear            [dim, input_dim], [dim] */
+  const float *a_w, *a_b;             /* attention pools: first Linear   [pool_hidden, dim], [pool_hidden] or NULL */
+  const float *b_w, *b_b;             /* ATTN_GATED: the gate's Linear   [pool_hidden, dim], [pool_hidden] or NULL */
+  const float *c_w, *c_b;             /* attention pools: score Linear   [1, pool_hidden], [1] or NULL */
+  const float *cls_w, *cls_b;         /* classifier [n_classes, dim] (ATTN_DECONF: [n_classes, dim + deconf_v]), [n_classes] or NULL */
+  const float *conf;                  /* ATTN_DECONF: confounder_feat    [deconf_k, deconf_v] */
+  const float *q_w, *q_b;             /* ATTN_DECONF: W_q                [deconf_j, dim], [deconf_j] */
+  const float *k_w, *k_b;             /* ATTN_DECONF: W_k                [deconf_j, deconf_v], [deconf_j] */
+} rrt_bagmil_weights;
+
+int rrt_bagmil_workspace_size(const rrt_bagmil_desc *desc, int64_t n_tokens, size_t *bytes);
+/* logits [n_classes]; optional (NULL: not wanted): attn [n_tokens] (attention pools: softmax over the bag, or the raw scores
+ * with no_norm != 0), pooled [dim] (attention pools: the bag embedding; MEAN: the column mean), argmax [n_classes] int64
+ * (MAX), deconf_a [deconf_k] and deconf_cf [deconf_v] (ATTN_DECONF).  An output the pool does not produce must be NULL
+ * (RRT_E_INVALID).  Nothing visits the host. */
+int rrt_bagmil_forward_f32(const rrt_bagmil_desc *desc, const rrt_bagmil_weights *w, const float *x, float *logits,
+                           float *attn, int32_t no_norm, float *pooled, int64_t *argmax, float *deconf_a, float *deconf_cf,
+                           int64_t n_tokens, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- batch-of-bags executor (BASELINE configs[4]: mixed-size bags, every bag an independent B=1 forward;
  * the reference loops `for bag in loader: model(bag)`, main.py:466-467 / :558-560) ----
  * Bags are independent units, and one bag's forward is a dependent chain of ~10 kernels that leaves

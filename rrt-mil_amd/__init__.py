@@ -33,8 +33,11 @@ from .mil import Attention, AttentionGated, DAttention, RRTMIL  # noqa: F401,E40
 from .clam import CLAM_MB, CLAM_SB  # noqa: F401,E402
 from .dsmil import DSMIL, MILNet  # noqa: F401,E402
 from .transmil import NystromAttention, TransMIL  # noqa: F401,E402
+from .attmil import ABMIL, GatedABMIL  # noqa: F401,E402  (attmil.DAttention / AttentionGated: the names are datten.py's here)
+from .attmil_ibmil import IBMIL  # noqa: F401,E402
+from .mean_max import MaxMIL, MeanMIL  # noqa: F401,E402
 from .encoder import (CrossRegionAttntion, InnerAttention, RegionAttntion, RRTEncoder,  # noqa: F401
                       TransLayer, initialize_weights)
 
-__all__ = ["RRTEncoder", "RRTMIL", "CLAM_SB", "CLAM_MB", "MILNet", "DSMIL", "TransMIL", "NystromAttention", "DAttention", "TransLayer", "RegionAttntion", "CrossRegionAttntion", "InnerAttention",
+__all__ = ["RRTEncoder", "RRTMIL", "CLAM_SB", "CLAM_MB", "MILNet", "DSMIL", "TransMIL", "NystromAttention", "ABMIL", "GatedABMIL", "IBMIL", "MeanMIL", "MaxMIL", "DAttention", "TransLayer", "RegionAttntion", "CrossRegionAttntion", "InnerAttention",
            "initialize_weights", "geometry", "sharding", "synth", "device_error"]

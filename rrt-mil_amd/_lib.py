@@ -90,6 +90,16 @@ class DsmilWeights(C.Structure):
         "emb_w", "emb_b", "icls_w", "icls_b", "q_w", "q_b", "fcc_w", "fcc_b")]
 
 
+class BagmilDesc(C.Structure):
+    _fields_ = [("enc", EncoderDesc)] + [(n, C.c_int32) for n in (
+        "input_dim", "emb_act", "has_rrt", "n_classes", "pool", "pool_hidden", "pool_act", "deconf_k", "deconf_v", "deconf_j")]
+
+
+class BagmilWeights(C.Structure):
+    _fields_ = [("enc", EncoderWeights)] + [(n, C.c_void_p) for n in (
+        "emb_w", "emb_b", "a_w", "a_b", "b_w", "b_b", "c_w", "c_b", "cls_w", "cls_b", "conf", "q_w", "q_b", "k_w", "k_b")]
+
+
 class NystromDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dim", "heads", "dim_head", "num_landmarks", "pinv_iterations", "residual",
                                          "residual_conv_kernel")]
@@ -226,6 +236,13 @@ SIGNATURES = {
     "rrt_dsmil_workspace_size": (C.c_int, [C.POINTER(DsmilDesc), C.c_int64, C.POINTER(C.c_size_t)]),
     "rrt_dsmil_forward_f32": (C.c_int, [C.POINTER(DsmilDesc), C.POINTER(DsmilWeights)] + [C.c_void_p] * 6 +
                               [C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_bag_mean_workspace_size": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_bag_mean_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_bag_mean_backward_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "rrt_deconf_head_f32": (C.c_int, [C.c_void_p] * 11 + [C.c_int32] * 5 + [C.c_void_p]),
+    "rrt_bagmil_workspace_size": (C.c_int, [C.POINTER(BagmilDesc), C.c_int64, C.POINTER(C.c_size_t)]),
+    "rrt_bagmil_forward_f32": (C.c_int, [C.POINTER(BagmilDesc), C.POINTER(BagmilWeights), C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int32] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rrt_executor_create": (C.c_int, [C.POINTER(EncoderDesc), C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     "rrt_executor_create_on_streams": (C.c_int, [C.POINTER(EncoderDesc), C.c_int32, C.POINTER(C.c_void_p), C.c_int64,
                                                  C.POINTER(C.c_void_p)]),
@@ -272,6 +289,7 @@ SIGNATURES = {
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32X3 = 0, 1, 2, 3
 POS_NONE, POS_PEG, POS_PPEG = 0, 1, 2
 EPEG_ATTN, EPEG_VALUE_BF, EPEG_VALUE_AF = 0, 1, 2
+BAGPOOL_MEAN, BAGPOOL_MAX, BAGPOOL_ATTN, BAGPOOL_ATTN_GATED, BAGPOOL_ATTN_DECONF = range(5)     # rrt_bagmil_desc.pool
 
 PLAN_FUSED, PLAN_FUSED_PROJ, PLAN_FUSED16, PLAN_FUSED_X3, PLAN_CRMSA_PARTS, PLAN_ATTN_HD = 1, 2, 4, 8, 16, 32     # rrt_encoder_plan flags
 # stage-boundary event slots of rrt_encoder_forward_events_f32 (enum in include/rrt_hip.h)

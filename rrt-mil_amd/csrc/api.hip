@@ -1729,6 +1729,97 @@ int carve_dsmil_head(const rrt_dsmil_desc* d, int64_t N, char* base, HeadWs* hw,
   return rc;
 }
 
+// ---- ABMIL / gated ABMIL / IBMIL / MeanMIL / MaxMIL heads (bag_pool.hip + the pools above)
+HeadFront head_front(const rrt_bagmil_desc* d) { return HeadFront{&d->enc, d->input_dim, d->emb_act, d->has_rrt, 0}; }
+
+int check_bag_mean(int64_t N, int dim, int C) {
+  if (N <= 0 || dim <= 0) return RRT_E_INVALID;
+  if (C < 1 || C > 8) return unsupported("bag mean: 1 <= n_classes <= 8");
+  if (dim % 32) return unsupported("bag mean: dim must be a multiple of 32");
+  if (dim > 2048) return unsupported("bag mean: dim > 2048");
+  if (N > (int64_t)1000000) return unsupported("bag mean: bag larger than 1e6 tokens");
+  return RRT_OK;
+}
+
+struct MeanWs {
+  float *part1, *part2;
+  size_t bytes;
+};
+MeanWs carve_mean(int64_t N, int dim, char* base) {
+  MeanWs w{};
+  Arena a{base};
+  w.part1 = a.take(bag_mean_part1_rows((int)N) * dim);
+  w.part2 = a.take(bag_mean_part2_rows((int)N) * dim);
+  w.bytes = a.bytes();
+  return w;
+}
+
+int check_deconf(int dim, int K, int V, int J, int C) {
+  if (dim <= 0 || V <= 0 || J <= 0 || C <= 0) return RRT_E_INVALID;
+  if (K < 1 || K > 64) return unsupported("deconfounder: 1 <= n_conf <= 64");
+  if (dim % 32 || dim > 2048) return unsupported("deconfounder: dim must be a multiple of 32 up to 2048");
+  if (V % 32 || V > 2048) return unsupported("deconfounder: conf_dim must be a multiple of 32 up to 2048");
+  if (J % 4 || J > 512) return unsupported("deconfounder: joint_dim must be a multiple of 4 up to 512");
+  return RRT_OK;
+}
+
+bool bagmil_attn(int pool) { return pool == RRT_BAGPOOL_ATTN || pool == RRT_BAGPOOL_ATTN_GATED || pool == RRT_BAGPOOL_ATTN_DECONF; }
+int bagmil_pool_act(const rrt_bagmil_desc* d) { return d->pool == RRT_BAGPOOL_ATTN_GATED ? d->pool_act : RRT_ACT_TANH; }
+
+int check_bagmil(const rrt_bagmil_desc* d, int64_t N) {
+  if (!d) return RRT_E_INVALID;
+  int rc = check_head_front(head_front(d), N);
+  if (rc) return rc;
+  if (d->n_classes <= 0) return RRT_E_INVALID;
+  switch (d->pool) {
+    case RRT_BAGPOOL_MEAN: return check_bag_mean(N, d->enc.dim, d->n_classes);
+    case RRT_BAGPOOL_MAX: return check_instance_max(N, d->enc.dim, d->n_classes);
+    case RRT_BAGPOOL_ATTN:
+    case RRT_BAGPOOL_ATTN_GATED:
+    case RRT_BAGPOOL_ATTN_DECONF:
+      rc = check_pool(N, d->enc.dim, d->pool_hidden, bagmil_pool_act(d), d->n_classes);
+      if (rc) return rc;
+      if (d->enc.dim > 2048) return unsupported("pool: dim > 2048");
+      if (d->pool == RRT_BAGPOOL_ATTN_DECONF) return check_deconf(d->enc.dim, d->deconf_k, d->deconf_v, d->deconf_j, d->n_classes);
+      return RRT_OK;
+    default: return unsupported("pool must be RRT_BAGPOOL_*");
+  }
+}
+
+// the tail's scratch: ONE carve for whichever pool the head has, plus a 256-byte piece for the critical instances of a MAX
+// caller that does not ask for them and a [dim] row for the deconfounder's input when the caller does not ask for `pooled`
+struct BagmilWs {
+  PoolWs pool;
+  IMaxWs imax;
+  MeanWs mean;
+  long long* argmax;
+  float* pooled;
+  size_t bytes;
+};
+BagmilWs carve_bagmil_scratch(const rrt_bagmil_desc* d, int64_t N, char* base) {
+  BagmilWs w{};
+  Arena a{base};
+  const int D = d->enc.dim;
+  if (d->pool == RRT_BAGPOOL_MEAN) {
+    w.mean = carve_mean(N, D, a.take<char>(carve_mean(N, D, nullptr).bytes));
+  } else if (d->pool == RRT_BAGPOOL_MAX) {
+    w.imax = carve_imax(N, d->n_classes, a.take<char>(carve_imax(N, d->n_classes, nullptr).bytes));
+    w.argmax = (long long*)a.take<char>(256);
+  } else {
+    const int gated = d->pool == RRT_BAGPOOL_ATTN_GATED;
+    w.pool = carve_pool(N, D, d->pool_hidden, gated, a.take<char>(carve_pool(N, D, d->pool_hidden, gated, nullptr).bytes));
+    w.pooled = a.take((size_t)D);
+  }
+  w.bytes = a.bytes();
+  return w;
+}
+int carve_bagmil_head(const rrt_bagmil_desc* d, int64_t N, char* base, HeadWs* hw, BagmilWs* bws) {
+  int rc = carve_head(head_front(d), N, carve_bagmil_scratch(d, N, nullptr).bytes, bagmil_attn(d->pool) ? d->pool_hidden : 0, base,
+                      hw);
+  if (rc == RRT_OK && bws) *bws = carve_bagmil_scratch(d, N, hw->head);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2033,6 +2124,98 @@ int rrt_dsmil_forward_f32(const rrt_dsmil_desc* desc, const rrt_dsmil_weights* w
   // (feats = the embedding: the bag stream reads it AFTER the encoder has run)
   return (int)launch_dsmil_pool(hw.emb, am, w->q_w, w->q_b, w->fcc_w, w->fcc_b, logits, A, B, ds.pool.raw, ds.pool.v, ds.pool.vb,
                                 ds.pool.lpart, ds.pool.part, (int)n_tokens, D, desc->q_dim, K, st);
+}
+
+// ---- ABMIL / gated ABMIL / IBMIL / MeanMIL / MaxMIL: the mean pool and its adjoint, the deconfounder, the one-call forward
+int rrt_bag_mean_workspace_size(int64_t n_tokens, int32_t dim, int32_t n_classes, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_bag_mean(n_tokens, dim, n_classes);
+  if (rc) return rc;
+  *bytes = carve_mean(n_tokens, dim, nullptr).bytes;
+  return RRT_OK;
+}
+
+int rrt_bag_mean_f32(const float* y, const float* w, const float* b, float* logits, float* colmean, int64_t n_tokens,
+                     int32_t dim, int32_t n_classes, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!y || !w || !logits) return RRT_E_INVALID;
+  int rc = check_bag_mean(n_tokens, dim, n_classes);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < carve_mean(n_tokens, dim, nullptr).bytes) return RRT_E_WORKSPACE;
+  MeanWs ws = carve_mean(n_tokens, dim, (char*)workspace);
+  return (int)launch_bag_mean(y, w, b, logits, colmean, ws.part1, ws.part2, (int)n_tokens, dim, n_classes, (hipStream_t)stream);
+}
+
+int rrt_bag_mean_backward_f32(const float* d_logits, const float* colmean, const float* w, float* dy, float* dW, float* db,
+                              int64_t n_tokens, int32_t dim, int32_t n_classes, void* stream) {
+  if (!d_logits || (dy && !w) || (dW && !colmean) || (!dy && !dW && !db)) return RRT_E_INVALID;
+  int rc = check_bag_mean(n_tokens, dim, n_classes);
+  if (rc) return rc;
+  return (int)launch_bag_mean_backward(d_logits, colmean, w, dy, dW, db, (int)n_tokens, dim, n_classes, (hipStream_t)stream);
+}
+
+int rrt_deconf_head_f32(const float* pooled, const float* conf, const float* q_w, const float* q_b, const float* k_w,
+                        const float* k_b, const float* head_w, const float* head_b, float* logits, float* a, float* cf,
+                        int32_t dim, int32_t n_conf, int32_t conf_dim, int32_t joint_dim, int32_t n_classes, void* stream) {
+  if (!pooled || !conf || !q_w || !k_w || !head_w || !logits) return RRT_E_INVALID;
+  int rc = check_deconf(dim, n_conf, conf_dim, joint_dim, n_classes);
+  if (rc) return rc;
+  return (int)launch_deconf_head(pooled, conf, q_w, q_b, k_w, k_b, head_w, head_b, logits, a, cf, dim, n_conf, conf_dim, joint_dim,
+                                 n_classes, (hipStream_t)stream);
+}
+
+int rrt_bagmil_workspace_size(const rrt_bagmil_desc* desc, int64_t n_tokens, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_bagmil(desc, n_tokens);
+  if (rc) return rc;
+  HeadWs hw;
+  rc = carve_bagmil_head(desc, n_tokens, nullptr, &hw, nullptr);
+  if (rc) return rc;
+  *bytes = hw.bytes;
+  return RRT_OK;
+}
+
+int rrt_bagmil_forward_f32(const rrt_bagmil_desc* desc, const rrt_bagmil_weights* w, const float* x, float* logits, float* attn,
+                           int32_t no_norm, float* pooled, int64_t* argmax, float* deconf_a, float* deconf_cf, int64_t n_tokens,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  if (!desc || !w || !x || !logits) return RRT_E_INVALID;
+  int rc = check_bagmil(desc, n_tokens);
+  if (rc) return rc;
+  const int pool = desc->pool;
+  const bool att = bagmil_attn(pool), gated = pool == RRT_BAGPOOL_ATTN_GATED, deconf = pool == RRT_BAGPOOL_ATTN_DECONF;
+  if (!w->emb_w || !w->cls_w) return RRT_E_INVALID;
+  if (att && (!w->a_w || !w->c_w || (gated && !w->b_w))) return RRT_E_INVALID;
+  if (deconf && (!w->conf || !w->q_w || !w->k_w)) return RRT_E_INVALID;
+  // an output the pool does not produce
+  if ((attn && !att) || (pooled && pool == RRT_BAGPOOL_MAX) || (argmax && pool != RRT_BAGPOOL_MAX) ||
+      ((deconf_a || deconf_cf) && !deconf))
+    return RRT_E_INVALID;
+  HeadWs hw;
+  BagmilWs bws;
+  rc = carve_bagmil_head(desc, n_tokens, (char*)workspace, &hw, &bws);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < hw.bytes) return RRT_E_WORKSPACE;
+  const int D = desc->enc.dim, C = desc->n_classes;
+  hipStream_t st = (hipStream_t)stream;
+  const float* b_w = gated ? w->b_w : nullptr;
+  bool p16 = false;
+  rc = head_front_forward(head_front(desc), hw, x, w->emb_w, w->emb_b, &w->enc, att ? w->a_w : nullptr, b_w,
+                          att ? desc->pool_hidden : 0, nullptr, /*tuning=*/false, n_tokens, stream, &p16);
+  if (rc) return rc;
+  // mean and max: fp32 in every mode (a 16-bit instance score could select another instance, as in DSMIL)
+  if (pool == RRT_BAGPOOL_MEAN)
+    return (int)launch_bag_mean(hw.y, w->cls_w, w->cls_b, logits, pooled, bws.mean.part1, bws.mean.part2, (int)n_tokens, D, C, st);
+  if (pool == RRT_BAGPOOL_MAX)
+    return (int)launch_instance_max(hw.y, w->cls_w, w->cls_b, nullptr, logits, argmax ? (long long*)argmax : bws.argmax,
+                                    bws.imax.pv, bws.imax.pi, (int)n_tokens, D, C, st);
+  // attention pools: the ABMIL pool of RRTMIL; the deconfounder variant takes its pooled row and no predictor
+  float* pl = deconf ? (pooled ? pooled : bws.pooled) : pooled;
+  rc = pool_predict(hw.y, w->a_w, w->a_b, b_w, w->b_b, w->c_w, w->c_b, deconf ? nullptr : w->cls_w, deconf ? nullptr : w->cls_b, pl,
+                    deconf ? nullptr : logits, attn, no_norm, n_tokens, D, desc->pool_hidden, bagmil_pool_act(desc),
+                    deconf ? 0 : C, gemm_precision(desc->enc.compute), bws.pool, st, p16 ? hw.y16 : nullptr,
+                    p16 ? hw.pa16 : nullptr, (p16 && b_w) ? hw.pb16 : nullptr);
+  if (rc || !deconf) return rc;
+  return (int)launch_deconf_head(pl, w->conf, w->q_w, w->q_b, w->k_w, w->k_b, w->cls_w, w->cls_b, logits, deconf_a, deconf_cf, D,
+                                 desc->deconf_k, desc->deconf_v, desc->deconf_j, C, st);
 }
 
 }  // extern "C"

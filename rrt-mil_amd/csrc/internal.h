@@ -272,6 +272,20 @@ hipError_t launch_dsmil_pool(const float* feats, const long long* argmax, const 
                              const float* fcc_b, float* logits, float* A, float* B, float* raw, float* v, float* vb, float* lpart,
                              float* part, int N, int dim, int Q, int K, hipStream_t st);
 
+// MeanMIL's tail and its adjoint, IBMIL's deconfounder (bag_pool.hip)
+constexpr int MEAN_CHUNK = 32;     // rows of y per first-level partial row
+constexpr int MEAN_FAN = 64;       // partial rows per second-level partial row (used from MEAN_FAN + 1 partials on)
+constexpr int MEAN_BWD_ROWS = 64;  // rows of dy per block of the adjoint
+size_t bag_mean_part1_rows(int N);
+size_t bag_mean_part2_rows(int N);
+hipError_t launch_bag_mean(const float* y, const float* w, const float* b, float* logits, float* colmean, float* part1,
+                           float* part2, int N, int dim, int C, hipStream_t st);
+hipError_t launch_bag_mean_backward(const float* d_logits, const float* colmean, const float* w, float* dy, float* dW, float* db,
+                                    int N, int dim, int C, hipStream_t st);
+hipError_t launch_deconf_head(const float* pooled, const float* conf, const float* q_w, const float* q_b, const float* k_w,
+                              const float* k_b, const float* head_w, const float* head_b, float* logits, float* a, float* cf,
+                              int dim, int K, int V, int J, int C, hipStream_t st);
+
 // ---- row f2 building blocks (backward)
 // nn.Linear backward: dX = dY W (forward GEMM on a transposed W), dW = dY^T X (split-K TN kernel), db = colsum(dY)
 size_t linear_bwd_workspace(int M, int N, int K);

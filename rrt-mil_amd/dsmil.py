@@ -24,7 +24,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from ._head import HeadState, head_compute
+from ._head import HeadState, _InstanceMax, head_compute, instance_max  # noqa: F401  (both live in _head.py: MaxMIL shares them)
 from .clam import _BranchPool
 from .encoder import RRTEncoder
 from .mil import lib_linear
@@ -61,54 +61,6 @@ class BClassifier(nn.Module):
         A = F.softmax(torch.mm(Q, self.q(m_feats).transpose(0, 1)) / math.sqrt(Q.shape[1]), 0)
         B = torch.mm(A.transpose(0, 1), feats)
         return self.fcc(B.unsqueeze(0)).view(1, -1), A, B
-
-
-def instance_max(y, weight, bias, return_classes=False):
-    """y (N, dim) fp32 device tensor, weight (C, dim), bias (C,) or None -> (cmax (C,), argmax (C,) int64[, classes (N, C)])
-    through rrt_instance_max_f32 (no graph)."""
-    lib = _lib.load()
-    if not y.is_cuda:
-        raise _lib.RRTHipError("rrt_mil_amd.dsmil runs on MI355X only; there is no CPU fallback")
-    y, w = y.detach().float().contiguous(), weight.detach().float().contiguous()
-    b = bias.detach().float().contiguous() if bias is not None else None
-    (n, d), c = y.shape, w.shape[0]
-    dev = y.device
-    cmax = torch.empty(c, dtype=torch.float32, device=dev)
-    idx = torch.empty(c, dtype=torch.int64, device=dev)
-    classes = torch.empty((n, c), dtype=torch.float32, device=dev) if return_classes else None
-    need = C.c_size_t()
-    _lib.check(lib.rrt_instance_max_workspace_size(n, d, c, C.byref(need)), "rrt_instance_max_workspace_size")
-    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.rrt_instance_max_f32(y.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None,
-                                            classes.data_ptr() if classes is not None else None, cmax.data_ptr(), idx.data_ptr(),
-                                            n, d, c, ws.data_ptr(), ws.numel(), st), "rrt_instance_max_f32")
-    return (cmax, idx, classes) if return_classes else (cmax, idx)
-
-
-class _InstanceMax(torch.autograd.Function):
-    """cmax[j] = max_n (y_n . w[j] + b[j]) and its row m_j as ONE pass over y (rrt_instance_max_f32); the [N, C] scores are
-    never stored.  The backward is sparse -- d y[m_j] += d cmax_j w[j], d w[j] = d cmax_j y[m_j], d b = d cmax -- never a
-    dense [N, C] product."""
-
-    @staticmethod
-    def forward(ctx, y, weight, bias):
-        cmax, idx = instance_max(y, weight, bias)
-        ctx.save_for_backward(y.detach().float().index_select(0, idx), weight, idx)
-        ctx.n, ctx.has_bias = y.shape[0], bias is not None
-        ctx.mark_non_differentiable(idx)
-        return cmax, idx
-
-    @staticmethod
-    def backward(ctx, d_cmax, _d_idx):
-        ym, weight, idx = ctx.saved_tensors
-        d_cmax = d_cmax.float()
-        rows = d_cmax[:, None] * weight.float()
-        dy = torch.zeros((ctx.n, ym.shape[1]), dtype=torch.float32, device=ym.device)
-        for j in range(idx.shape[0]):              # one class at a time: two classes may share a critical instance
-            dy.index_add_(0, idx[j:j + 1], rows[j:j + 1])
-        return dy, d_cmax[:, None] * ym, (d_cmax if ctx.has_bias else None)
 
 
 class MILNet(HeadState, nn.Module):

@@ -196,7 +196,29 @@ def dsmil_head_state(shapes, tag):
     return out
 
 
-K_ALIGN, K_NOISE = 0.33, 0.4     # nystrom_state: k rows = K_ALIGN * q rows + K_NOISE * their own draw
+def bagmil_head_state(shapes, tag):
+    """Closed-form parameters for an ABMIL / gated ABMIL / IBMIL / MeanMIL / MaxMIL head (without the encoder's entries):
+    ``shapes`` is an ordered {state_dict key: shape}.  Weights N(0, 1) * gain / sqrt(fan_in) -- gain 1.5 on the score Linear
+    of an attention pool (``attention.2`` / ``attention_c``: an attention that is visibly non-uniform over the bag) and on
+    the last Linear of a ``head`` Sequential (MeanMIL / MaxMIL: instance scores of O(1), so that the maxima stand out), 2.0
+    on ``W_q`` / ``W_k`` (their product is the confounder score); biases uniform in +-0.1; ``confounder_feat`` N(0, 0.7^2)."""
+    head_last = max([int(k.split(".")[1]) for k in shapes if k.startswith("head.") and k.count(".") == 2], default=-1)
+    out = {}
+    for key, shape in shapes.items():
+        shape = tuple(shape)
+        name = f"bagmil/{tag}/{key}"
+        if key == "confounder_feat":
+            out[key] = (normal(name, shape) * 0.7).astype(np.float32)
+        elif key.endswith(".bias"):
+            out[key] = uniform(name, shape, -0.1, 0.1)
+        else:
+            score = key.startswith(("attention.2.", "attention_c.")) or key.startswith(f"head.{head_last}.")
+            gain = 1.5 if score else (2.0 if key.startswith(("W_q.", "W_k.")) else 1.0)
+            out[key] = (normal(name, shape) * (gain / np.sqrt(shape[-1]))).astype(np.float32)
+    return out
+
+
+K_ALIGN, K_NOISE = 0.33, 0.4    # nystrom_state: k rows = K_ALIGN * q rows + K_NOISE * their own draw
 
 
 def nystrom_state(dim=512, heads=8, dim_head=64, residual_conv_kernel=33, gain=1.0, residual=True, tag="nys"):

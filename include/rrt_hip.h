@@ -903,6 +903,54 @@ int rrt_nystrom_zav_f32(const float *z, const float *av, float *wz, int32_t head
 int rrt_nystrom_output_f32(const float *qkv, const float *kl, const float *wz, const float *conv_w, float *o,
                            int64_t n_padded, int32_t heads, int32_t conv_k, void *stream);
 
+/* ---- Nystrom attention, training (exports added under ABI 29, no existing struct or signature touched).  Exact fp32 on the
+ * fp32 matrix cores, no atomics: two runs give the same bits.  The same envelope as the forward above.
+ *
+ * forward_train: y is bit-identical to rrt_nystrom_attention_f32; what the backward reads (qkv, the landmarks, a2, z, av, wz,
+ * o and the row log-sum-exp of ql k^T) stays in the caller-owned stash of rrt_nystrom_train_sizes' stash_bytes.
+ * backward: dy [n, dim] -> the parameter gradients (WRITTEN, not accumulated; conv_w [heads, k] is unused when
+ * residual = 0) and, when dx is not NULL, dx [n, dim].  x and w are the forward's. */
+typedef struct rrt_nystrom_grads {
+  float *qkv_w;
+  float *out_w, *out_b;
+  float *conv_w;
+} rrt_nystrom_grads;
+
+int rrt_nystrom_train_sizes(const rrt_nystrom_desc *desc, int64_t n, size_t *stash_bytes, size_t *backward_workspace_bytes);
+int rrt_nystrom_attention_forward_train_f32(const rrt_nystrom_desc *desc, const rrt_nystrom_weights *w, const float *x,
+                                            float *y, int64_t n, void *stash, size_t stash_bytes, void *stream);
+int rrt_nystrom_attention_backward_f32(const rrt_nystrom_desc *desc, const rrt_nystrom_weights *w, const float *x,
+                                       const float *dy, const void *stash, size_t stash_bytes,
+                                       const rrt_nystrom_grads *grads, float *dx, int64_t n, void *workspace,
+                                       size_t workspace_bytes, void *stream);
+
+/* Backward stage entry points, one per kernel group (layouts as the forward stages; d_qkv is the gradient of the qkv linear's
+ * output with the q columns still scaled, i.e. before the 64^-0.5 of the epilogue is applied to it).
+ *  output_backward        : qkv, kl, wz, conv_w (or NULL), d_o [np, heads * 64] -> d_qkv (q and v thirds written, k third
+ *                           zeroed), d_kl, d_wz [heads, 256, 64], d_conv_w [heads, conv_k] (untouched when conv_w is NULL);
+ *  zav_backward           : z, av, d_wz -> d_z [heads, 256, 256], d_av [heads, 256, 64];
+ *  landmark_attn_backward : qkv, ql, d_av -> d_ql (written); ADDS dk, dv into the k and v thirds of d_qkv, q third untouched;
+ *  pinv_sim_backward      : ql, kl, d_z -> d_ql, d_kl (written): the gradient of pinv(softmax(ql kl^T)), including the part
+ *                           through the all-heads scale of z0 (its largest-column-sum factor; the largest-row-sum factor
+ *                           has no gradient behind a softmax);
+ *  landmarks_backward     : ADDS d_ql[j] / l and d_kl[j] / l into the q and k thirds of the l rows of landmark j. */
+int rrt_nystrom_output_backward_workspace_size(int64_t n_padded, int32_t heads, size_t *bytes);
+int rrt_nystrom_output_backward_f32(const float *qkv, const float *kl, const float *wz, const float *conv_w, const float *d_o,
+                                    float *d_qkv, float *d_kl, float *d_wz, float *d_conv_w, int64_t n_padded, int32_t heads,
+                                    int32_t conv_k, void *workspace, size_t workspace_bytes, void *stream);
+int rrt_nystrom_zav_backward_f32(const float *z, const float *av, const float *d_wz, float *d_z, float *d_av, int32_t heads,
+                                 void *stream);
+int rrt_nystrom_landmark_attn_backward_workspace_size(int64_t n_padded, int32_t heads, size_t *bytes);
+int rrt_nystrom_landmark_attn_backward_f32(const float *qkv, const float *ql, const float *d_av, float *d_qkv, float *d_ql,
+                                           int64_t n_padded, int32_t heads, void *workspace, size_t workspace_bytes,
+                                           void *stream);
+int rrt_nystrom_pinv_sim_backward_workspace_size(int32_t heads, int32_t iterations, size_t *bytes);
+int rrt_nystrom_pinv_sim_backward_f32(const float *ql, const float *kl, const float *d_z, float *d_ql, float *d_kl,
+                                      int32_t heads, int32_t iterations, void *workspace, size_t workspace_bytes,
+                                      void *stream);
+int rrt_nystrom_landmarks_backward_f32(const float *d_ql, const float *d_kl, float *d_qkv, int64_t n_padded, int32_t heads,
+                                       void *stream);
+
 /* TransMIL's PPEG (transmil.py:47-61): x, y [1 + side * side, dim]; row 0 (the cls token) passes through, the other rows as
  * a side x side image become x + conv7(x) + conv5(x) + conv3(x), depth-wise with zero borders.  The side is EXACTLY the
  * caller's (rrt_peg_f32 derives it from the row count, wraps, and lifts sides below 7 to 7).  w / b: HOST arrays of three

@@ -109,6 +109,10 @@ class NystromWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("qkv_w", "out_w", "out_b", "conv_w")]
 
 
+class NystromGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("qkv_w", "out_w", "out_b", "conv_w")]
+
+
 class TransmilDesc(C.Structure):
     _fields_ = [("input_dim", C.c_int32), ("n_classes", C.c_int32), ("act", C.c_int32), ("attn", NystromDesc)]
 
@@ -284,6 +288,23 @@ SIGNATURES = {
     "rrt_transmil_workspace_size": (C.c_int, [C.POINTER(TransmilDesc), C.c_int64, C.POINTER(C.c_size_t)]),
     "rrt_transmil_forward_f32": (C.c_int, [C.POINTER(TransmilDesc), C.POINTER(TransmilWeights)] + [C.c_void_p] * 3 +
                                  [C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_nystrom_train_sizes": (C.c_int, [C.POINTER(NystromDesc), C.c_int64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_attention_forward_train_f32": (C.c_int, [C.POINTER(NystromDesc), C.POINTER(NystromWeights), C.c_void_p,
+                                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_nystrom_attention_backward_f32": (C.c_int, [C.POINTER(NystromDesc), C.POINTER(NystromWeights), C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_size_t, C.POINTER(NystromGrads), C.c_void_p, C.c_int64,
+                                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_nystrom_output_backward_workspace_size": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_output_backward_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                                                     C.c_void_p]),
+    "rrt_nystrom_zav_backward_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p]),
+    "rrt_nystrom_landmark_attn_backward_workspace_size": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_landmark_attn_backward_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_void_p, C.c_size_t,
+                                                                            C.c_void_p]),
+    "rrt_nystrom_pinv_sim_backward_workspace_size": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_pinv_sim_backward_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                                                       C.c_void_p]),
+    "rrt_nystrom_landmarks_backward_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_void_p]),
 }
 
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32X3 = 0, 1, 2, 3

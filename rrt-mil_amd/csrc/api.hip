@@ -3234,7 +3234,7 @@ NystromWs carve_nystrom(const rrt_nystrom_desc* d, int64_t n, char* base) {
 
 // y [n, dim] = NystromAttention(x); everything checked by the caller
 int nystrom_forward(const rrt_nystrom_desc* d, const rrt_nystrom_weights* w, const float* x, float* y, int64_t n,
-                    const NystromWs& ws, hipStream_t st) {
+                    const NystromWs& ws, hipStream_t st, float* lse = nullptr) {
   const int hd = d->heads * 64;
   const int64_t pad = ws.np - n;
   if (pad) RRT_TRY(hipMemsetAsync(ws.qkv, 0, (size_t)pad * 3 * hd * sizeof(float), st));
@@ -3244,7 +3244,7 @@ int nystrom_forward(const rrt_nystrom_desc* d, const rrt_nystrom_weights* w, con
   RRT_TRY(launch_linear(x, w->qkv_w, ws.qkv + (size_t)pad * 3 * hd, (int)n, 3 * hd, d->dim, ep, st));
   RRT_TRY(launch_nystrom_landmarks(ws.qkv, ws.ql, ws.kl, (long)ws.np, d->heads, st));
   RRT_TRY(launch_nystrom_sim2(ws.ql, ws.kl, ws.a2, d->heads, st));
-  RRT_TRY(launch_nystrom_lattn(ws.qkv, ws.ql, ws.av, ws.lattn, (long)ws.np, d->heads, st));
+  RRT_TRY(launch_nystrom_lattn(ws.qkv, ws.ql, ws.av, ws.lattn, (long)ws.np, d->heads, st, lse));
   RRT_TRY(launch_nystrom_pinv(ws.a2, ws.z, ws.pinv, d->heads, d->pinv_iterations, st));
   RRT_TRY(launch_nystrom_zav(ws.z, ws.av, ws.wz, d->heads, st));
   RRT_TRY(launch_nystrom_output(ws.qkv, ws.kl, ws.wz, d->residual ? w->conv_w : nullptr, ws.o, (long)ws.np, d->heads,
@@ -3447,6 +3447,234 @@ int rrt_transmil_forward_f32(const rrt_transmil_desc* desc, const rrt_transmil_w
   RRT_TRY(launch_layernorm(ws.seq2, nullptr, w->norm_w, w->norm_b, ws.ln, 1, D, st));
   RRT_TRY(launch_transmil_head(ws.ln, w->fc2_w, w->fc2_b, logits, D, desc->n_classes, st));
   return RRT_OK;
+}
+
+}  // extern "C"
+
+// ---- Nystrom attention: training (nystrom_bwd.hip)
+namespace {
+
+// the forward's workspace kept whole (what the backward reads: qkv, ql, kl, a2, z, av, wz, o) | lse [heads, 256]
+struct NystromStash {
+  NystromWs f;
+  float* lse;
+  size_t bytes;
+};
+NystromStash carve_nystrom_stash(const rrt_nystrom_desc* d, int64_t n, char* base) {
+  NystromStash s{};
+  s.f = carve_nystrom(d, n, base);
+  Arena a{base};
+  a.take<char>(s.f.bytes);
+  s.lse = a.take((size_t)d->heads * 256);
+  s.bytes = a.bytes();
+  return s;
+}
+
+size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
+
+struct NystromBwdWs {
+  float *d_o, *d_qkv, *d_ql, *d_kl, *d_wz, *d_av, *d_z, *part, *pinv;
+  char* lin;
+  size_t bytes;
+};
+NystromBwdWs carve_nystrom_bwd(const rrt_nystrom_desc* d, int64_t n, char* base) {
+  NystromBwdWs ws{};
+  const int64_t np = (n + 255) / 256 * 256;
+  const int hd = d->heads * 64;
+  const size_t lm = (size_t)d->heads * 256 * 64, mm = (size_t)d->heads * 256 * 256;
+  Arena a{base};
+  ws.d_o = a.take((size_t)np * hd);
+  ws.d_qkv = a.take((size_t)np * 3 * hd);
+  ws.d_ql = a.take(lm);
+  ws.d_kl = a.take(lm);
+  ws.d_wz = a.take(lm);
+  ws.d_av = a.take(lm);
+  ws.d_z = a.take(mm);
+  ws.part = a.take(max_sz(nystrom_output_bwd_floats((long)np, d->heads), nystrom_lattn_bwd_floats((long)np, d->heads)));
+  ws.pinv = a.take(nystrom_pinv_bwd_floats(d->heads, d->pinv_iterations));
+  ws.lin = a.take<char>(max_sz(linear_bwd_workspace((int)n, d->dim, hd), linear_bwd_workspace((int)n, 3 * hd, d->dim)));
+  ws.bytes = a.bytes();
+  return ws;
+}
+
+struct LattnBwdWs {
+  float *fwd, *av, *lse, *bwd;
+  size_t bytes;
+};
+LattnBwdWs carve_lattn_bwd(int64_t np, int heads, char* base) {
+  LattnBwdWs ws{};
+  Arena a{base};
+  ws.fwd = a.take(nystrom_lattn_floats((long)np, heads));
+  ws.av = a.take((size_t)heads * 256 * 64);
+  ws.lse = a.take((size_t)heads * 256);
+  ws.bwd = a.take(nystrom_lattn_bwd_floats((long)np, heads));
+  ws.bytes = a.bytes();
+  return ws;
+}
+
+struct PinvSimBwdWs {
+  float *a2, *bwd;
+  size_t bytes;
+};
+PinvSimBwdWs carve_pinv_sim_bwd(int heads, int iters, char* base) {
+  PinvSimBwdWs ws{};
+  Arena a{base};
+  ws.a2 = a.take((size_t)heads * 256 * 256);
+  ws.bwd = a.take(nystrom_pinv_bwd_floats(heads, iters));
+  ws.bytes = a.bytes();
+  return ws;
+}
+
+int check_pinv_iterations(int32_t iterations) {
+  if (iterations < 1 || iterations > 16) return unsupported("nystrom: pinv_iterations must be in 1..16");
+  return RRT_OK;
+}
+int check_np_heads(int64_t np, int32_t heads) {
+  int rc = check_nystrom_np(np);
+  if (!rc) rc = check_nystrom_heads(heads);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rrt_nystrom_train_sizes(const rrt_nystrom_desc* desc, int64_t n, size_t* stash_bytes, size_t* backward_workspace_bytes) {
+  if (!stash_bytes || !backward_workspace_bytes) return RRT_E_INVALID;
+  int rc = check_nystrom(desc, n);
+  if (rc) return rc;
+  *stash_bytes = carve_nystrom_stash(desc, n, nullptr).bytes;
+  *backward_workspace_bytes = carve_nystrom_bwd(desc, n, nullptr).bytes;
+  return RRT_OK;
+}
+
+int rrt_nystrom_attention_forward_train_f32(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w, const float* x, float* y,
+                                            int64_t n, void* stash, size_t stash_bytes, void* stream) {
+  if (!desc || !w || !x || !y) return RRT_E_INVALID;
+  int rc = check_nystrom(desc, n);
+  if (rc) return rc;
+  if (!nystrom_weights_ok(desc, w)) return RRT_E_INVALID;
+  if (!stash || stash_bytes < carve_nystrom_stash(desc, n, nullptr).bytes) return RRT_E_WORKSPACE;
+  const NystromStash s = carve_nystrom_stash(desc, n, (char*)stash);
+  return nystrom_forward(desc, w, x, y, n, s.f, (hipStream_t)stream, s.lse);
+}
+
+int rrt_nystrom_attention_backward_f32(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w, const float* x,
+                                       const float* dy, const void* stash, size_t stash_bytes, const rrt_nystrom_grads* grads,
+                                       float* dx, int64_t n, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!desc || !w || !x || !dy || !grads) return RRT_E_INVALID;
+  int rc = check_nystrom(desc, n);
+  if (rc) return rc;
+  if (!nystrom_weights_ok(desc, w)) return RRT_E_INVALID;
+  if (!grads->qkv_w || !grads->out_w || !grads->out_b || (desc->residual && !grads->conv_w)) return RRT_E_INVALID;
+  if (!stash || stash_bytes < carve_nystrom_stash(desc, n, nullptr).bytes) return RRT_E_WORKSPACE;
+  if (!workspace || workspace_bytes < carve_nystrom_bwd(desc, n, nullptr).bytes) return RRT_E_WORKSPACE;
+  const NystromStash s = carve_nystrom_stash(desc, n, (char*)stash);
+  const NystromBwdWs b = carve_nystrom_bwd(desc, n, (char*)workspace);
+  hipStream_t st = (hipStream_t)stream;
+  const int heads = desc->heads, hd = heads * 64;
+  const long np = (long)s.f.np;
+  const int64_t pad = s.f.np - n;
+  // to_out: the pad rows of d_o are zero
+  if (pad) RRT_TRY(hipMemsetAsync(b.d_o, 0, (size_t)pad * hd * sizeof(float), st));
+  RRT_TRY(launch_linear_backward(dy, s.f.o + (size_t)pad * hd, w->out_w, b.d_o + (size_t)pad * hd, grads->out_w, grads->out_b,
+                                 (int)n, desc->dim, hd, RRT_COMPUTE_F32, b.lin, st));
+  RRT_TRY(launch_nystrom_output_backward(s.f.qkv, s.f.kl, s.f.wz, desc->residual ? w->conv_w : nullptr, b.d_o, b.d_qkv, b.d_kl,
+                                         b.d_wz, grads->conv_w, b.part, np, heads, desc->residual_conv_kernel, st));
+  RRT_TRY(launch_nystrom_zav_backward(s.f.z, s.f.av, b.d_wz, b.d_z, b.d_av, heads, st));
+  RRT_TRY(launch_nystrom_lattn_backward(s.f.qkv, s.f.ql, s.f.av, s.lse, b.d_av, b.d_qkv, b.d_ql, b.part, np, heads, st));
+  RRT_TRY(launch_nystrom_pinv_sim_backward(s.f.ql, s.f.kl, s.f.a2, b.d_z, b.d_ql, b.d_kl, 1, b.pinv, heads,
+                                           desc->pinv_iterations, st));
+  RRT_TRY(launch_nystrom_landmarks_backward(b.d_ql, b.d_kl, b.d_qkv, np, heads, st));
+  // to_qkv: the forward scales q in the linear's epilogue; the pad rows of dx are dropped
+  float* d_rows = b.d_qkv + (size_t)pad * 3 * hd;
+  RRT_TRY(launch_nystrom_scale_q(d_rows, (long)n, heads, st));
+  RRT_TRY(launch_linear_backward(d_rows, x, w->qkv_w, dx, grads->qkv_w, nullptr, (int)n, 3 * hd, desc->dim, RRT_COMPUTE_F32,
+                                 b.lin, st));
+  return RRT_OK;
+}
+
+int rrt_nystrom_output_backward_workspace_size(int64_t n_padded, int32_t heads, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_np_heads(n_padded, heads);
+  if (rc) return rc;
+  Arena a{nullptr};
+  a.take(nystrom_output_bwd_floats((long)n_padded, heads));
+  *bytes = a.bytes();
+  return RRT_OK;
+}
+
+int rrt_nystrom_output_backward_f32(const float* qkv, const float* kl, const float* wz, const float* conv_w, const float* d_o,
+                                    float* d_qkv, float* d_kl, float* d_wz, float* d_conv_w, int64_t n_padded, int32_t heads,
+                                    int32_t conv_k, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!qkv || !kl || !wz || !d_o || !d_qkv || !d_kl || !d_wz || (conv_w && !d_conv_w)) return RRT_E_INVALID;
+  int rc = check_np_heads(n_padded, heads);
+  if (rc) return rc;
+  if (conv_w && (conv_k < 1 || conv_k % 2 == 0 || conv_k > 63)) return unsupported("nystrom: residual_conv_kernel must be odd and <= 63");
+  Arena a{(char*)workspace};
+  float* part = a.take(nystrom_output_bwd_floats((long)n_padded, heads));
+  if (!workspace || workspace_bytes < a.bytes()) return RRT_E_WORKSPACE;
+  return (int)launch_nystrom_output_backward(qkv, kl, wz, conv_w, d_o, d_qkv, d_kl, d_wz, d_conv_w, part, (long)n_padded, heads,
+                                             conv_k, (hipStream_t)stream);
+}
+
+int rrt_nystrom_zav_backward_f32(const float* z, const float* av, const float* d_wz, float* d_z, float* d_av, int32_t heads,
+                                 void* stream) {
+  if (!z || !av || !d_wz || !d_z || !d_av) return RRT_E_INVALID;
+  int rc = check_nystrom_heads(heads);
+  if (rc) return rc;
+  return (int)launch_nystrom_zav_backward(z, av, d_wz, d_z, d_av, heads, (hipStream_t)stream);
+}
+
+int rrt_nystrom_landmark_attn_backward_workspace_size(int64_t n_padded, int32_t heads, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_np_heads(n_padded, heads);
+  if (rc) return rc;
+  *bytes = carve_lattn_bwd(n_padded, heads, nullptr).bytes;
+  return RRT_OK;
+}
+
+int rrt_nystrom_landmark_attn_backward_f32(const float* qkv, const float* ql, const float* d_av, float* d_qkv, float* d_ql,
+                                           int64_t n_padded, int32_t heads, void* workspace, size_t workspace_bytes,
+                                           void* stream) {
+  if (!qkv || !ql || !d_av || !d_qkv || !d_ql) return RRT_E_INVALID;
+  int rc = check_np_heads(n_padded, heads);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < carve_lattn_bwd(n_padded, heads, nullptr).bytes) return RRT_E_WORKSPACE;
+  const LattnBwdWs ws = carve_lattn_bwd(n_padded, heads, (char*)workspace);
+  hipStream_t st = (hipStream_t)stream;
+  RRT_TRY(launch_nystrom_lattn(qkv, ql, ws.av, ws.fwd, (long)n_padded, heads, st, ws.lse));
+  return (int)launch_nystrom_lattn_backward(qkv, ql, ws.av, ws.lse, d_av, d_qkv, d_ql, ws.bwd, (long)n_padded, heads, st);
+}
+
+int rrt_nystrom_pinv_sim_backward_workspace_size(int32_t heads, int32_t iterations, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_nystrom_heads(heads);
+  if (!rc) rc = check_pinv_iterations(iterations);
+  if (rc) return rc;
+  *bytes = carve_pinv_sim_bwd(heads, iterations, nullptr).bytes;
+  return RRT_OK;
+}
+
+int rrt_nystrom_pinv_sim_backward_f32(const float* ql, const float* kl, const float* d_z, float* d_ql, float* d_kl,
+                                      int32_t heads, int32_t iterations, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!ql || !kl || !d_z || !d_ql || !d_kl) return RRT_E_INVALID;
+  int rc = check_nystrom_heads(heads);
+  if (!rc) rc = check_pinv_iterations(iterations);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < carve_pinv_sim_bwd(heads, iterations, nullptr).bytes) return RRT_E_WORKSPACE;
+  const PinvSimBwdWs ws = carve_pinv_sim_bwd(heads, iterations, (char*)workspace);
+  hipStream_t st = (hipStream_t)stream;
+  RRT_TRY(launch_nystrom_sim2(ql, kl, ws.a2, heads, st));
+  return (int)launch_nystrom_pinv_sim_backward(ql, kl, ws.a2, d_z, d_ql, d_kl, 0, ws.bwd, heads, iterations, st);
+}
+
+int rrt_nystrom_landmarks_backward_f32(const float* d_ql, const float* d_kl, float* d_qkv, int64_t n_padded, int32_t heads,
+                                       void* stream) {
+  if (!d_ql || !d_kl || !d_qkv) return RRT_E_INVALID;
+  int rc = check_np_heads(n_padded, heads);
+  if (rc) return rc;
+  return (int)launch_nystrom_landmarks_backward(d_ql, d_kl, d_qkv, (long)n_padded, heads, (hipStream_t)stream);
 }
 
 }  // extern "C"

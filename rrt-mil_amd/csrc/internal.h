@@ -379,11 +379,33 @@ size_t nystrom_lattn_floats(long np, int heads);
 size_t nystrom_pinv_floats(int heads);
 hipError_t launch_nystrom_landmarks(const float* qkv, float* ql, float* kl, long np, int heads, hipStream_t st);
 hipError_t launch_nystrom_sim2(const float* ql, const float* kl, float* a2, int heads, hipStream_t st);
-hipError_t launch_nystrom_lattn(const float* qkv, const float* ql, float* av, float* ws, long np, int heads, hipStream_t st);
+hipError_t launch_nystrom_lattn(const float* qkv, const float* ql, float* av, float* ws, long np, int heads, hipStream_t st,
+                                float* lse = nullptr);     // lse [heads, 256] (optional): the row log-sum-exp of ql k^T
 hipError_t launch_nystrom_pinv(const float* a2, float* z, float* ws, int heads, int iters, hipStream_t st);
 hipError_t launch_nystrom_zav(const float* z, const float* av, float* wz, int heads, hipStream_t st);
 hipError_t launch_nystrom_output(const float* qkv, const float* kl, const float* wz, const float* conv_w, float* o, long np,
                                  int heads, int ks, hipStream_t st);
+// Nystrom attention backward (nystrom_bwd.hip).  d_qkv [np, 3 * heads * 64] is the gradient of the SCALED q | k | v.
+//  output_backward   writes the q and v thirds of d_qkv and zeroes the k third; ws: nystrom_output_bwd_floats
+//  lattn_backward    ADDS dk, dv into the k and v thirds, writes d_ql; av / lse as launch_nystrom_lattn left them;
+//                    ws: nystrom_lattn_bwd_floats
+//  pinv_sim_backward d_ql, d_kl (+)= the gradient of pinv(a2 = softmax(ql kl^T)) under d_z; ws: nystrom_pinv_bwd_floats
+//  landmarks_backward ADDS the 1 / l shares of d_ql, d_kl into the q and k thirds
+size_t nystrom_output_bwd_floats(long np, int heads);
+size_t nystrom_lattn_bwd_floats(long np, int heads);
+size_t nystrom_pinv_bwd_floats(int heads, int iters);
+hipError_t launch_nystrom_output_backward(const float* qkv, const float* kl, const float* wz, const float* conv_w,
+                                          const float* d_o, float* d_qkv, float* d_kl, float* d_wz, float* d_conv_w, float* ws,
+                                          long np, int heads, int ks, hipStream_t st);
+hipError_t launch_nystrom_zav_backward(const float* z, const float* av, const float* d_wz, float* d_z, float* d_av, int heads,
+                                       hipStream_t st);
+hipError_t launch_nystrom_lattn_backward(const float* qkv, const float* ql, const float* av, const float* lse, const float* d_av,
+                                         float* d_qkv, float* d_ql, float* ws, long np, int heads, hipStream_t st);
+hipError_t launch_nystrom_pinv_sim_backward(const float* ql, const float* kl, const float* a2, const float* d_z, float* d_ql,
+                                            float* d_kl, int accumulate, float* ws, int heads, int iters, hipStream_t st);
+hipError_t launch_nystrom_landmarks_backward(const float* d_ql, const float* d_kl, float* d_qkv, long np, int heads,
+                                             hipStream_t st);
+hipError_t launch_nystrom_scale_q(float* d_qkv, long rows, int heads, hipStream_t st);
 hipError_t launch_transmil_assemble(const float* h, const float* cls, float* seq, int N, int rows, int dim, hipStream_t st);
 hipError_t launch_transmil_head(const float* x, const float* w, const float* b, float* logits, int dim, int n_classes,
                                 hipStream_t st);

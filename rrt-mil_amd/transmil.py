@@ -5,8 +5,12 @@ Same constructor signatures, module tree and parameter names as the reference (`
 ``layer{1,2}.norm``, ``layer{1,2}.attn.{to_qkv, to_out.0, res_conv}``, ``pos_layer.{proj, proj1, proj2}``, ``norm``,
 ``_fc2``): reference checkpoints load with ``strict=True``.
 
-Inference only.  A bag is ONE C-ABI call (rrt_transmil_forward_f32: ``forward_bag``).  There is no backward: a call that
-needs a graph, or ``train()`` with dropout, raises ``NotImplementedError`` -- use ``eval()`` under ``torch.no_grad()``.
+Inference is the default: a bag is ONE C-ABI call (rrt_transmil_forward_f32: ``forward_bag``), and a call that needs a graph,
+or ``train()`` with dropout, raises ``NotImplementedError`` -- use ``eval()`` under ``torch.no_grad()``.
+
+Training is opt-in: after ``model.enable_training()`` a call that needs a graph (or ``train()`` with dropout) takes the layer
+path -- torch ops around ``NystromAttention``, whose forward-with-stash and backward are the HIP kernels of csrc/nystrom.hip and
+csrc/nystrom_bwd.hip under a ``torch.autograd.Function``; a call that needs no graph still takes the one-call path, bit for bit.
 The arithmetic is exact fp32 on the fp32 matrix cores in every context: under ``torch.autocast`` the modules STILL compute
 in fp32 (there is no 16-bit path for the pseudo-inverse iteration, whose conditioning does not survive 8 mantissa bits).
 """
@@ -46,9 +50,64 @@ def _no_cpu(t, who):
                                "CPU fallback")
 
 
+def _needs_graph(module, x):
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
+
+
 def _no_graph(module, x, who):
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters())):
-        raise NotImplementedError(f"rrt_mil_amd.{who} has no backward: call it in eval() under torch.no_grad()")
+    if _needs_graph(module, x):
+        raise NotImplementedError(f"rrt_mil_amd.{who} has no backward by default: call it in eval() under torch.no_grad(), "
+                                  "or opt in to the training path with enable_training()")
+
+
+class _NystromFn(torch.autograd.Function):
+    """y [n, dim] = NystromAttention without its Dropout, fp32: rrt_nystrom_attention_forward_train_f32 (the bits of
+    rrt_nystrom_attention_f32; what the backward reads stays in a stash the graph owns) and
+    rrt_nystrom_attention_backward_f32 (d x and the gradients of to_qkv.weight, to_out.0.weight, to_out.0.bias,
+    res_conv.weight)."""
+
+    @staticmethod
+    def forward(ctx, desc, x2d, wq, wo, bo, wc):
+        lib = _lib.load()
+        ts = [t.detach().float().contiguous() if t is not None else None for t in (x2d, wq, wo, bo, wc)]
+        x, dev = ts[0], ts[0].device
+        n = x.shape[0]
+        w = _lib.NystromWeights()
+        w.qkv_w, w.out_w, w.out_b, w.conv_w = (_ptr(t) for t in ts[1:])
+        stash_bytes, bwd_bytes = C.c_size_t(), C.c_size_t()
+        _lib.check(lib.rrt_nystrom_train_sizes(C.byref(desc), n, C.byref(stash_bytes), C.byref(bwd_bytes)),
+                   "rrt_nystrom_train_sizes")
+        stash = torch.empty(stash_bytes.value, dtype=torch.uint8, device=dev)
+        y = torch.empty((n, desc.dim), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.rrt_nystrom_attention_forward_train_f32(C.byref(desc), C.byref(w), x.data_ptr(), y.data_ptr(), n,
+                                                                   stash.data_ptr(), stash.numel(), st),
+                       "rrt_nystrom_attention_forward_train_f32")
+        ctx.save_for_backward(stash, *[t for t in ts if t is not None])
+        ctx.desc, ctx.bwd_bytes, ctx.has_conv = desc, bwd_bytes.value, ts[4] is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        stash, x, wq, wo, bo = ctx.saved_tensors[:5]
+        wc = ctx.saved_tensors[5] if ctx.has_conv else None
+        desc, dev, n = ctx.desc, x.device, x.shape[0]
+        dy = dy.float().contiguous()
+        w, g = _lib.NystromWeights(), _lib.NystromGrads()
+        w.qkv_w, w.out_w, w.out_b, w.conv_w = (_ptr(t) for t in (wq, wo, bo, wc))
+        grads = [torch.empty_like(t) if t is not None else None for t in (wq, wo, bo, wc)]
+        g.qkv_w, g.out_w, g.out_b, g.conv_w = (_ptr(t) for t in grads)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        ws = torch.empty(ctx.bwd_bytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.rrt_nystrom_attention_backward_f32(C.byref(desc), C.byref(w), x.data_ptr(), dy.data_ptr(),
+                                                              stash.data_ptr(), stash.numel(), C.byref(g), _ptr(dx), n,
+                                                              ws.data_ptr(), ws.numel(), st),
+                       "rrt_nystrom_attention_backward_f32")
+        return (None, dx) + tuple(gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[2:]))
 
 
 class NystromAttention(HeadState, nn.Module):
@@ -76,6 +135,14 @@ class NystromAttention(HeadState, nn.Module):
                                       groups=heads, bias=False)
         self._dropout = dropout
         self._ws = None
+        self._train_enabled = False
+
+    def enable_training(self, mode=True):
+        """Opt in to (or out of) the training path: with it on, a call that needs a graph -- or ``train()`` with dropout --
+        runs the HIP forward-with-stash and backward under autograd instead of raising.  A plain attribute: not part of
+        ``state_dict``, kept by pickle and deepcopy.  Returns self."""
+        self._train_enabled = bool(mode)
+        return self
 
     def _desc(self):
         d = _lib.NystromDesc()
@@ -100,14 +167,22 @@ class NystromAttention(HeadState, nn.Module):
         if return_attn:
             raise NotImplementedError("rrt_mil_amd.NystromAttention: return_attn=True is not implemented")
         _no_cpu(x, "NystromAttention")
-        if self.training and self._dropout > 0.:
-            raise NotImplementedError("rrt_mil_amd.NystromAttention in train() with dropout: inference only, call eval() "
-                                      "under torch.no_grad()")
-        _no_graph(self, x, "NystromAttention")
+        stochastic = self.training and self._dropout > 0.
+        layer_path = getattr(self, "_train_enabled", False) and (stochastic or _needs_graph(self, x))
+        if not layer_path:
+            if stochastic:
+                raise NotImplementedError("rrt_mil_amd.NystromAttention in train() with dropout: inference only by default, "
+                                          "call eval() under torch.no_grad(), or opt in with enable_training()")
+            _no_graph(self, x, "NystromAttention")
         if x.dim() != 3 or x.shape[0] != 1:
             raise ValueError(f"NystromAttention expects (1, n, dim) -- batch > 1 is not supported -- got {tuple(x.shape)}")
         if x.shape[2] != self.dim:
             raise ValueError(f"expected feature dim {self.dim}, got {x.shape[2]}")
+        if layer_path:
+            with torch.autocast("cuda", enabled=False):      # fp32 in every context, as the one-call path
+                y = _NystromFn.apply(self._desc(), x[0].float(), self.to_qkv.weight, self.to_out[0].weight, self.to_out[0].bias,
+                                     self.res_conv.weight if self.residual else None)
+                return self.to_out[1](y.unsqueeze(0))
         lib = _lib.load()
         x2d = x[0].float().contiguous()
         n, dev = x2d.shape[0], x2d.device
@@ -168,6 +243,33 @@ class TransMIL(HeadState, nn.Module):
         self.apply(initialize_weights)
         self._act = {"relu": _lib.ACT_RELU, "gelu": _lib.ACT_GELU}.get(act.lower(), _lib.ACT_NONE)
         self._ws = None
+        self._train_enabled = False
+
+    def enable_training(self, mode=True):
+        """Opt in to (or out of) the training path, here and in both attention modules (see
+        NystromAttention.enable_training).  Returns self."""
+        self._train_enabled = bool(mode)
+        self.layer1.attn.enable_training(mode)
+        self.layer2.attn.enable_training(mode)
+        return self
+
+    def _forward_layers(self, x2d):
+        """The layer path under autograd: torch ops around the two HIP attentions -> (logits (1, n_classes), the
+        (1 + H*H, 512) rows before the last LayerNorm).  fp32 in every context."""
+        import torch.nn.functional as F
+        with torch.autocast("cuda", enabled=False):
+            h = self._fc1(x2d.float())
+            N, D = h.shape
+            H = _ceil_sqrt(N)
+            h = torch.cat([self.cls_token.reshape(1, D).float(), h, h[:H * H - N]])     # the wrap, then the cls token in front
+            h = h + self.layer1.attn(self.layer1.norm(h).unsqueeze(0))[0]
+            img = h[1:].t().reshape(1, D, H, H)
+            pe = img
+            for conv in (self.pos_layer.proj, self.pos_layer.proj1, self.pos_layer.proj2):
+                pe = pe + F.conv2d(img, conv.weight, conv.bias, padding=conv.kernel_size[0] // 2, groups=D)
+            h = torch.cat([h[:1], pe.reshape(D, H * H).t()])
+            h = h + self.layer2.attn(self.layer2.norm(h).unsqueeze(0))[0]
+            return self._fc2(self.norm(h[:1])), h
 
     def _desc_weights(self, keep):
         d, w = _lib.TransmilDesc(), _lib.TransmilWeights()
@@ -193,15 +295,21 @@ class TransMIL(HeadState, nn.Module):
         """One bag: x2d (N, input_dim) device tensor -> logits (1, n_classes) through ONE rrt_transmil_forward_f32 call
         (with ``return_features`` also the (1 + H*H, 512) rows before the last LayerNorm)."""
         _no_cpu(x2d, "TransMIL")
-        if self.training and any(isinstance(m, nn.Dropout) and m.p > 0. for m in self.modules()):
-            raise NotImplementedError("rrt_mil_amd.TransMIL in train() with dropout: inference only, call eval() under "
-                                      "torch.no_grad()")
-        _no_graph(self, x2d, "TransMIL")
+        stochastic = self.training and any(isinstance(m, nn.Dropout) and m.p > 0. for m in self.modules())
+        layer_path = getattr(self, "_train_enabled", False) and (stochastic or _needs_graph(self, x2d))
+        if not layer_path:
+            if stochastic:
+                raise NotImplementedError("rrt_mil_amd.TransMIL in train() with dropout: inference only by default, call eval() "
+                                          "under torch.no_grad(), or opt in with enable_training()")
+            _no_graph(self, x2d, "TransMIL")
         if x2d.dim() != 2:
             raise ValueError(f"forward_bag expects (N, input_dim), got {tuple(x2d.shape)}")
         n, in_dim = x2d.shape
         if in_dim != self._fc1[0].in_features:
             raise ValueError(f"expected feature dim {self._fc1[0].in_features}, got {in_dim}")
+        if layer_path:
+            logits, feat = self._forward_layers(x2d)
+            return (logits, feat) if return_features else logits
         lib = _lib.load()
         x2d = x2d.float().contiguous()
         keep = []
@@ -210,7 +318,7 @@ class TransMIL(HeadState, nn.Module):
         _lib.check(lib.rrt_transmil_workspace_size(C.byref(d), n, C.byref(need)), "rrt_transmil_workspace_size")
         dev = x2d.device
         ws = self._workspace(need.value, dev)
-        logits =torch.empty((1, self.n_classes), dtype=torch.float32, device=dev)
+        logits = torch.empty((1, self.n_classes), dtype=torch.float32, device=dev)
         feat = None
         if return_features:
             side = _ceil_sqrt(n)

@@ -986,6 +986,34 @@ int rrt_transmil_workspace_size(const rrt_transmil_desc *desc, int64_t n_tokens,
 int rrt_transmil_forward_f32(const rrt_transmil_desc *desc, const rrt_transmil_weights *w, const float *x, float *logits,
                              float *feat, int64_t n_tokens, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Attention maps: one query row of the Nystrom-approximated attention matrix (modules/nystrom_attention.py:143-147, the
+ * return_attn branch; exports added under ABI 29, no existing struct or signature touched).  Inference, exact fp32 on the
+ * fp32 matrix cores, no atomics, fixed summation order: the same inputs give the same bits.  Per head, for query row t of the
+ * unpadded sequence (pad = np - n zero rows in front):
+ *   a1 = softmax(q[pad + t] kl^T) [256];  r = a1 z [256];  lse3_i = logsumexp_j(ql_i . k_j) over ALL np keys;
+ *   attn[j] = sum_i r_i exp(ql_i . k_j - lse3_i),  j = 0 .. np - 1
+ * softmax(ql k^T) [256, np] is never written.  The row is NOT a probability vector: the pad keys keep their share (the n
+ * real columns do not sum to 1) and entries can be negative (z is an iterated pseudo-inverse).  The reference itself reads
+ * row 0 of the PADDED sequence, a zero pad row whenever n % 256 != 0; here the row is always pad + t.
+ *
+ * attn_row (stage): qkv, ql, kl, z as the stage entry points above leave them, lse3 [heads, 256], row_padded in
+ *   [0, n_padded) -> r [heads, 256] and attn [heads, n_padded] (ALL padded columns: sum_j attn[h, j] = sum_i r[h, i]).
+ * attention_row: rrt_nystrom_attention_f32 plus row `row` in [0, n) -> attn [heads, n] (the n real columns); y has the bits
+ *   of rrt_nystrom_attention_f32.  Its workspace is rrt_nystrom_attention_row_workspace_size's.
+ * transmil_forward_attn: rrt_transmil_forward_f32 plus attn1 / attn2 [heads, 1 + H * H] (either may be NULL): the cls
+ *   token's row in layer 1 / layer 2, the cls column (0) and the wrapped rows included; logits and feat have the bits of
+ *   rrt_transmil_forward_f32.  Its workspace is rrt_transmil_attn_workspace_size's.
+ * A row outside its range is RRT_E_UNSUPPORTED with "row" in rrt_strerror. */
+int rrt_nystrom_attn_row_f32(const float *qkv, const float *ql, const float *kl, const float *z, const float *lse3, float *r,
+                             float *attn, int64_t row_padded, int64_t n_padded, int32_t heads, void *stream);
+int rrt_nystrom_attention_row_workspace_size(const rrt_nystrom_desc *desc, int64_t n, size_t *bytes);
+int rrt_nystrom_attention_row_f32(const rrt_nystrom_desc *desc, const rrt_nystrom_weights *w, const float *x, float *y,
+                                  int64_t row, float *attn, int64_t n, void *workspace, size_t workspace_bytes, void *stream);
+int rrt_transmil_attn_workspace_size(const rrt_transmil_desc *desc, int64_t n_tokens, size_t *bytes);
+int rrt_transmil_forward_attn_f32(const rrt_transmil_desc *desc, const rrt_transmil_weights *w, const float *x, float *logits,
+                                  float *feat, float *attn1, float *attn2, int64_t n_tokens, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -305,6 +305,13 @@ SIGNATURES = {
     "rrt_nystrom_pinv_sim_backward_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
                                                                        C.c_void_p]),
     "rrt_nystrom_landmarks_backward_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_void_p]),
+    "rrt_nystrom_attn_row_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
+    "rrt_nystrom_attention_row_workspace_size": (C.c_int, [C.POINTER(NystromDesc), C.c_int64, C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_attention_row_f32": (C.c_int, [C.POINTER(NystromDesc), C.POINTER(NystromWeights), C.c_void_p, C.c_void_p,
+                                                C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_transmil_attn_workspace_size": (C.c_int, [C.POINTER(TransmilDesc), C.c_int64, C.POINTER(C.c_size_t)]),
+    "rrt_transmil_forward_attn_f32": (C.c_int, [C.POINTER(TransmilDesc), C.POINTER(TransmilWeights)] + [C.c_void_p] * 5 +
+                                      [C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32X3 = 0, 1, 2, 3

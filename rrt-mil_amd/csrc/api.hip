@@ -3300,6 +3300,74 @@ TransmilWs carve_transmil(const rrt_transmil_desc* d, int64_t N, char* base) {
   return ws;
 }
 
+// what a query row of the attention matrix needs on top of a forward's workspace of `front` bytes: lse | r, [heads, 256] each
+struct RowWs {
+  float *lse, *r;
+  size_t bytes;
+};
+RowWs carve_row(size_t front, int heads, char* base) {
+  RowWs ws{};
+  Arena a{base};
+  a.take<char>(front);
+  ws.lse = a.take((size_t)heads * 256);
+  ws.r = a.take((size_t)heads * 256);
+  ws.bytes = a.bytes();
+  return ws;
+}
+
+// row `row` (of the n unpadded rows) of the approximated attention matrix, columns 0 .. n - 1 -> attn [heads, n]; ws is as
+// nystrom_forward left it, with rw.lse filled by the same forward
+int nystrom_row(const rrt_nystrom_desc* d, int64_t row, float* attn, int64_t n, const NystromWs& ws, const RowWs& rw,
+                hipStream_t st) {
+  const int64_t pad = ws.np - n;
+  RRT_TRY(launch_nystrom_attn_row(ws.qkv, ws.ql, ws.kl, ws.z, rw.lse, rw.r, attn, (long)(pad + row), (long)ws.np, (long)pad,
+                                  (long)n, d->heads, st));
+  return RRT_OK;
+}
+
+// TransMIL.forward for both exports; everything checked by the caller.  attn1 / attn2 (either may be NULL; rw is read only
+// when one is not): the cls token's row of layer 1 / layer 2, [heads, 1 + H * H].  Without them the launches are those of
+// the plain forward, and logits / feat have the same bits either way (lse is one more store of the landmark merge).
+int transmil_forward(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, const float* x, float* logits, float* feat,
+                     float* attn1, float* attn2, int64_t n_tokens, const TransmilWs& ws, const RowWs& rw, hipStream_t st) {
+  const NystromWs nws = carve_nystrom(&desc->attn, ws.rows, ws.nys);
+  const int D = desc->attn.dim, R = (int)ws.rows;
+  int rc;
+  LinearEpilogue ep{};
+  ep.bias = w->fc1_b;
+  ep.act = desc->act;
+  RRT_TRY(launch_linear(x, w->fc1_w, ws.emb, (int)n_tokens, D, desc->input_dim, ep, st));
+  RRT_TRY(launch_transmil_assemble(ws.emb, w->cls_token, ws.seq, (int)n_tokens, R, D, st));
+  // layer 1: seq += Nystrom(LN(seq))
+  RRT_TRY(launch_layernorm(ws.seq, nullptr, w->layer[0].norm_w, w->layer[0].norm_b, ws.ln, R, D, st));
+  rc = nystrom_forward(&desc->attn, &w->layer[0].attn, ws.ln, ws.att, ws.rows, nws, st, attn1 ? rw.lse : nullptr);
+  if (!rc && attn1) rc = nystrom_row(&desc->attn, 0, attn1, ws.rows, nws, rw, st);
+  if (rc) return rc;
+  RRT_TRY(launch_add_cols(ws.seq, ws.att, (size_t)R, D, D, st));
+  // PPEG: row 0 passes through
+  RRT_TRY(hipMemcpyAsync(ws.seq2, ws.seq, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  RRT_TRY(launch_ppeg_side(ws.seq + D, w->pos_w, w->pos_b, ws.seq2 + D, ws.side, D, st));
+  // layer 2
+  RRT_TRY(launch_layernorm(ws.seq2, nullptr, w->layer[1].norm_w, w->layer[1].norm_b, ws.ln, R, D, st));
+  rc = nystrom_forward(&desc->attn, &w->layer[1].attn, ws.ln, ws.att, ws.rows, nws, st, attn2 ? rw.lse : nullptr);
+  if (!rc && attn2) rc = nystrom_row(&desc->attn, 0, attn2, ws.rows, nws, rw, st);
+  if (rc) return rc;
+  RRT_TRY(launch_add_cols(ws.seq2, ws.att, (size_t)R, D, D, st));
+  if (feat) RRT_TRY(hipMemcpyAsync(feat, ws.seq2, (size_t)R * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  // the head reads row 0 only
+  RRT_TRY(launch_layernorm(ws.seq2, nullptr, w->norm_w, w->norm_b, ws.ln, 1, D, st));
+  RRT_TRY(launch_transmil_head(ws.ln, w->fc2_w, w->fc2_b, logits, D, desc->n_classes, st));
+  return RRT_OK;
+}
+
+bool transmil_weights_ok(const rrt_transmil_desc* desc, const rrt_transmil_weights* w) {
+  if (!w->fc1_w || !w->cls_token || !w->norm_w || !w->norm_b || !w->fc2_w || !w->pos_w[0] || !w->pos_w[1] || !w->pos_w[2])
+    return false;
+  for (int i = 0; i < 2; ++i)
+    if (!w->layer[i].norm_w || !w->layer[i].norm_b || !nystrom_weights_ok(&desc->attn, &w->layer[i].attn)) return false;
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3415,38 +3483,66 @@ int rrt_transmil_forward_f32(const rrt_transmil_desc* desc, const rrt_transmil_w
   if (!desc || !w || !x || !logits) return RRT_E_INVALID;
   int rc = check_transmil(desc, n_tokens);
   if (rc) return rc;
-  if (!w->fc1_w || !w->cls_token || !w->norm_w || !w->norm_b || !w->fc2_w || !w->pos_w[0] || !w->pos_w[1] || !w->pos_w[2])
-    return RRT_E_INVALID;
-  for (int i = 0; i < 2; ++i)
-    if (!w->layer[i].norm_w || !w->layer[i].norm_b || !nystrom_weights_ok(&desc->attn, &w->layer[i].attn)) return RRT_E_INVALID;
+  if (!transmil_weights_ok(desc, w)) return RRT_E_INVALID;
   if (!workspace || workspace_bytes < carve_transmil(desc, n_tokens, nullptr).bytes) return RRT_E_WORKSPACE;
-  const TransmilWs ws = carve_transmil(desc, n_tokens, (char*)workspace);
-  const NystromWs nws = carve_nystrom(&desc->attn, ws.rows, ws.nys);
-  hipStream_t st = (hipStream_t)stream;
-  const int D = desc->attn.dim, R = (int)ws.rows;
-  LinearEpilogue ep{};
-  ep.bias = w->fc1_b;
-  ep.act = desc->act;
-  RRT_TRY(launch_linear(x, w->fc1_w, ws.emb, (int)n_tokens, D, desc->input_dim, ep, st));
-  RRT_TRY(launch_transmil_assemble(ws.emb, w->cls_token, ws.seq, (int)n_tokens, R, D, st));
-  // layer 1: seq += Nystrom(LN(seq))
-  RRT_TRY(launch_layernorm(ws.seq, nullptr, w->layer[0].norm_w, w->layer[0].norm_b, ws.ln, R, D, st));
-  rc = nystrom_forward(&desc->attn, &w->layer[0].attn, ws.ln, ws.att, ws.rows, nws, st);
+  return transmil_forward(desc, w, x, logits, feat, nullptr, nullptr, n_tokens, carve_transmil(desc, n_tokens, (char*)workspace),
+                          RowWs{}, (hipStream_t)stream);
+}
+
+int rrt_transmil_attn_workspace_size(const rrt_transmil_desc* desc, int64_t n_tokens, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_transmil(desc, n_tokens);
   if (rc) return rc;
-  RRT_TRY(launch_add_cols(ws.seq, ws.att, (size_t)R, D, D, st));
-  // PPEG: row 0 passes through
-  RRT_TRY(hipMemcpyAsync(ws.seq2, ws.seq, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, st));
-  RRT_TRY(launch_ppeg_side(ws.seq + D, w->pos_w, w->pos_b, ws.seq2 + D, ws.side, D, st));
-  // layer 2
-  RRT_TRY(launch_layernorm(ws.seq2, nullptr, w->layer[1].norm_w, w->layer[1].norm_b, ws.ln, R, D, st));
-  rc = nystrom_forward(&desc->attn, &w->layer[1].attn, ws.ln, ws.att, ws.rows, nws, st);
-  if (rc) return rc;
-  RRT_TRY(launch_add_cols(ws.seq2, ws.att, (size_t)R, D, D, st));
-  if (feat) RRT_TRY(hipMemcpyAsync(feat, ws.seq2, (size_t)R * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-  // the head reads row 0 only
-  RRT_TRY(launch_layernorm(ws.seq2, nullptr, w->norm_w, w->norm_b, ws.ln, 1, D, st));
-  RRT_TRY(launch_transmil_head(ws.ln, w->fc2_w, w->fc2_b, logits, D, desc->n_classes, st));
+  *bytes = carve_row(carve_transmil(desc, n_tokens, nullptr).bytes, desc->attn.heads, nullptr).bytes;
   return RRT_OK;
+}
+
+int rrt_transmil_forward_attn_f32(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, const float* x, float* logits,
+                                  float* feat, float* attn1, float* attn2, int64_t n_tokens, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  if (!desc || !w || !x || !logits) return RRT_E_INVALID;
+  int rc = check_transmil(desc, n_tokens);
+  if (rc) return rc;
+  if (!transmil_weights_ok(desc, w)) return RRT_E_INVALID;
+  const size_t front = carve_transmil(desc, n_tokens, nullptr).bytes;
+  if (!workspace || workspace_bytes < carve_row(front, desc->attn.heads, nullptr).bytes) return RRT_E_WORKSPACE;
+  return transmil_forward(desc, w, x, logits, feat, attn1, attn2, n_tokens, carve_transmil(desc, n_tokens, (char*)workspace),
+                          carve_row(front, desc->attn.heads, (char*)workspace), (hipStream_t)stream);
+}
+
+int rrt_nystrom_attn_row_f32(const float* qkv, const float* ql, const float* kl, const float* z, const float* lse3, float* r,
+                             float* attn, int64_t row_padded, int64_t n_padded, int32_t heads, void* stream) {
+  if (!qkv || !ql || !kl || !z || !lse3 || !r || !attn) return RRT_E_INVALID;
+  int rc = check_nystrom_np(n_padded);
+  if (!rc) rc = check_nystrom_heads(heads);
+  if (rc) return rc;
+  if (row_padded < 0 || row_padded >= n_padded) return unsupported("nystrom: row_padded must be in [0, n_padded)");
+  return (int)launch_nystrom_attn_row(qkv, ql, kl, z, lse3, r, attn, (long)row_padded, (long)n_padded, 0, (long)n_padded, heads,
+                                      (hipStream_t)stream);
+}
+
+int rrt_nystrom_attention_row_workspace_size(const rrt_nystrom_desc* desc, int64_t n, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_nystrom(desc, n);
+  if (rc) return rc;
+  *bytes = carve_row(carve_nystrom(desc, n, nullptr).bytes, desc->heads, nullptr).bytes;
+  return RRT_OK;
+}
+
+int rrt_nystrom_attention_row_f32(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w, const float* x, float* y,
+                                  int64_t row, float* attn, int64_t n, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!desc || !w || !x || !y || !attn) return RRT_E_INVALID;
+  int rc = check_nystrom(desc, n);
+  if (rc) return rc;
+  if (!nystrom_weights_ok(desc, w)) return RRT_E_INVALID;
+  if (row < 0 || row >= n) return unsupported("nystrom: row must be in [0, n)");
+  const size_t front = carve_nystrom(desc, n, nullptr).bytes;
+  if (!workspace || workspace_bytes < carve_row(front, desc->heads, nullptr).bytes) return RRT_E_WORKSPACE;
+  const NystromWs ws = carve_nystrom(desc, n, (char*)workspace);
+  const RowWs rw = carve_row(front, desc->heads, (char*)workspace);
+  rc = nystrom_forward(desc, w, x, y, n, ws, (hipStream_t)stream, rw.lse);
+  if (rc) return rc;
+  return nystrom_row(desc, row, attn, n, ws, rw, (hipStream_t)stream);
 }
 
 }  // extern "C"

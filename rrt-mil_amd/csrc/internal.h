@@ -385,6 +385,11 @@ hipError_t launch_nystrom_pinv(const float* a2, float* z, float* ws, int heads, 
 hipError_t launch_nystrom_zav(const float* z, const float* av, float* wz, int heads, hipStream_t st);
 hipError_t launch_nystrom_output(const float* qkv, const float* kl, const float* wz, const float* conv_w, float* o, long np,
                                  int heads, int ks, hipStream_t st);
+// One query row of the approximated attention matrix (nystrom_row.hip): r [heads, 256] = softmax(q[row_padded] kl^T) z and
+// attn [heads, out_ld], whose entry key - col0 is sum_i r_i exp(ql_i . k_key - lse3_i) for the keys col0 .. np - 1
+hipError_t launch_nystrom_attn_row(const float* qkv, const float* ql, const float* kl, const float* z, const float* lse3,
+                                   float* r, float* attn, long row_padded, long np, long col0, long out_ld, int heads,
+                                   hipStream_t st);
 // Nystrom attention backward (nystrom_bwd.hip).  d_qkv [np, 3 * heads * 64] is the gradient of the SCALED q | k | v.
 //  output_backward   writes the q and v thirds of d_qkv and zeroes the k third; ws: nystrom_output_bwd_floats
 //  lattn_backward    ADDS dk, dv into the k and v thirds, writes d_ql; av / lse as launch_nystrom_lattn left them;

@@ -11,6 +11,9 @@ or ``train()`` with dropout, raises ``NotImplementedError`` -- use ``eval()`` un
 Training is opt-in: after ``model.enable_training()`` a call that needs a graph (or ``train()`` with dropout) takes the layer
 path -- torch ops around ``NystromAttention``, whose forward-with-stash and backward are the HIP kernels of csrc/nystrom.hip and
 csrc/nystrom_bwd.hip under a ``torch.autograd.Function``; a call that needs no graph still takes the one-call path, bit for bit.
+Attention maps are an inference output: ``TransMIL.forward_bag(x, return_attn=True)`` adds the class token's row of the
+Nystrom-approximated attention matrix of both layers (rrt_transmil_forward_attn_f32, csrc/nystrom_row.hip), and
+``NystromAttention.attention_row(x, row)`` any one row; with either, a call that needs a graph raises, opt-in or not.
 The arithmetic is exact fp32 on the fp32 matrix cores in every context: under ``torch.autocast`` the modules STILL compute
 in fp32 (there is no 16-bit path for the pseudo-inverse iteration, whose conditioning does not survive 8 mantissa bits).
 """
@@ -113,7 +116,7 @@ class _NystromFn(torch.autograd.Function):
 class NystromAttention(HeadState, nn.Module):
     """modules/nystrom_attention.py:32-149.  ``forward(x)`` with x (1, n, dim) -> (1, n, dim); ``mask=`` and
     ``return_attn=True`` are not implemented (the reference's mask branch names undefined variables, and TransMIL passes
-    neither).  The HIP path supports dim_head = 64, num_landmarks = 256, heads <= 16, pinv_iterations <= 16, an odd
+    neither); ``attention_row(x, row)`` gives one row of the approximated attention matrix.  The HIP path supports dim_head = 64, num_landmarks = 256, heads <= 16, pinv_iterations <= 16, an odd
     residual_conv_kernel <= 63 and dim a multiple of 32 up to 1024; anything else raises NotImplementedError at the call."""
 
     def __init__(self, dim, dim_head=64, heads=8, num_landmarks=256, pinv_iterations=6, residual=True,
@@ -197,6 +200,46 @@ class NystromAttention(HeadState, nn.Module):
             _lib.check(lib.rrt_nystrom_attention_f32(C.byref(d), C.byref(w), x2d.data_ptr(), y.data_ptr(), n,
                                                      ws.data_ptr(), ws.numel(), st), "rrt_nystrom_attention_f32")
         return y.unsqueeze(0)
+
+    def attention_row(self, x, row=0):
+        """x (1, n, dim), ``row`` in [0, n) -> (y (1, n, dim), attn (1, heads, n)): ``forward(x)``, bit for bit, and row
+        ``row`` of the Nystrom-approximated attention matrix over the n tokens (the reference's ``return_attn=True`` is row 0
+        without column 0 when n % 256 == 0; at other n it reads a zero pad row, here the row is always the token's own).
+        One rrt_nystrom_attention_row_f32 call; softmax(ql k^T) is never materialised.  Inference only: ``eval()`` under
+        ``torch.no_grad()``.  Not a probability vector: the front pad keys keep their share, so the row does not sum to 1,
+        and entries can be negative (the pseudo-inverse is an approximation)."""
+        _no_cpu(x, "NystromAttention")
+        _no_map_with_graph(self, x, self.training and self._dropout > 0., "NystromAttention.attention_row")
+        if x.dim() != 3 or x.shape[0] != 1:
+            raise ValueError(f"NystromAttention expects (1, n, dim) -- batch > 1 is not supported -- got {tuple(x.shape)}")
+        if x.shape[2] != self.dim:
+            raise ValueError(f"expected feature dim {self.dim}, got {x.shape[2]}")
+        lib = _lib.load()
+        x2d = x[0].float().contiguous()
+        n, dev = x2d.shape[0], x2d.device
+        if not 0 <= int(row) < n:
+            raise ValueError(f"row must be in [0, {n}), got {row}")
+        d, keep = self._desc(), []
+        w = self._weights(keep)
+        need = C.c_size_t()
+        _lib.check(lib.rrt_nystrom_attention_row_workspace_size(C.byref(d), n, C.byref(need)),
+                   "rrt_nystrom_attention_row_workspace_size")
+        ws = self._workspace(need.value, dev)
+        y = torch.empty((n, self.dim), dtype=torch.float32, device=dev)
+        attn = torch.empty((self.heads, n), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.rrt_nystrom_attention_row_f32(C.byref(d), C.byref(w), x2d.data_ptr(), y.data_ptr(), int(row),
+                                                         attn.data_ptr(), n, ws.data_ptr(), ws.numel(), st),
+                       "rrt_nystrom_attention_row_f32")
+        return y.unsqueeze(0), attn.unsqueeze(0)
+
+
+def _no_map_with_graph(module, x, stochastic, who):
+    """the attention map is an inference output, with or without enable_training()"""
+    if stochastic or _needs_graph(module, x):
+        raise NotImplementedError(f"rrt_mil_amd.{who}: the attention map is an inference output (no gradient flows through "
+                                  "it, and the training path does not compute it): call it in eval() under torch.no_grad()")
 
 
 class _NystromLayer(nn.Module):
@@ -291,11 +334,20 @@ class TransMIL(HeadState, nn.Module):
         w.fc2_w, w.fc2_b = p(self._fc2.weight), p(self._fc2.bias)
         return d, w
 
-    def forward_bag(self, x2d, return_features=False):
+    def forward_bag(self, x2d, return_features=False, return_attn=False):
         """One bag: x2d (N, input_dim) device tensor -> logits (1, n_classes) through ONE rrt_transmil_forward_f32 call
-        (with ``return_features`` also the (1 + H*H, 512) rows before the last LayerNorm)."""
+        (with ``return_features`` also the (1 + H*H, 512) rows before the last LayerNorm).
+
+        With ``return_attn`` the result gains, last, ``attn`` (2, heads, N), indexed [layer, head, patch]: the class token's
+        row of the Nystrom-approximated attention matrix in layer 1 and in layer 2, without its own column, the wrap folded
+        back (the sequence is [cls, h_0 .. h_{N-1}, h_0 .. h_{H*H-N-1}], so patch i < H*H - N gets the sum of its two
+        columns).  One rrt_transmil_forward_attn_f32 call plus two torch ops for the fold; the logits (and features) have
+        the bits of the call without it.  Inference only.  Not a probability vector: the cls column and the front pad keys
+        keep their share, so a row does not sum to 1, and entries can be negative."""
         _no_cpu(x2d, "TransMIL")
         stochastic = self.training and any(isinstance(m, nn.Dropout) and m.p > 0. for m in self.modules())
+        if return_attn:
+            _no_map_with_graph(self, x2d, stochastic, "TransMIL(return_attn=True)")
         layer_path = getattr(self, "_train_enabled", False) and (stochastic or _needs_graph(self, x2d))
         if not layer_path:
             if stochastic:
@@ -315,33 +367,45 @@ class TransMIL(HeadState, nn.Module):
         keep = []
         d, w = self._desc_weights(keep)
         need = C.c_size_t()
-        _lib.check(lib.rrt_transmil_workspace_size(C.byref(d), n, C.byref(need)), "rrt_transmil_workspace_size")
+        size_fn = lib.rrt_transmil_attn_workspace_size if return_attn else lib.rrt_transmil_workspace_size
+        _lib.check(size_fn(C.byref(d), n, C.byref(need)), size_fn.__name__)
         dev = x2d.device
         ws = self._workspace(need.value, dev)
         logits = torch.empty((1, self.n_classes), dtype=torch.float32, device=dev)
         feat = None
+        side = _ceil_sqrt(n)
         if return_features:
-            side = _ceil_sqrt(n)
             feat = torch.empty((1 + side * side, 512), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.rrt_transmil_forward_f32(C.byref(d), C.byref(w), x2d.data_ptr(), logits.data_ptr(), _ptr(feat), n,
-                                                    ws.data_ptr(), ws.numel(), st), "rrt_transmil_forward_f32")
-        return (logits, feat) if return_features else logits
+            if not return_attn:
+                _lib.check(lib.rrt_transmil_forward_f32(C.byref(d), C.byref(w), x2d.data_ptr(), logits.data_ptr(), _ptr(feat), n,
+                                                        ws.data_ptr(), ws.numel(), st), "rrt_transmil_forward_f32")
+                return (logits, feat) if return_features else logits
+            rows = torch.empty((2, d.attn.heads, 1 + side * side), dtype=torch.float32, device=dev)
+            _lib.check(lib.rrt_transmil_forward_attn_f32(C.byref(d), C.byref(w), x2d.data_ptr(), logits.data_ptr(), _ptr(feat),
+                                                         rows[0].data_ptr(), rows[1].data_ptr(), n, ws.data_ptr(), ws.numel(),
+                                                         st), "rrt_transmil_forward_attn_f32")
+        # without the cls column; the wrapped rows' columns go back to their patches
+        attn = rows[:, :, 1:1 + n].clone()
+        attn[:, :, :side * side - n] += rows[:, :, 1 + n:]
+        return (logits, feat, attn) if return_features else (logits, attn)
 
-    def forward_bags(self, bags):
-        """A list of independent slides (each (N_i, input_dim) or (1, N_i, input_dim)) -> list of logits: a plain loop of
-        forward_bag on the caller's stream."""
-        return [self.forward(b) for b in bags]
+    def forward_bags(self, bags, return_attn=False):
+        """A list of independent slides (each (N_i, input_dim) or (1, N_i, input_dim)) -> list of logits (with
+        ``return_attn``: of (logits, attn) pairs): a plain loop of forward_bag on the caller's stream."""
+        return [self.forward(b, return_attn=return_attn) for b in bags]
 
-    def forward(self, x):
+    def forward(self, x, return_attn=False):
+        """x (1, N, input_dim) or (N, input_dim) -> logits (1, n_classes); with ``return_attn`` -> (logits, attn (2, heads, N)),
+        see forward_bag."""
         _no_cpu(x, "TransMIL")
         if x.dim() == 3:
             if x.shape[0] != 1:
                 raise ValueError(f"TransMIL expects one bag, (1, N, input_dim) or (N, input_dim) -- batch > 1 is not "
                                  f"supported -- got {tuple(x.shape)}")
             x = x[0]
-        return self.forward_bag(x)
+        return self.forward_bag(x, return_attn=return_attn)
 
 
 def _ceil_sqrt(n):

@@ -257,6 +257,43 @@ int rrt_linear_unpartition_residual_f32(const float *A, const float *B, const fl
                                         const float *resid, float *out, int32_t N, int32_t K,
                                         const rrt_grid *g, int32_t compute, void *stream);
 
+/* The kernel form one GEMM of this library takes (exports added under ABI 29, no existing struct or signature touched).
+ * Host only, nothing is launched; the answer comes from the function the launchers of csrc/linear_f32.hip dispatch from
+ * (plan_linear), so it cannot drift from what runs.  tests/test_linear_form_matrix.py asserts the form of every case with it
+ * and tests/test_linear_form_grid_cpu.py sweeps it against the instantiations that file compiles.
+ *   operands  RRT_LINEAR_OPS_F32   fp32 operands in memory (compute = RRT_COMPUTE_F32 / BF16 / F16 rounds them after LDS)
+ *             RRT_LINEAR_OPS_16    16-bit images (rrt_cast16; compute = RRT_COMPUTE_BF16 / F16), K % 64 == 0
+ *             RRT_LINEAR_OPS_SPLIT split images (rrt_cast_split; compute = RRT_COMPUTE_F32X3)
+ *   epilogue  RRT_LINEAR_EPI_*: plain (bias, q-scale), activation, un-partition + residual, dropout (fp32 training), both
+ *   solo      the scheduling hint of rrt_encoder_desc.solo;  zero64: the 64-counter side job is set
+ * plan[RRT_LINEAR_PLAN_INTS]: [0] kernel RRT_LINEAR_KERNEL_*, [1] MT, [2] NT (block tile = 16 MT x 64 NT), [3] cap of the
+ * persistent grid (0 for split-K), [4] tiles, [5] grid, [6] 1 = the warp-specialised kernel's deferred-epilogue instantiation,
+ * [7] split-K: K groups per block (else 0), [8] split-K: 1 = the dropout instantiation, [9] epilogue of the instantiation
+ * (RRT_LINEAR_EPI_*), [10] MFMA operand precision of the instantiation (RRT_COMPUTE_*), [11] 0.
+ * What the kernel itself decides from its arguments (the straight-line un-partition store: N % (64 NT) == 0 and q_cols == 0;
+ * the 32-bit byte-offset limit of the buffer stores) is not reported.  RRT_E_UNSUPPORTED for what the launchers refuse. */
+enum { RRT_LINEAR_OPS_F32 = 0, RRT_LINEAR_OPS_16 = 1, RRT_LINEAR_OPS_SPLIT = 2 };
+enum { RRT_LINEAR_EPI_PLAIN = 0, RRT_LINEAR_EPI_UNPART = 1, RRT_LINEAR_EPI_ACT = 2, RRT_LINEAR_EPI_UNPART_DROP = 3,
+       RRT_LINEAR_EPI_DROP = 4 };
+enum { RRT_LINEAR_KERNEL_PLAIN = 0, RRT_LINEAR_KERNEL_WS = 1, RRT_LINEAR_KERNEL_SPLITK = 2 };
+#define RRT_LINEAR_PLAN_INTS 12
+int rrt_linear_plan(int64_t M, int32_t N, int32_t K, int32_t compute, int32_t operands, int32_t epilogue,
+                    int32_t solo, int32_t zero64, int32_t *plan);
+
+/* Stage entry for tests: one GEMM with the WHOLE epilogue the forwards can ask for, so that every kernel form plan_linear can
+ * pick is reachable at a small shape (the rrt_linear*_f32 entries above and below never set solo, dropout or zero64).
+ * A, B: fp32 [M, K] / [N, K], or 16-bit / split images of them, per `operands`; bias [N] or NULL; columns [0, q_cols) times
+ * q_scale after the bias; act = RRT_ACT_*; resid (may be NULL) [g->L, N] with g: C row = token, A row = slot, M == g->H^2;
+ * drop_p > 0: the training forward's dropout epilogue, threshold, scale and seed derived from (drop_p, drop_seed, drop_layer)
+ * exactly as rrt_encoder_forward_train_f32 derives them for R-MSA layer drop_layer (100: CR-MSA); zero64 (may be NULL): 64
+ * ints that block 0 sets to 0.  Launches what the launchers launch and nothing else; RRT_E_INVALID on NULL / non-positive /
+ * inconsistent arguments, RRT_E_UNSUPPORTED where the launchers refuse (dropout outside exact fp32 or with an activation, an
+ * activation together with resid or on split images, K not a multiple of 32 / 64). */
+int rrt_debug_linear_f32(const void *A, const void *B, const float *bias, const float *resid, float *C,
+                         int64_t M, int32_t N, int32_t K, const rrt_grid *g, int32_t operands, int32_t compute,
+                         int32_t q_cols, float q_scale, int32_t act, int32_t solo,
+                         float drop_p, uint64_t drop_seed, int32_t drop_layer, int32_t *zero64, void *stream);
+
 /* Region attention core (rmsa.py:103-122): qkv [n_regions*P, 3*dim] (q already scaled),
  * EPEG taps pe_w [heads, epeg_k] (NULL/0 = none; pe bias is softmax-invariant and not needed)
  * -> o [n_regions*P, dim] (heads merged).

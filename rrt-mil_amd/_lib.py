@@ -166,6 +166,11 @@ SIGNATURES = {
     "rrt_linear_unpartition_residual_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Grid),
                                                       C.c_int32, C.c_void_p]),
+    "rrt_linear_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                  C.POINTER(C.c_int32)]),
+    "rrt_debug_linear_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_int32, C.POINTER(Grid), C.c_int32,
+                                                          C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_float,
+                                                          C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
     "rrt_region_attention_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "rrt_region_attention_hd_supported": (C.c_int, [C.c_int32] * 4),
@@ -320,6 +325,12 @@ EPEG_ATTN, EPEG_VALUE_BF, EPEG_VALUE_AF = 0, 1, 2
 BAGPOOL_MEAN, BAGPOOL_MAX, BAGPOOL_ATTN, BAGPOOL_ATTN_GATED, BAGPOOL_ATTN_DECONF = range(5)     # rrt_bagmil_desc.pool
 
 PLAN_FUSED, PLAN_FUSED_PROJ, PLAN_FUSED16, PLAN_FUSED_X3, PLAN_CRMSA_PARTS, PLAN_ATTN_HD = 1, 2, 4, 8, 16, 32     # rrt_encoder_plan flags
+# rrt_linear_plan / rrt_debug_linear_f32 (enums in include/rrt_hip.h)
+LINEAR_OPS_F32, LINEAR_OPS_16, LINEAR_OPS_SPLIT = 0, 1, 2
+LINEAR_EPI_PLAIN, LINEAR_EPI_UNPART, LINEAR_EPI_ACT, LINEAR_EPI_UNPART_DROP, LINEAR_EPI_DROP = 0, 1, 2, 3, 4
+LINEAR_KERNEL_PLAIN, LINEAR_KERNEL_WS, LINEAR_KERNEL_SPLITK = 0, 1, 2
+LINEAR_PLAN_INTS = 12
+LINEAR_PLAN_FIELDS = ("kernel", "mt", "nt", "cap", "ntiles", "grid", "defer", "kg", "drop", "mode", "prec")
 # stage-boundary event slots of rrt_encoder_forward_events_f32 (enum in include/rrt_hip.h)
 EV_START, EV_LN_PARTITION, EV_QKV, EV_ATTN, EV_PROJ, EV_CR_COMBINE, EV_CR_INNER, EV_END, EV_COUNT = range(9)
 
@@ -379,3 +390,10 @@ def region_grid(L, region_num=8, region_size=0, min_region_num=0, min_region_rat
     check(load().rrt_region_grid(L, region_num, region_size, min_region_num, min_region_ratio, C.byref(g)),
           "rrt_region_grid")
     return g
+
+
+def linear_plan(M, N, K, compute=COMPUTE_F32, operands=LINEAR_OPS_F32, epilogue=LINEAR_EPI_PLAIN, solo=0, zero64=0):
+    """The kernel form a GEMM of this shape takes (rrt_linear_plan; host only): dict over LINEAR_PLAN_FIELDS."""
+    out = (C.c_int32 * LINEAR_PLAN_INTS)()
+    check(load().rrt_linear_plan(M, N, K, compute, operands, epilogue, solo, zero64, out), "rrt_linear_plan")
+    return dict(zip(LINEAR_PLAN_FIELDS, out))

@@ -2812,6 +2812,92 @@ int make_branch(const float* bs, Branch* b) {
 }
 }  // namespace
 
+// ---- the GEMM family's form report and its stage entry (tests/test_linear_form_matrix.py, test_linear_form_grid_cpu.py)
+namespace {
+// the fields of a LinearEpilogue that plan_linear looks at, for an RRT_LINEAR_EPI_* value; `set` stands for "this pointer is
+// given" (never followed)
+int epilogue_kind(int32_t epilogue, int32_t compute, int32_t operands, int32_t K, int32_t solo, bool zero64, LinearEpilogue* ep) {
+  static const float set_f = 0.f;
+  static int set_i = 0;
+  if (epilogue < RRT_LINEAR_EPI_PLAIN || epilogue > RRT_LINEAR_EPI_DROP) return RRT_E_INVALID;
+  if (operands == RRT_LINEAR_OPS_F32) {
+    if (compute < 0 || compute > 2) return unsupported("linear: fp32 operands take RRT_COMPUTE_F32 / BF16 / F16");
+  } else if (operands == RRT_LINEAR_OPS_16) {
+    if (compute != RRT_COMPUTE_BF16 && compute != RRT_COMPUTE_F16) return unsupported("linear: 16-bit images take RRT_COMPUTE_BF16 / F16");
+  } else if (operands == RRT_LINEAR_OPS_SPLIT) {
+    if (compute != RRT_COMPUTE_F32X3) return unsupported("linear: split images take RRT_COMPUTE_F32X3");
+  } else {
+    return RRT_E_INVALID;
+  }
+  if (K % (operands == RRT_LINEAR_OPS_16 ? 64 : 32))
+    return unsupported("linear: K must be a multiple of 32 (16-bit images: 64)");
+  ep->prec = operands == RRT_LINEAR_OPS_SPLIT ? 0 : compute;
+  ep->act = epilogue == RRT_LINEAR_EPI_ACT ? RRT_ACT_RELU : RRT_ACT_NONE;
+  ep->resid = (epilogue == RRT_LINEAR_EPI_UNPART || epilogue == RRT_LINEAR_EPI_UNPART_DROP) ? &set_f : nullptr;
+  ep->drop_on = epilogue == RRT_LINEAR_EPI_DROP || epilogue == RRT_LINEAR_EPI_UNPART_DROP;
+  ep->solo = solo != 0;
+  ep->zero64 = zero64 ? &set_i : nullptr;
+  return RRT_OK;
+}
+}  // namespace
+
+int rrt_linear_plan(int64_t M, int32_t N, int32_t K, int32_t compute, int32_t operands, int32_t epilogue, int32_t solo,
+                    int32_t zero64, int32_t* plan) {
+  if (!plan || M <= 0 || M > 0x7FFFFFFF || N <= 0 || K <= 0) return RRT_E_INVALID;
+  for (int i = 0; i < RRT_LINEAR_PLAN_INTS; ++i) plan[i] = 0;
+  LinearEpilogue ep{};
+  int rc = epilogue_kind(epilogue, compute, operands, K, solo, zero64 != 0, &ep);
+  if (rc) return rc;
+  LinearPlan pl{};
+  if (plan_linear(operands, (int)M, N, K, ep, &pl) != hipSuccess)
+    return unsupported("linear: the launcher of this operand kind refuses the combination (K % 32 / % 64, dropout outside exact "
+                       "fp32 or with an activation, activation on split images)");
+  const int v[RRT_LINEAR_PLAN_INTS] = {pl.kernel, pl.mt, pl.nt, pl.cap, pl.ntiles, pl.grid, pl.defer, pl.kg, pl.drop, pl.mode, pl.prec, 0};
+  for (int i = 0; i < RRT_LINEAR_PLAN_INTS; ++i) plan[i] = v[i];
+  return RRT_OK;
+}
+
+int rrt_debug_linear_f32(const void* A, const void* B, const float* bias, const float* resid, float* C, int64_t M, int32_t N,
+                         int32_t K, const rrt_grid* g, int32_t operands, int32_t compute, int32_t q_cols, float q_scale,
+                         int32_t act, int32_t solo, float drop_p, uint64_t drop_seed, int32_t drop_layer, int32_t* zero64,
+                         void* stream) {
+  if (!A || !B || !C || M <= 0 || M > 0x7FFFFFFF || N <= 0 || K <= 0 || (resid && !g)) return RRT_E_INVALID;
+  if (q_cols < 0 || q_cols > N || act < RRT_ACT_NONE || act > RRT_ACT_SIGMOID || drop_layer < 0) return RRT_E_INVALID;
+  DropCfg dc{};
+  if (make_drop(drop_p, &dc)) return RRT_E_INVALID;
+  if (resid && act) return unsupported("linear: the un-partition epilogue has no activation");
+  const bool drop_on = dc.thresh != 0;
+  const int32_t epilogue = drop_on ? (resid ? RRT_LINEAR_EPI_UNPART_DROP : RRT_LINEAR_EPI_DROP)
+                           : resid ? RRT_LINEAR_EPI_UNPART : act ? RRT_LINEAR_EPI_ACT : RRT_LINEAR_EPI_PLAIN;
+  if (drop_on && act) return unsupported("linear: the dropout epilogue has no activation");
+  LinearEpilogue ep{};
+  int rc = epilogue_kind(epilogue, compute, operands, K, solo, zero64 != nullptr, &ep);
+  if (rc) return rc;
+  ep.act = act;
+  ep.bias = bias;
+  ep.q_cols = q_cols;
+  ep.q_scale = q_scale;
+  ep.resid = resid;
+  ep.zero64 = zero64;
+  if (resid) {
+    ep.g = to_dev(*g);
+    if (M != ep.g.Np) return RRT_E_INVALID;
+  }
+  if (drop_on) {
+    ep.drop_thresh = dc.thresh;
+    ep.drop_scale = dc.scale;
+    ep.drop_seed = dc.seed(drop_seed, drop_layer);
+  }
+  LinearPlan pl{};
+  if (plan_linear(operands, (int)M, N, K, ep, &pl) != hipSuccess)
+    return unsupported("linear: the launcher of this operand kind refuses the combination (K % 32 / % 64, dropout outside exact "
+                       "fp32 or with an activation, activation on split images)");
+  hipStream_t st = (hipStream_t)stream;
+  if (operands == RRT_LINEAR_OPS_16) return (int)launch_linear16(A, B, C, (int)M, N, K, ep, st);
+  if (operands == RRT_LINEAR_OPS_SPLIT) return (int)launch_linear_split(A, B, C, (int)M, N, K, ep, st);
+  return (int)launch_linear((const float*)A, (const float*)B, C, (int)M, N, K, ep, st);
+}
+
 int rrt_encoder_forward_train_f32(const rrt_encoder_desc* desc, const rrt_encoder_weights* w, const float* x,
                                   float* y, int64_t n_tokens, void* stash, size_t stash_bytes, float drop_p,
                                   uint64_t drop_seed, const float* branch_scale, void* stream) {

@@ -62,6 +62,25 @@ struct LinearEpilogue {
 hipError_t launch_linear(const float* A, const float* B, float* C, int M, int N, int K,
                          const LinearEpilogue& ep, hipStream_t st);
 
+// The kernel form of one GEMM (linear_f32.hip::plan_linear): the three launchers launch from it and rrt_linear_plan reports
+// it -- there is no second copy of the tile-shape rules.  Values as the RRT_LINEAR_* constants of rrt_hip.h.
+enum { LINEAR_OPS_F32 = RRT_LINEAR_OPS_F32, LINEAR_OPS_16 = RRT_LINEAR_OPS_16, LINEAR_OPS_SPLIT = RRT_LINEAR_OPS_SPLIT };
+enum { LINEAR_KERNEL_PLAIN = RRT_LINEAR_KERNEL_PLAIN, LINEAR_KERNEL_WS = RRT_LINEAR_KERNEL_WS,
+       LINEAR_KERNEL_SPLITK = RRT_LINEAR_KERNEL_SPLITK };
+struct LinearPlan {
+  int kernel;            // LINEAR_KERNEL_*
+  int mt, nt;            // block tile = (16 mt) x (64 nt)
+  int cap;               // resident-block cap of the persistent grid (0: split-K, one tile per block)
+  int tiles_n, ntiles, grid;
+  int defer;             // warp-specialised kernel: the DEFER instantiation (a block gets a second tile)
+  int kg, drop;          // split-K: K groups per block, the DROP instantiation
+  int mode;              // epilogue instantiation, RRT_LINEAR_EPI_* (= linear_f32.hip MODE_*)
+  int prec;              // MFMA operand precision of the instantiation: RRT_COMPUTE_*
+};
+// ops: LINEAR_OPS_*; of ep only prec, act, drop_on, solo and whether resid / zero64 are set are looked at.
+// hipErrorInvalidValue for what the launcher of that operand kind refuses.
+hipError_t plan_linear(int ops, int M, int N, int K, const LinearEpilogue& ep, LinearPlan* out);
+
 // ---- 16-bit operand path of the reduced-precision modes (cast16.hip, linear_f32.hip IN16, rmsa_fused16.hip)
 constexpr int CAST16_MAX_JOBS = 2 * RRT_MAX_RMSA_LAYERS + 2;   // + CR-MSA's inner qkv / proj
 struct Cast16Jobs {

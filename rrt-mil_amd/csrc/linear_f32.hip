@@ -93,6 +93,8 @@ struct Frag8<PREC_F16> {
 #endif
 // Epilogue flavours (template MODE): plain store; un-partition + residual; activation.
 constexpr int MODE_PLAIN = 0, MODE_UNPART = 1, MODE_ACT = 2, MODE_UNPART_DROP = 3, MODE_DROP = 4;   // 3, 4: training
+static_assert(MODE_PLAIN == RRT_LINEAR_EPI_PLAIN && MODE_UNPART == RRT_LINEAR_EPI_UNPART && MODE_ACT == RRT_LINEAR_EPI_ACT &&
+              MODE_UNPART_DROP == RRT_LINEAR_EPI_UNPART_DROP && MODE_DROP == RRT_LINEAR_EPI_DROP, "rrt_linear_plan reports MODE_*");
 
 // Elementwise activation of the epilogue (RRT_ACT_*; callers of the hot path: patch_to_emb's ReLU/GELU
 // modules/rrt.py:208-217, DAttention's hidden activation / gate modules/datten.py:14-22,52-62).
@@ -1170,47 +1172,40 @@ __global__ __launch_bounds__(256 * KG, 1) void linear_splitk_kernel(const float*
 #define RRT_NLW16 4
 #endif
 constexpr int NLW16 = RRT_NLW16;      // loader waves of the 16-bit-operand GEMMs
+// (the launchers below decide nothing: kernel, grid and the deferred form come from plan_linear's LinearPlan)
 template <int MT, int NT, int MODE, int PREC>
-hipError_t launch_cfg16(const void* A, const void* B, float* C, int M, int N, int K, int grid_cap,
+hipError_t launch_cfg16(const void* A, const void* B, float* C, int M, int N, int K, const LinearPlan& pl,
                         const LinearEpilogue& ep, hipStream_t st) {
   constexpr int BM = 16 * MT, BN = 64 * NT;
   constexpr int LDS_BYTES = 2 * (BM + BN) * BK * 4;
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const int ntiles = tiles_m * tiles_n;
-  const int grid = ntiles < grid_cap ? ntiles : grid_cap;
-  if (ntiles <= grid) {                                // no block gets a second tile: nothing to defer
+  if (!pl.defer) {                                     // no block gets a second tile: nothing to defer
     auto kws = linear_ws_kernel<MT, NT, MODE, PREC, true, false, NLW16>;
     RRT_ALLOW_LDS(kws, LDS_BYTES);
-    kws<<<dim3(grid), dim3(64 * (4 + NLW16)), LDS_BYTES, st>>>(A, B, C, M, N, K, tiles_n, ntiles, ep);
+    kws<<<dim3(pl.grid), dim3(64 * (4 + NLW16)), LDS_BYTES, st>>>(A, B, C, M, N, K, pl.tiles_n, pl.ntiles, ep);
   } else {
     auto kws = linear_ws_kernel<MT, NT, MODE, PREC, true, true, NLW16>;
     RRT_ALLOW_LDS(kws, LDS_BYTES);
-    kws<<<dim3(grid), dim3(64 * (4 + NLW16)), LDS_BYTES, st>>>(A, B, C, M, N, K, tiles_n, ntiles, ep);
+    kws<<<dim3(pl.grid), dim3(64 * (4 + NLW16)), LDS_BYTES, st>>>(A, B, C, M, N, K, pl.tiles_n, pl.ntiles, ep);
   }
   return hipGetLastError();
 }
 
 template <int MT, int NT, int MODE, int PREC>
-hipError_t launch_cfg(const float* A, const float* B, float* C, int M, int N, int K, int grid_cap,
+hipError_t launch_cfg(const float* A, const float* B, float* C, int M, int N, int K, const LinearPlan& pl,
                       const LinearEpilogue& ep, hipStream_t st) {
   constexpr int BM = 16 * MT, BN = 64 * NT;
   constexpr int LDS_BYTES = 2 * (BM + BN) * BK * 4;
   static_assert(2 * LDS_BYTES <= 160 * 1024, "two blocks per CU must fit the 160 KiB LDS");
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const int ntiles = tiles_m * tiles_n;
-  const int grid = ntiles < grid_cap ? ntiles : grid_cap;
   if constexpr (MT >= 6) {
-    static const bool use_ws = rrt_tune_env("RRT_LINEAR_NO_WS") == nullptr;
-    if (use_ws) {
-      static const bool force_defer = rrt_tune_env("RRT_LINEAR_DEFER") != nullptr;   // tuning hook
-      if (ntiles <= grid && !force_defer) {            // no block gets a second tile: nothing to defer
+    if (pl.kernel == LINEAR_KERNEL_WS) {
+      if (!pl.defer) {                                 // no block gets a second tile: nothing to defer
         auto kws = linear_ws_kernel<MT, NT, MODE, PREC, false, false>;
         RRT_ALLOW_LDS(kws, LDS_BYTES);
-        kws<<<dim3(grid), dim3(384), LDS_BYTES, st>>>(A, B, C, M, N, K, tiles_n, ntiles, ep);
+        kws<<<dim3(pl.grid), dim3(384), LDS_BYTES, st>>>(A, B, C, M, N, K, pl.tiles_n, pl.ntiles, ep);
       } else {
         auto kws = linear_ws_kernel<MT, NT, MODE, PREC, false, true>;
         RRT_ALLOW_LDS(kws, LDS_BYTES);
-        kws<<<dim3(grid), dim3(384), LDS_BYTES, st>>>(A, B, C, M, N, K, tiles_n, ntiles, ep);
+        kws<<<dim3(pl.grid), dim3(384), LDS_BYTES, st>>>(A, B, C, M, N, K, pl.tiles_n, pl.ntiles, ep);
       }
       return hipGetLastError();
     }
@@ -1218,13 +1213,14 @@ hipError_t launch_cfg(const float* A, const float* B, float* C, int M, int N, in
   if constexpr (PREC == PREC_SPLIT) {
     return hipErrorInvalidValue;          // the split form exists in the warp-specialised kernel only
   } else {
+    if (pl.kernel != LINEAR_KERNEL_PLAIN) return hipErrorInvalidValue;
     auto kern = linear_kernel<MT, NT, MODE, PREC>;
     if (LDS_BYTES > 64 * 1024) {
       static OncePerDevice once;
       if (once.first())
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     }
-    kern<<<dim3(grid), dim3(256), LDS_BYTES, st>>>(A, B, C, M, N, K, tiles_n, ntiles, ep);
+    kern<<<dim3(pl.grid), dim3(256), LDS_BYTES, st>>>(A, B, C, M, N, K, pl.tiles_n, pl.ntiles, ep);
     return hipGetLastError();
   }
 }
@@ -1300,32 +1296,18 @@ Cfg choose(int M, int N, int prec = PREC_F32, int K = 0) {
 RRT_TRACE_DEFINE_READER(rrt_debug_trace_linear)
 #endif
 
-// C[M,N] fp32 = A . B^T on (hi, lo) bf16 images of A and B (RRT_COMPUTE_F32X3, cast16.hip); epilogues as fp32
-hipError_t launch_linear_split(const void* A, const void* B, float* C, int M, int N, int K, const LinearEpilogue& ep,
-                               hipStream_t st) {
-  if (K % 32 || ep.drop_on || ep.act) return hipErrorInvalidValue;
-  const bool u = ep.resid != nullptr;
-  Cfg c{9, 1, 512};                                // the warp-specialised kernel's tile shapes only
-  {
-    static const Cfg cands[] = {{9, 1, 512}, {8, 1, 512}, {9, 2, 512}, {8, 2, 512}, {9, 2, 256}, {8, 2, 256}};
-    long best_cost = -1;
-    for (const Cfg& q : cands) {
-      long tiles = (long)((M + 16 * q.mt - 1) / (16 * q.mt)) * ((N + 64 * q.nt - 1) / (64 * q.nt));
-      long grid = tiles < q.cap ? tiles : q.cap;
-      long cost = ((tiles + grid - 1) / grid) * ((grid + 255) / 256) * q.mt * q.nt;
-      if (best_cost < 0 || cost < best_cost) { c = q; best_cost = cost; }
-    }
+// tile shape of the split-image GEMMs (launch_linear_split): the warp-specialised kernel's tile shapes only
+static Cfg choose_split(int M, int N) {
+  Cfg c{9, 1, 512};
+  static const Cfg cands[] = {{9, 1, 512}, {8, 1, 512}, {9, 2, 512}, {8, 2, 512}, {9, 2, 256}, {8, 2, 256}};
+  long best_cost = -1;
+  for (const Cfg& q : cands) {
+    long tiles = (long)((M + 16 * q.mt - 1) / (16 * q.mt)) * ((N + 64 * q.nt - 1) / (64 * q.nt));
+    long grid = tiles < q.cap ? tiles : q.cap;
+    long cost = ((tiles + grid - 1) / grid) * ((grid + 255) / 256) * q.mt * q.nt;
+    if (best_cost < 0 || cost < best_cost) { c = q; best_cost = cost; }
   }
-#define RRT_SPLIT_CASE(MT_, NT_)                                                                                  \
-  if (c.mt == MT_ && c.nt == NT_)                                                                                 \
-    return u ? launch_cfg<MT_, NT_, MODE_UNPART, PREC_SPLIT>((const float*)A, (const float*)B, C, M, N, K, c.cap, ep, st) \
-             : launch_cfg<MT_, NT_, MODE_PLAIN, PREC_SPLIT>((const float*)A, (const float*)B, C, M, N, K, c.cap, ep, st);
-  RRT_SPLIT_CASE(9, 1);
-  RRT_SPLIT_CASE(8, 1);
-  RRT_SPLIT_CASE(9, 2);
-  RRT_SPLIT_CASE(8, 2);
-#undef RRT_SPLIT_CASE
-  return hipErrorInvalidValue;
+  return c;
 }
 
 // tile shape of the 16-bit-operand GEMMs (launch_linear16)
@@ -1383,21 +1365,104 @@ static Cfg choose16(int M, int N, int K, bool solo) {
   return best;
 }
 
+// The one place where a GEMM's kernel form is decided: which kernel, which tile shape, how many resident blocks, whether a
+// block defers its epilogue under its next tile.  A pure function of (operand kind, M, N, K) and of WHICH fields of the epilogue
+// are set (no pointer is followed): launch_linear / launch_linear16 / launch_linear_split switch on its answer and
+// rrt_linear_plan reports it.  What a kernel decides from its own arguments -- the straight-line un-partition form, the
+// 32-bit-offset limit of the buffer stores -- is not part of the plan.
+hipError_t plan_linear(int ops, int M, int N, int K, const LinearEpilogue& ep, LinearPlan* out) {
+  LinearPlan pl{};
+  const bool u = ep.resid != nullptr;
+  Cfg c{};
+  bool ws = true;
+  bool force_defer = false;
+  if (ops == LINEAR_OPS_SPLIT) {
+    if (K % 32 || ep.drop_on || ep.act) return hipErrorInvalidValue;
+    c = choose_split(M, N);
+    pl.mode = u ? MODE_UNPART : MODE_PLAIN;
+    pl.prec = PREC_SPLIT;
+  } else if (ops == LINEAR_OPS_16) {
+    if ((ep.prec != PREC_BF16 && ep.prec != PREC_F16) || K % 64 || ep.drop_on) return hipErrorInvalidValue;
+    c = choose16(M, N, K, ep.solo);
+    pl.mode = u ? MODE_UNPART : ep.act ? MODE_ACT : MODE_PLAIN;
+    pl.prec = ep.prec;
+  } else if (ops == LINEAR_OPS_F32) {
+    if (ep.drop_on && (ep.prec != PREC_F32 || ep.act)) return hipErrorInvalidValue;   // dropout: fp32 training only
+    // the GEMMs of CR-MSA's representatives (M = 64 k <= 512 rows), when the forward has the GPU to itself: K split inside
+    // the block (linear_splitk_kernel; its 16-wave, 80-96 KiB blocks do not fit next to another bag's fused R-MSA block)
+    static const bool no_splitk = rrt_tune_env("RRT_NO_SPLITK") != nullptr;
+    if (!no_splitk && ep.solo && ep.prec == PREC_F32 && !u && !ep.act && !ep.zero64 && M <= 512 && K % (4 * BK) == 0 && K >= 256) {
+      pl.kernel = LINEAR_KERNEL_SPLITK;
+      pl.kg = 4;
+      pl.mt = (N >= 1024 && !ep.drop_on) ? 2 : 1;   // qkv: 32-row tiles (6 x 24 = 144 blocks at k = 3); proj: 16-row tiles (12 x 8 = 96 blocks)
+      pl.nt = 1;
+      pl.drop = ep.drop_on ? 1 : 0;
+      pl.mode = ep.drop_on ? MODE_DROP : MODE_PLAIN;
+      pl.prec = PREC_F32;
+      pl.tiles_n = (N + 63) / 64;
+      pl.ntiles = ((M + 16 * pl.mt - 1) / (16 * pl.mt)) * pl.tiles_n;
+      pl.grid = pl.ntiles;                          // one tile per block, no cap
+      *out = pl;
+      return hipSuccess;
+    }
+    c = choose(M, N, ep.prec, K);
+    pl.mode = ep.drop_on ? (u ? MODE_UNPART_DROP : MODE_DROP) : u ? MODE_UNPART : ep.act ? MODE_ACT : MODE_PLAIN;
+    pl.prec = ep.drop_on ? PREC_F32 : (ep.prec == PREC_BF16 || ep.prec == PREC_F16) ? ep.prec : PREC_F32;
+  } else {
+    return hipErrorInvalidValue;
+  }
+  if (c.mt <= 0 || c.nt <= 0 || c.cap <= 0) return hipErrorInvalidValue;
+  if (ops != LINEAR_OPS_16) {                       // fp32 bytes through the staging ring (split images included)
+    static const bool use_ws = rrt_tune_env("RRT_LINEAR_NO_WS") == nullptr;
+    static const bool defer_hook = rrt_tune_env("RRT_LINEAR_DEFER") != nullptr;   // tuning hook
+    ws = c.mt >= 6 && use_ws;
+    force_defer = defer_hook;
+  }
+  pl.kernel = ws ? LINEAR_KERNEL_WS : LINEAR_KERNEL_PLAIN;
+  pl.mt = c.mt;
+  pl.nt = c.nt;
+  pl.cap = c.cap;
+  const int BM = 16 * c.mt, BN = 64 * c.nt;
+  pl.tiles_n = (N + BN - 1) / BN;
+  pl.ntiles = ((M + BM - 1) / BM) * pl.tiles_n;
+  pl.grid = pl.ntiles < c.cap ? pl.ntiles : c.cap;
+  pl.defer = (ws && (pl.ntiles > pl.grid || force_defer)) ? 1 : 0;   // no block gets a second tile: nothing to defer
+  *out = pl;
+  return hipSuccess;
+}
+
+// C[M,N] fp32 = A . B^T on (hi, lo) bf16 images of A and B (RRT_COMPUTE_F32X3, cast16.hip); epilogues as fp32
+hipError_t launch_linear_split(const void* A, const void* B, float* C, int M, int N, int K, const LinearEpilogue& ep,
+                               hipStream_t st) {
+  LinearPlan pl{};
+  if (hipError_t e = plan_linear(LINEAR_OPS_SPLIT, M, N, K, ep, &pl)) return e;
+#define RRT_SPLIT_CASE(MT_, NT_)                                                                                  \
+  if (pl.mt == MT_ && pl.nt == NT_)                                                                               \
+    return pl.mode == MODE_UNPART                                                                                 \
+               ? launch_cfg<MT_, NT_, MODE_UNPART, PREC_SPLIT>((const float*)A, (const float*)B, C, M, N, K, pl, ep, st) \
+               : launch_cfg<MT_, NT_, MODE_PLAIN, PREC_SPLIT>((const float*)A, (const float*)B, C, M, N, K, pl, ep, st);
+  RRT_SPLIT_CASE(9, 1);
+  RRT_SPLIT_CASE(8, 1);
+  RRT_SPLIT_CASE(9, 2);
+  RRT_SPLIT_CASE(8, 2);
+#undef RRT_SPLIT_CASE
+  return hipErrorInvalidValue;
+}
+
 // C[M,N] fp32 = A16[M,K] . B16[N,K]^T with the operands already in 16 bits (ep.prec = 1 bf16 / 2 fp16); the
 // epilogues are the fp32 kernel's.  K % 64 == 0; the warp-specialised large-tile kernel only (the callers are the
 // R-MSA projections of the reduced-precision path: M = Np >= 3136 rows).
 hipError_t launch_linear16(const void* A, const void* B, float* C, int M, int N, int K, const LinearEpilogue& ep,
                            hipStream_t st) {
-  if ((ep.prec != PREC_BF16 && ep.prec != PREC_F16) || K % 64 || ep.drop_on) return hipErrorInvalidValue;
-  const bool u = ep.resid != nullptr;
-  const Cfg c = choose16(M, N, K, ep.solo);
+  LinearPlan pl{};
+  if (hipError_t e = plan_linear(LINEAR_OPS_16, M, N, K, ep, &pl)) return e;
 #define RRT_MODES16(MT_, NT_, P_)                                                                  \
-  (u ? launch_cfg16<MT_, NT_, MODE_UNPART, P_>(A, B, C, M, N, K, c.cap, ep, st)                    \
-     : ep.act ? launch_cfg16<MT_, NT_, MODE_ACT, P_>(A, B, C, M, N, K, c.cap, ep, st)              \
-              : launch_cfg16<MT_, NT_, MODE_PLAIN, P_>(A, B, C, M, N, K, c.cap, ep, st))
+  (pl.mode == MODE_UNPART ? launch_cfg16<MT_, NT_, MODE_UNPART, P_>(A, B, C, M, N, K, pl, ep, st)  \
+   : pl.mode == MODE_ACT  ? launch_cfg16<MT_, NT_, MODE_ACT, P_>(A, B, C, M, N, K, pl, ep, st)     \
+                          : launch_cfg16<MT_, NT_, MODE_PLAIN, P_>(A, B, C, M, N, K, pl, ep, st))
 #define RRT_CASE16(MT_, NT_)                                                                       \
-  if (c.mt == MT_ && c.nt == NT_)                                                                  \
-    return ep.prec == PREC_BF16 ? RRT_MODES16(MT_, NT_, PREC_BF16) : RRT_MODES16(MT_, NT_, PREC_F16);
+  if (pl.mt == MT_ && pl.nt == NT_)                                                                \
+    return pl.prec == PREC_BF16 ? RRT_MODES16(MT_, NT_, PREC_BF16) : RRT_MODES16(MT_, NT_, PREC_F16);
   RRT_CASE16(9, 1);
   RRT_CASE16(8, 1);
   RRT_CASE16(9, 2);
@@ -1422,48 +1487,46 @@ hipError_t launch_linear16(const void* A, const void* B, float* C, int M, int N,
 
 hipError_t launch_linear(const float* A, const float* B, float* C, int M, int N, int K,
                          const LinearEpilogue& ep, hipStream_t st) {
-  const bool u = ep.resid != nullptr;
-  if (ep.drop_on && (ep.prec != PREC_F32 || ep.act)) return hipErrorInvalidValue;   // dropout: fp32 training only
-  // the GEMMs of CR-MSA's representatives (M = 64 k <= 512 rows), when the forward has the GPU to itself: K split inside
-  // the block (linear_splitk_kernel; its 16-wave, 80-96 KiB blocks do not fit next to another bag's fused R-MSA block)
-  static const bool no_splitk = rrt_tune_env("RRT_NO_SPLITK") != nullptr;
-  if (!no_splitk && ep.solo && ep.prec == PREC_F32 && !u && !ep.act && !ep.zero64 && M <= 512 && K % (4 * BK) == 0 && K >= 256) {
+  LinearPlan pl{};
+  if (hipError_t e = plan_linear(LINEAR_OPS_F32, M, N, K, ep, &pl)) return e;
+  if (pl.kernel == LINEAR_KERNEL_SPLITK) {
     constexpr int KG = 4;
-    const int tiles_n = (N + 63) / 64;
-    if (N >= 1024 && !ep.drop_on) {                 // qkv: 32-row tiles (6 x 24 = 144 blocks at k = 3)
+    if (pl.kg != KG) return hipErrorInvalidValue;
+    if (pl.mt == 2 && !pl.drop) {
       constexpr int MT = 2;
       constexpr int LDS_BYTES = KG * 2 * (16 * MT + 64) * BK * 4;
       auto kern = linear_splitk_kernel<MT, KG>;
       RRT_ALLOW_LDS(kern, LDS_BYTES);
-      kern<<<dim3(((M + 16 * MT - 1) / (16 * MT)) * tiles_n), dim3(256 * KG), LDS_BYTES, st>>>(A, B, C, M, N, K, tiles_n, ep);
-    } else {                                        // proj: 16-row tiles (12 x 8 = 96 blocks)
+      kern<<<dim3(pl.grid), dim3(256 * KG), LDS_BYTES, st>>>(A, B, C, M, N, K, pl.tiles_n, ep);
+    } else if (pl.mt == 1) {
       constexpr int MT = 1;
       constexpr int LDS_BYTES = KG * 2 * (16 * MT + 64) * BK * 4;
-      if (ep.drop_on) {
+      if (pl.drop) {
         auto kern = linear_splitk_kernel<MT, KG, true>;
         RRT_ALLOW_LDS(kern, LDS_BYTES);
-        kern<<<dim3(((M + 16 * MT - 1) / (16 * MT)) * tiles_n), dim3(256 * KG), LDS_BYTES, st>>>(A, B, C, M, N, K, tiles_n, ep);
+        kern<<<dim3(pl.grid), dim3(256 * KG), LDS_BYTES, st>>>(A, B, C, M, N, K, pl.tiles_n, ep);
       } else {
         auto kern = linear_splitk_kernel<MT, KG>;
         RRT_ALLOW_LDS(kern, LDS_BYTES);
-        kern<<<dim3(((M + 16 * MT - 1) / (16 * MT)) * tiles_n), dim3(256 * KG), LDS_BYTES, st>>>(A, B, C, M, N, K, tiles_n, ep);
+        kern<<<dim3(pl.grid), dim3(256 * KG), LDS_BYTES, st>>>(A, B, C, M, N, K, pl.tiles_n, ep);
       }
+    } else {
+      return hipErrorInvalidValue;
     }
     return hipGetLastError();
   }
-  const Cfg c = choose(M, N, ep.prec, K);
 #define RRT_CASE(MT_, NT_)                                                                          \
-  if (c.mt == MT_ && c.nt == NT_) {                                                                 \
-    if (ep.prec == PREC_BF16) return RRT_MODES(MT_, NT_, PREC_BF16);                                \
-    if (ep.prec == PREC_F16) return RRT_MODES(MT_, NT_, PREC_F16);                                  \
+  if (pl.mt == MT_ && pl.nt == NT_) {                                                               \
+    if (pl.prec == PREC_BF16) return RRT_MODES(MT_, NT_, PREC_BF16);                                \
+    if (pl.prec == PREC_F16) return RRT_MODES(MT_, NT_, PREC_F16);                                  \
     return RRT_MODES(MT_, NT_, PREC_F32);                                                           \
   }
 #define RRT_MODES(MT_, NT_, P_)                                                                     \
-  (ep.drop_on ? (u ? launch_cfg<MT_, NT_, MODE_UNPART_DROP, PREC_F32>(A, B, C, M, N, K, c.cap, ep, st)  \
-                       : launch_cfg<MT_, NT_, MODE_DROP, PREC_F32>(A, B, C, M, N, K, c.cap, ep, st))        \
-   : u ? launch_cfg<MT_, NT_, MODE_UNPART, P_>(A, B, C, M, N, K, c.cap, ep, st)                      \
-     : ep.act ? launch_cfg<MT_, NT_, MODE_ACT, P_>(A, B, C, M, N, K, c.cap, ep, st)                 \
-              : launch_cfg<MT_, NT_, MODE_PLAIN, P_>(A, B, C, M, N, K, c.cap, ep, st))
+  (pl.mode == MODE_UNPART_DROP ? launch_cfg<MT_, NT_, MODE_UNPART_DROP, PREC_F32>(A, B, C, M, N, K, pl, ep, st) \
+   : pl.mode == MODE_DROP      ? launch_cfg<MT_, NT_, MODE_DROP, PREC_F32>(A, B, C, M, N, K, pl, ep, st)        \
+   : pl.mode == MODE_UNPART    ? launch_cfg<MT_, NT_, MODE_UNPART, P_>(A, B, C, M, N, K, pl, ep, st)            \
+   : pl.mode == MODE_ACT       ? launch_cfg<MT_, NT_, MODE_ACT, P_>(A, B, C, M, N, K, pl, ep, st)               \
+                               : launch_cfg<MT_, NT_, MODE_PLAIN, P_>(A, B, C, M, N, K, pl, ep, st))
   RRT_CASE(9, 1);
   RRT_CASE(8, 1);
   RRT_CASE(9, 2);

@@ -88,6 +88,36 @@ def test_encoder_plan_flags(lib):
     assert lib.rrt_encoder_plan(C.byref(enc._desc), 9000, None) == -1
 
 
+def test_linear_plan_and_debug_linear_exports(lib):
+    """rrt_linear_plan reports the launchers' own decision (host only): kernel, tile, cap, tiles, grid, deferred form, split-K's
+    KG / DROP; rrt_debug_linear_f32 validates before it launches.  The R-MSA projections of a 9 k bag and the representatives'
+    GEMMs as anchors; tests/test_linear_form_grid_cpu.py sweeps the rest."""
+    for name in ("rrt_linear_plan", "rrt_debug_linear_f32"):
+        assert name in _lib.SIGNATURES and hasattr(lib, name)
+    p = _lib.linear_plan(9216, 512, 512)                                   # out-projection, fp32: 96 x 64 tiles, one round
+    assert (p["kernel"], p["mt"], p["nt"], p["cap"], p["ntiles"], p["grid"], p["defer"]) == (_lib.LINEAR_KERNEL_WS, 6, 1, 768, 768, 768, 0)
+    p = _lib.linear_plan(9216, 1536, 512)                                  # qkv: 144 x 64 tiles, three per resident block
+    assert (p["kernel"], p["mt"], p["nt"], p["cap"], p["ntiles"], p["grid"], p["defer"]) == (_lib.LINEAR_KERNEL_WS, 9, 1, 512, 1536, 512, 1)
+    p = _lib.linear_plan(192, 1536, 512, solo=1)                           # the representatives' qkv with one bag in flight
+    assert (p["kernel"], p["mt"], p["kg"], p["drop"], p["grid"]) == (_lib.LINEAR_KERNEL_SPLITK, 2, 4, 0, 144)
+    assert _lib.linear_plan(192, 1536, 512, solo=0)["kernel"] == _lib.LINEAR_KERNEL_PLAIN
+    assert _lib.linear_plan(192, 1536, 512, solo=1, zero64=1)["kernel"] == _lib.LINEAR_KERNEL_PLAIN
+    p = _lib.linear_plan(192, 512, 512, epilogue=_lib.LINEAR_EPI_DROP, solo=1)
+    assert (p["kernel"], p["mt"], p["drop"], p["mode"]) == (_lib.LINEAR_KERNEL_SPLITK, 1, 1, _lib.LINEAR_EPI_DROP)
+    a = _lib.linear_plan(9216, 512, 512, _lib.COMPUTE_BF16, _lib.LINEAR_OPS_16, _lib.LINEAR_EPI_UNPART, solo=1)
+    b = _lib.linear_plan(9216, 512, 512, _lib.COMPUTE_BF16, _lib.LINEAR_OPS_16, _lib.LINEAR_EPI_UNPART, solo=0)
+    assert (a["mt"], a["nt"], a["cap"]) == (6, 1, 768) and (b["mt"], b["nt"], b["cap"]) == (6, 2, 512) and a["mode"] == b["mode"] == 1
+    buf = (C.c_int32 * _lib.LINEAR_PLAN_INTS)()
+    assert lib.rrt_linear_plan(16, 64, 64, 0, 0, 0, 0, 0, None) == -1 and lib.rrt_linear_plan(0, 64, 64, 0, 0, 0, 0, 0, buf) == -1
+    assert lib.rrt_linear_plan(16, 64, 64, 0, 3, 0, 0, 0, buf) == -1 and lib.rrt_linear_plan(16, 64, 64, 0, 0, 5, 0, 0, buf) == -1
+    for args in ((16, 64, 48, 0, 0, 0), (16, 64, 32, 1, 1, 0), (16, 64, 64, 0, 1, 0), (16, 64, 64, 1, 0, 4), (16, 64, 64, 1, 1, 4),
+                 (16, 64, 64, 3, 2, 2), (16, 64, 64, 3, 2, 4), (16, 64, 64, 3, 0, 0)):
+        rc = lib.rrt_linear_plan(*args, 0, 0, buf)
+        assert rc == -2 and b"linear" in lib.rrt_strerror(rc), args
+    # the stage entry refuses on the host, before anything is launched
+    assert lib.rrt_debug_linear_f32(None, None, None, None, None, 16, 64, 64, None, 0, 0, 0, 1.0, 0, 0, 0.0, 0, 0, None, None) == -1
+
+
 @pytest.fixture(scope="module")
 def plan_golden():
     """the host-side answers of the library before the forward launched from one plan value (tools/make_golden_plan.py)"""

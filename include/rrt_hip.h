@@ -841,6 +841,34 @@ int rrt_linear_backward_f32(const float *dY, const float *X, const float *W, flo
                             float *db, int64_t M, int32_t N, int32_t K, int32_t compute,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* Stage entries for tests: the element-wise passes of the training step (csrc/ln_bwd.hip) and the batched weight transpose
+ * (csrc/linear_bwd.hip), one launcher each, which only the whole-encoder entries reached before (exports added under ABI 29,
+ * no existing struct or signature touched; tests/test_train_blocks_matrix.py, tests/test_train_blocks_grid_cpu.py).
+ * Dropout: threshold, scale 1/(1-p) and seed are derived from (drop_p, drop_seed, drop_layer) exactly as
+ * rrt_encoder_forward_train_f32 / rrt_encoder_backward_f32 derive them (drop_layer: any non-negative tag, e.g. the R-MSA layer
+ * index, 100 for CR-MSA); element i is kept iff hash(seed, layer, i) >= p * 2^32.  drop_p = 0: no mask.  Every entry checks
+ * its arguments before it launches: RRT_E_INVALID on NULL / non-positive / inconsistent ones, RRT_E_UNSUPPORTED as noted.
+ *   act_forward     h[i] = act(hpre[i]), then the mask (index i) and the scale 1/(1-p).  act = RRT_ACT_GELU (exact, erf) or
+ *                   RRT_ACT_RELU, n % 4 == 0 (else RRT_E_UNSUPPORTED).
+ *   act_backward    in place: dh[i] = mask(dh[i]) * scale * act'(hpre[i]); ReLU's derivative at +-0 is 0.  dh != hpre.
+ *   partition_rows  dst [H*H, dim] region-major <- src [g->L, dim] token order, pad slots 0 (region_partition of a gradient),
+ *                   times `scale` (a branch multiplier, >= 0) and, with drop_p > 0, the mask indexed by PADDED SLOT * dim +
+ *                   column and 1/(1-p).  dim % 4 == 0 (else RRT_E_UNSUPPORTED), H*H <= 2^24, src != dst.
+ *   drop_mask       dst[i] = keep(i) ? src[i] * scale / (1-p) : 0 for any n <= 2^31 - 1, no alignment assumed; src == dst runs
+ *                   the in-place form (which launches nothing when drop_p == 0 and scale == 1), else the copying form.
+ *   transpose_batch out[j] [C[j], R[j]] = in[j] [R[j], C[j]]^T for n_jobs matrices in ONE launch; in, out, R, C are HOST
+ *                   arrays of n_jobs entries.  n_jobs <= 2 * RRT_MAX_RMSA_LAYERS + 2 (else RRT_E_UNSUPPORTED). */
+int rrt_debug_act_forward_f32(const float *hpre, float *h, int64_t n, int32_t act, float drop_p, uint64_t drop_seed,
+                              int32_t drop_layer, void *stream);
+int rrt_debug_act_backward_f32(float *dh, const float *hpre, int64_t n, int32_t act, float drop_p, uint64_t drop_seed,
+                               int32_t drop_layer, void *stream);
+int rrt_debug_partition_rows_f32(const float *src, float *dst, int32_t dim, const rrt_grid *g, float drop_p,
+                                 uint64_t drop_seed, int32_t drop_layer, float scale, void *stream);
+int rrt_debug_drop_mask_f32(const float *src, float *dst, int64_t n, float drop_p, uint64_t drop_seed, int32_t drop_layer,
+                            float scale, void *stream);
+int rrt_debug_transpose_batch_f32(const float *const *in, float *const *out, const int32_t *R, const int32_t *C,
+                                  int32_t n_jobs, void *stream);
+
 /* ---- row f2: training.  Forward that stashes what the backward needs, and the backward itself ----
  * Supported: the default path (1-D 'attn' EPEG R-MSA layers, CR-MSA with the phi matrix or the MLP phi,
  * all_shortcut), an R-MSA head dim that is a multiple of 16 up to 256 (any other multiple of 4 without EPEG on regions of

@@ -267,6 +267,16 @@ SIGNATURES = {
     "rrt_linear_backward_workspace_size": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     "rrt_linear_backward_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_debug_act_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_uint64, C.c_int32,
+                                            C.c_void_p]),
+    "rrt_debug_act_backward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_uint64, C.c_int32,
+                                             C.c_void_p]),
+    "rrt_debug_partition_rows_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Grid), C.c_float, C.c_uint64,
+                                               C.c_int32, C.c_float, C.c_void_p]),
+    "rrt_debug_drop_mask_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_uint64, C.c_int32, C.c_float,
+                                          C.c_void_p]),
+    "rrt_debug_transpose_batch_f32": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
     "rrt_encoder_train_sizes": (C.c_int, [C.POINTER(EncoderDesc), C.c_int64, C.POINTER(C.c_size_t),
                                           C.POINTER(C.c_size_t)]),
     "rrt_encoder_forward_train_f32": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderWeights), C.c_void_p,
@@ -330,6 +340,7 @@ LINEAR_OPS_F32, LINEAR_OPS_16, LINEAR_OPS_SPLIT = 0, 1, 2
 LINEAR_EPI_PLAIN, LINEAR_EPI_UNPART, LINEAR_EPI_ACT, LINEAR_EPI_UNPART_DROP, LINEAR_EPI_DROP = 0, 1, 2, 3, 4
 LINEAR_KERNEL_PLAIN, LINEAR_KERNEL_WS, LINEAR_KERNEL_SPLITK = 0, 1, 2
 LINEAR_PLAN_INTS = 12
+TRANSPOSE_MAX_JOBS = 2 * RRT_MAX_RMSA_LAYERS + 2      # rrt_debug_transpose_batch_f32: jobs of one launch (csrc/internal.h)
 LINEAR_PLAN_FIELDS = ("kernel", "mt", "nt", "cap", "ntiles", "grid", "defer", "kg", "drop", "mode", "prec")
 # stage-boundary event slots of rrt_encoder_forward_events_f32 (enum in include/rrt_hip.h)
 EV_START, EV_LN_PARTITION, EV_QKV, EV_ATTN, EV_PROJ, EV_CR_COMBINE, EV_CR_INNER, EV_END, EV_COUNT = range(9)

@@ -2898,6 +2898,78 @@ int rrt_debug_linear_f32(const void* A, const void* B, const float* bias, const 
   return (int)launch_linear((const float*)A, (const float*)B, C, (int)M, N, K, ep, st);
 }
 
+// ---- stage entries of the training backward's element-wise kernels (ln_bwd.hip) and the batched transpose (linear_bwd.hip):
+//      one launcher each, arguments checked, the dropout words derived as the training entries derive them
+//      (tests/test_train_blocks_matrix.py, test_train_blocks_grid_cpu.py)
+namespace {
+int check_act_stage(const void* a, const void* b, int64_t n, int32_t act, float drop_p, int32_t drop_layer, DropCfg* dc) {
+  if (!a || !b || n <= 0 || n > (int64_t)1 << 40 || drop_layer < 0) return RRT_E_INVALID;
+  if (make_drop(drop_p, dc)) return RRT_E_INVALID;
+  if (act != RRT_ACT_GELU && act != RRT_ACT_RELU) return unsupported("activation pass: RRT_ACT_GELU or RRT_ACT_RELU");
+  if (n % 4) return unsupported("activation pass: n must be a multiple of 4");
+  return RRT_OK;
+}
+}  // namespace
+
+int rrt_debug_act_forward_f32(const float* hpre, float* h, int64_t n, int32_t act, float drop_p, uint64_t drop_seed,
+                              int32_t drop_layer, void* stream) {
+  DropCfg dc{};
+  const int rc = check_act_stage(hpre, h, n, act, drop_p, drop_layer, &dc);
+  if (rc) return rc;
+  return (int)launch_act_forward(hpre, h, (size_t)n, act, dc.thresh, dc.seed(drop_seed, drop_layer), dc.scale, (hipStream_t)stream);
+}
+
+int rrt_debug_act_backward_f32(float* dh, const float* hpre, int64_t n, int32_t act, float drop_p, uint64_t drop_seed,
+                               int32_t drop_layer, void* stream) {
+  DropCfg dc{};
+  const int rc = check_act_stage(dh, hpre, n, act, drop_p, drop_layer, &dc);
+  if (rc) return rc;
+  if ((const float*)dh == hpre) return RRT_E_INVALID;
+  return (int)launch_act_backward(dh, hpre, (size_t)n, act, dc.thresh, dc.seed(drop_seed, drop_layer), dc.scale, (hipStream_t)stream);
+}
+
+int rrt_debug_partition_rows_f32(const float* src, float* dst, int32_t dim, const rrt_grid* g, float drop_p, uint64_t drop_seed,
+                                 int32_t drop_layer, float scale, void* stream) {
+  if (!src || !dst || src == dst || !g || dim <= 0 || drop_layer < 0 || !(scale >= 0.f)) return RRT_E_INVALID;
+  if (g->L <= 0 || g->H <= 0 || g->s <= 0 || g->regions_side <= 0 || (int64_t)g->regions_side * g->s != g->H ||
+      g->L > (int64_t)g->H * g->H || (int64_t)g->H * g->H > (int64_t)1 << 24)
+    return RRT_E_INVALID;
+  DropCfg dc{};
+  if (make_drop(drop_p, &dc)) return RRT_E_INVALID;
+  if (dim % 4) return unsupported("partition rows: dim must be a multiple of 4");
+  return (int)launch_partition_rows(src, dst, dim, to_dev(*g), dc.thresh, dc.seed(drop_seed, drop_layer), dc.scale * scale,
+                                    (hipStream_t)stream);
+}
+
+int rrt_debug_drop_mask_f32(const float* src, float* dst, int64_t n, float drop_p, uint64_t drop_seed, int32_t drop_layer,
+                            float scale, void* stream) {
+  if (!src || !dst || n <= 0 || n > 0x7FFFFFFF || drop_layer < 0 || !(scale >= 0.f)) return RRT_E_INVALID;
+  DropCfg dc{};
+  if (make_drop(drop_p, &dc)) return RRT_E_INVALID;
+  const unsigned seed = dc.seed(drop_seed, drop_layer);
+  if (src == dst) return (int)launch_apply_drop_mask(dst, (int)n, 1, dc.thresh, seed, dc.scale * scale, (hipStream_t)stream);
+  return (int)launch_copy_drop_mask(src, dst, (size_t)n, dc.thresh, seed, dc.scale * scale, (hipStream_t)stream);
+}
+
+int rrt_debug_transpose_batch_f32(const float* const* in, float* const* out, const int32_t* R, const int32_t* C, int32_t n_jobs,
+                                  void* stream) {
+  if (!in || !out || !R || !C || n_jobs <= 0) return RRT_E_INVALID;
+  if (n_jobs > TRANSPOSE_MAX_JOBS) return unsupported("transpose batch: more jobs than one launch takes (2 * RRT_MAX_RMSA_LAYERS + 2)");
+  TransposeJobs tj{};
+  int64_t blocks = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    if (!in[j] || !out[j] || in[j] == out[j] || R[j] <= 0 || C[j] <= 0 || (int64_t)R[j] * C[j] > (int64_t)1 << 28) return RRT_E_INVALID;
+    blocks += (int64_t)((R[j] + 31) / 32) * ((C[j] + 31) / 32);
+    tj.in[j] = in[j];
+    tj.out[j] = out[j];
+    tj.R[j] = R[j];
+    tj.C[j] = C[j];
+  }
+  if (blocks > 0x7FFFFFFF) return RRT_E_INVALID;
+  tj.n = n_jobs;
+  return (int)launch_transpose_batch(tj, (hipStream_t)stream);
+}
+
 int rrt_encoder_forward_train_f32(const rrt_encoder_desc* desc, const rrt_encoder_weights* w, const float* x,
                                   float* y, int64_t n_tokens, void* stash, size_t stash_bytes, float drop_p,
                                   uint64_t drop_seed, const float* branch_scale, void* stream) {

@@ -1079,6 +1079,91 @@ int rrt_transmil_forward_attn_f32(const rrt_transmil_desc *desc, const rrt_trans
                                   float *feat, float *attn1, float *attn2, int64_t n_tokens, void *workspace,
                                   size_t workspace_bytes, void *stream);
 
+/* ---- TransMIL, training: one forward call and one backward call for the whole model (exports added under ABI 29, no existing
+ * struct or signature touched).  Exact fp32, no atomics, no state in the library, every reduction in a fixed order: two runs
+ * give the same bits.  The envelope of rrt_transmil_forward_f32; the conventions of rrt_encoder_forward_train_f32 /
+ * rrt_encoder_backward_f32: caller-owned stash and workspace of rrt_transmil_train_sizes' sizes (a short one is
+ * RRT_E_WORKSPACE), stream-ordered, re-entrant, every argument checked before anything is launched.
+ *
+ * forward_train: x [n_tokens, input_dim] -> logits [n_classes] (the loss stays with the caller); what the backward reads stays
+ *   in the stash: _fc1's pre-activation (when there is an activation), the rows before and after both LayerNorms, both
+ *   attentions' stashes, and the one row the head sees.  After layer 2 only row 0 (the cls token) is read: the mask, the
+ *   residual, the last LayerNorm and _fc2 run on that one row.
+ * backward: d_logits [n_classes] -> every parameter gradient (WRITTEN, not accumulated; grads mirrors rrt_transmil_weights,
+ *   one float* per parameter, same shapes; attn.conv_w may be NULL when residual = 0) and, unless dx is NULL, dx
+ *   [n_tokens, input_dim] (NULL skips _fc1's dX product).  x, w and the three dropout arguments are the forward's.
+ * Dropout: the stateless mask of rrt_debug_drop_mask_f32 (kept iff hash(seed, index) >= p * 2^32, kept values scaled by
+ *   1 / (1 - p)), element index = row * dim + column of the masked tensor, drop_layer tags 200 (_fc1's Dropout, on
+ *   act(_fc1.0(x)) [n_tokens, dim], p = fc1_drop_p), 201 (layer 1's to_out Dropout on [1 + H * H, dim], p = attn_drop_p) and
+ *   202 (layer 2's, row 0 only: index = column).  p = 0: no mask and no launch for it.  Parity of distribution with torch's
+ *   dropout, not of bits. */
+typedef struct rrt_transmil_layer_grads {
+  float *norm_w, *norm_b;
+  rrt_nystrom_grads attn;
+} rrt_transmil_layer_grads;
+
+typedef struct rrt_transmil_grads {
+  float *fc1_w, *fc1_b;
+  float *cls_token;
+  rrt_transmil_layer_grads layer[2];
+  float *pos_w[3], *pos_b[3];
+  float *norm_w, *norm_b;
+  float *fc2_w, *fc2_b;
+} rrt_transmil_grads;
+
+int rrt_transmil_train_sizes(const rrt_transmil_desc *desc, int64_t n_tokens, size_t *stash_bytes,
+                             size_t *backward_workspace_bytes);
+int rrt_transmil_forward_train_f32(const rrt_transmil_desc *desc, const rrt_transmil_weights *w, const float *x, float *logits,
+                                   int64_t n_tokens, void *stash, size_t stash_bytes, float fc1_drop_p, float attn_drop_p,
+                                   uint64_t drop_seed, void *stream);
+int rrt_transmil_backward_f32(const rrt_transmil_desc *desc, const rrt_transmil_weights *w, const float *x,
+                              const float *d_logits, const void *stash, size_t stash_bytes, const rrt_transmil_grads *grads,
+                              float *dx, int64_t n_tokens, void *workspace, size_t workspace_bytes, float fc1_drop_p,
+                              float attn_drop_p, uint64_t drop_seed, void *stream);
+/* The same step with layer 2's output stage and to_out run for the cls row ALONE (output_row below, a one-row to_out; layer
+ * 2's attention stash then holds no o): the other side of the A/B in tools/bench_transmil_train.py.  The same function to
+ * rounding.  Not what the step uses: its median was lower in every run measured, but the min-max ranges overlapped in one
+ * (DESIGN.md section 8d).  Sizes, stash and workspace are its own; forward and backward must come from the same family. */
+int rrt_debug_transmil_train_sizes_row(const rrt_transmil_desc *desc, int64_t n_tokens, size_t *stash_bytes,
+                                       size_t *backward_workspace_bytes);
+int rrt_debug_transmil_forward_train_row_f32(const rrt_transmil_desc *desc, const rrt_transmil_weights *w, const float *x,
+                                             float *logits, int64_t n_tokens, void *stash, size_t stash_bytes, float fc1_drop_p,
+                                             float attn_drop_p, uint64_t drop_seed, void *stream);
+int rrt_debug_transmil_backward_row_f32(const rrt_transmil_desc *desc, const rrt_transmil_weights *w, const float *x,
+                                        const float *d_logits, const void *stash, size_t stash_bytes,
+                                        const rrt_transmil_grads *grads, float *dx, int64_t n_tokens, void *workspace,
+                                        size_t workspace_bytes, float fc1_drop_p, float attn_drop_p, uint64_t drop_seed,
+                                        void *stream);
+
+/* Stage entry points of the step's own kernels.
+ *  ppeg_side_backward     : the adjoint of rrt_ppeg_side_f32 WITHOUT the cls row: x, dy [side * side, dim] -> dx (dy plus the
+ *                           three transposed depth-wise convs), dw[i] [dim, 1, k, k] for k = 7, 5, 3 and db[i] [dim] (db or
+ *                           its entries may be NULL).  w, dw, db: HOST arrays of three DEVICE pointers.  The grid is EXACTLY
+ *                           side x side with zero borders, for every side >= 1 (rrt_peg_backward_f32 is the encoder's PPEG,
+ *                           which wraps and lifts sides below 7 to 7).  The tap sums are per-tile partials reduced in tile
+ *                           order (the kernel of rrt_reduce_partials_f32).  dim % 4 == 0, side <= 1000.
+ *  assemble_backward      : the adjoint of the sequence assembly [cls | h | wrap], h = drop(act(hpre)), H = ceil(sqrt(N)):
+ *                           d_seq [1 + H * H, dim] -> d_cls [dim] = d_seq[0] and d_emb [n_tokens, dim], row i =
+ *                           (d_seq[1 + i] + (i < H * H - N ? d_seq[1 + N + i] : 0)) * mask(tag 200) * act'(hpre[i]): the
+ *                           gradient of _fc1's Linear output.  hpre [n_tokens, dim] may be NULL when act is RRT_ACT_NONE.
+ *  output_row             : one query row of the output stage, o_row [heads * 64] = softmax(q[row] kl^T) wz +
+ *                           sum_t conv_w[h, t] v[row + t - conv_k / 2]; rows outside [0, n_padded) count as zero.
+ *  output_row_backward    : d_o_row [heads * 64] -> d_qkv [n_padded, 3 * heads * 64] under output_backward's contract (ALL of it
+ *                           written: zero but for row `row` of the q third and the stencil's reach in the v third), d_kl,
+ *                           d_wz [heads, 256, 64], d_conv_w [heads, conv_k] (untouched when conv_w is NULL).
+ * A row outside [0, n_padded) is RRT_E_UNSUPPORTED with "row" in rrt_strerror. */
+int rrt_ppeg_side_backward_workspace_size(int32_t side, int32_t dim, size_t *bytes);
+int rrt_ppeg_side_backward_f32(const float *x, const float *dy, const float *const *w, float *dx, float *const *dw,
+                               float *const *db, int32_t side, int32_t dim, void *workspace, size_t workspace_bytes,
+                               void *stream);
+int rrt_transmil_assemble_backward_f32(const float *d_seq, const float *hpre, float *d_emb, float *d_cls, int64_t n_tokens,
+                                       int32_t dim, int32_t act, float drop_p, uint64_t drop_seed, void *stream);
+int rrt_nystrom_output_row_f32(const float *qkv, const float *kl, const float *wz, const float *conv_w, float *o_row,
+                               int64_t row, int64_t n_padded, int32_t heads, int32_t conv_k, void *stream);
+int rrt_nystrom_output_row_backward_f32(const float *qkv, const float *kl, const float *wz, const float *conv_w,
+                                        const float *d_o_row, float *d_qkv, float *d_kl, float *d_wz, float *d_conv_w,
+                                        int64_t row, int64_t n_padded, int32_t heads, int32_t conv_k, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,12 +127,29 @@ class TransmilWeights(C.Structure):
                 ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p)]
 
 
+class TransmilLayerGrads(C.Structure):
+    _fields_ = [("norm_w", C.c_void_p), ("norm_b", C.c_void_p), ("attn", NystromGrads)]
+
+
+class TransmilGrads(C.Structure):
+    _fields_ = [("fc1_w", C.c_void_p), ("fc1_b", C.c_void_p), ("cls_token", C.c_void_p), ("layer", TransmilLayerGrads * 2),
+                ("pos_w", C.c_void_p * 3), ("pos_b", C.c_void_p * 3), ("norm_w", C.c_void_p), ("norm_b", C.c_void_p),
+                ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p)]
+
+
 class Bag(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("n_tokens", C.c_int64)]
 
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
 ACT_BY_NAME = {"relu": ACT_RELU, "gelu": ACT_GELU, "tanh": ACT_TANH}   # anything else: no activation
+
+# the one-call TransMIL training step and its cls-row A/B twin share their argument lists
+_TRANSMIL_FWD_TRAIN = [C.POINTER(TransmilDesc), C.POINTER(TransmilWeights), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                       C.c_size_t, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
+_TRANSMIL_BWD = [C.POINTER(TransmilDesc), C.POINTER(TransmilWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                 C.POINTER(TransmilGrads), C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_uint64,
+                 C.c_void_p]
 
 # name -> (restype, argtypes); every symbol include/rrt_hip.h declares
 SIGNATURES = {
@@ -327,6 +344,19 @@ SIGNATURES = {
     "rrt_transmil_attn_workspace_size": (C.c_int, [C.POINTER(TransmilDesc), C.c_int64, C.POINTER(C.c_size_t)]),
     "rrt_transmil_forward_attn_f32": (C.c_int, [C.POINTER(TransmilDesc), C.POINTER(TransmilWeights)] + [C.c_void_p] * 5 +
                                       [C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_transmil_train_sizes": (C.c_int, [C.POINTER(TransmilDesc), C.c_int64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "rrt_transmil_forward_train_f32": (C.c_int, _TRANSMIL_FWD_TRAIN),
+    "rrt_transmil_backward_f32": (C.c_int, _TRANSMIL_BWD),
+    "rrt_debug_transmil_train_sizes_row": (C.c_int, [C.POINTER(TransmilDesc), C.c_int64, C.POINTER(C.c_size_t),
+                                                      C.POINTER(C.c_size_t)]),
+    "rrt_debug_transmil_forward_train_row_f32": (C.c_int, _TRANSMIL_FWD_TRAIN),
+    "rrt_debug_transmil_backward_row_f32": (C.c_int, _TRANSMIL_BWD),
+    "rrt_ppeg_side_backward_workspace_size": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_ppeg_side_backward_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_transmil_assemble_backward_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_uint64,
+                                                                        C.c_void_p]),
+    "rrt_nystrom_output_row_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "rrt_nystrom_output_row_backward_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32X3 = 0, 1, 2, 3

@@ -436,3 +436,36 @@ hipError_t launch_transmil_head(const float* x, const float* w, const float* b, 
 // PPEG (k = 7, 5, 3) on a side x side grid stated by the caller: x, y [side * side, C] (peg.hip)
 hipError_t launch_ppeg_side(const float* x, const float* const* w, const float* const* b, float* y, int side, int C,
                             hipStream_t st);
+// ... and its adjoint: x, dy [side * side, C] -> dx, dw[0..2] (k = 7, 5, 3), db[0..2] (entries may be null); right for every
+// side >= 1 (launch_peg_backward is the encoder's PPEG: it wraps, and lifts sides below 7 to 7)
+size_t ppeg_side_bwd_workspace(int side, int C);
+hipError_t launch_ppeg_side_backward(const float* x, const float* dy, const float* const* w, float* dx, float* const* dw,
+                                     float* const* db, int side, int C, void* ws, hipStream_t st);
+
+// ---- TransMIL's one-call training step (transmil_bwd.hip)
+// adjoint of launch_transmil_assemble with _fc1's mask (index = row * dim + column of h) and activation derivative folded in:
+// d_seq [1 + side * side, dim] -> d_emb [N, dim] (the gradient of _fc1's Linear output), d_cls [dim]; hpre [N, dim] is read
+// unless act is RRT_ACT_NONE
+hipError_t launch_transmil_assemble_backward(const float* d_seq, const float* hpre, float* d_emb, float* d_cls, int N, int side,
+                                             int dim, int act, unsigned thresh, unsigned seed, float scale, hipStream_t st);
+// y [n_out] = W [n_out, n_in] x + b (b may be null; n_in % 4 == 0) and its adjoint (n_in % 64 == 0): d_w = dy (x) x, d_b = dy,
+// d_x = W^T dy
+hipError_t launch_row_linear(const float* x, const float* w, const float* b, float* y, int n_out, int n_in, hipStream_t st);
+hipError_t launch_row_linear_backward(const float* dy, const float* x, const float* w, float* d_w, float* d_b, float* d_x,
+                                      int n_out, int n_in, hipStream_t st);
+// the head on one row: hrow = res + drop(y), LayerNorm, _fc2 -> logits; hrow [dim] and stats [2] = (mean, rstd) are kept.
+// Backward: d_logits -> d_w, d_b, d_gamma, d_beta, d_hrow [dim] and d_y [dim] = d_hrow under the same mask.  dim <= 1024.
+hipError_t launch_transmil_row_head(const float* res, const float* y, const float* gamma, const float* beta, const float* w,
+                                    const float* b, float* hrow, float* stats, float* logits, int dim, int n_classes,
+                                    unsigned thresh, unsigned seed, float scale, hipStream_t st);
+hipError_t launch_transmil_row_head_backward(const float* d_logits, const float* hrow, const float* stats, const float* gamma,
+                                             const float* beta, const float* w, float* d_w, float* d_b, float* d_gamma,
+                                             float* d_beta, float* d_hrow, float* d_y, int dim, int n_classes, unsigned thresh,
+                                             unsigned seed, float scale, hipStream_t st);
+// one query row of launch_nystrom_output, o_row [heads * 64], and its adjoint under launch_nystrom_output_backward's d_qkv
+// contract (all of d_qkv written: zero but for row `row` of the q third and the stencil's reach in the v third)
+hipError_t launch_nystrom_output_row(const float* qkv, const float* kl, const float* wz, const float* conv_w, float* o_row,
+                                     long row, long np, int heads, int ks, hipStream_t st);
+hipError_t launch_nystrom_output_row_backward(const float* qkv, const float* kl, const float* wz, const float* conv_w,
+                                              const float* d_o_row, float* d_qkv, float* d_kl, float* d_wz, float* d_conv_w,
+                                              long row, long np, int heads, int ks, hipStream_t st);

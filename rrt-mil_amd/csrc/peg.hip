@@ -302,3 +302,48 @@ hipError_t launch_peg_backward(const float* x, const float* dy, const float* con
   return hipGetLastError();
 }
 
+// ---- the adjoint of launch_ppeg_side (TransMIL's pos_layer under training).  The grid is exactly side x side: nothing is
+// wrapped and a side below 7 is NOT lifted to 7 x 7 (launch_peg_backward is the encoder's PPEG, which does both), so the
+// adjoint stencil's output IS dx and the tap sums run against the grid's own zero borders.  ws: part [tiles][49][C] |
+// dweff [49][C] | column-sum scratch.
+size_t ppeg_side_bwd_workspace(int side, int C) {
+  const size_t tiles = (size_t)((side + 7) / 8) * ((side + 7) / 8);
+  return ((tiles + 1) * 49 * C + (size_t)((side * side + 127) / 128 + 1) * C) * sizeof(float) + 1024;
+}
+
+// x, dy [side * side, C] -> dx, dw[0..2] (k = 7, 5, 3), db[0..2] (entries may be null)
+hipError_t launch_ppeg_side_backward(const float* x, const float* dy, const float* const* w, float* dx, float* const* dw,
+                                     float* const* db, int side, int C, void* ws, hipStream_t st) {
+  const int N = side * side, tiles = ((side + 7) / 8) * ((side + 7) / 8);
+  float* part = (float*)ws;                               // [tiles][49][C]
+  float* dweff = part + (size_t)tiles * 49 * C;           // [49][C]
+  float* cs = dweff + (size_t)49 * C;                     // column-sum scratch
+  const float* nob[3] = {nullptr, nullptr, nullptr};
+  if (!dw[0] || !dw[1] || !dw[2]) return hipErrorInvalidValue;      // before anything is launched
+  hipError_t e = launch_peg_impl(dy, w, nob, dx, N, C, 7, 0, 1, 1, st, side);
+  if (e != hipSuccess) return e;
+  constexpr size_t lds = peg_bwd_dw_lds(7);               // (the instantiation launch_peg_backward checks against the CU's LDS)
+  auto kern = peg_bwd_dw_kernel<7>;
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  kern<<<dim3(tiles, (C + 63) / 64), 256, lds, st>>>(x, dy, part, N, C, side, side);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = launch_reduce_partials(part, dweff, tiles, (size_t)49 * C, st);
+  if (e != hipSuccess) return e;
+  const int ks[3] = {7, 5, 3};
+  float* first_db = nullptr;
+  for (int i = 0; i < 3; ++i) {
+    const int n = C * ks[i] * ks[i];
+    peg_scatter_dw_kernel<<<dim3((n + 255) / 256), 256, 0, st>>>(dweff, dw[i], C, 7, ks[i], 0);
+    if (!db[i]) continue;
+    if (first_db) {                                       // the three biases have one gradient: the column sums of dy
+      e = hipMemcpyAsync(db[i], first_db, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, st);
+    } else {
+      e = launch_colsum(dy, db[i], cs, N, C, st);
+      first_db = db[i];
+    }
+    if (e != hipSuccess) return e;
+  }
+  return hipGetLastError();
+}
+

@@ -11,6 +11,8 @@ or ``train()`` with dropout, raises ``NotImplementedError`` -- use ``eval()`` un
 Training is opt-in: after ``model.enable_training()`` a call that needs a graph (or ``train()`` with dropout) takes the layer
 path -- torch ops around ``NystromAttention``, whose forward-with-stash and backward are the HIP kernels of csrc/nystrom.hip and
 csrc/nystrom_bwd.hip under a ``torch.autograd.Function``; a call that needs no graph still takes the one-call path, bit for bit.
+``model.enable_training(one_call=True)`` takes the whole step into the library instead: ONE rrt_transmil_forward_train_f32 call
+and ONE rrt_transmil_backward_f32 call (csrc/transmil_bwd.hip).
 Attention maps are an inference output: ``TransMIL.forward_bag(x, return_attn=True)`` adds the class token's row of the
 Nystrom-approximated attention matrix of both layers (rrt_transmil_forward_attn_f32, csrc/nystrom_row.hip), and
 ``NystromAttention.attention_row(x, row)`` any one row; with either, a call that needs a graph raises, opt-in or not.
@@ -111,6 +113,66 @@ class _NystromFn(torch.autograd.Function):
                                                               ws.data_ptr(), ws.numel(), st),
                        "rrt_nystrom_attention_backward_f32")
         return (None, dx) + tuple(gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[2:]))
+
+
+class _TransmilStepFn(torch.autograd.Function):
+    """logits (1, n_classes) = the whole of TransMIL for one bag through rrt_transmil_forward_train_f32, and every parameter
+    gradient (and d x, when x needs one) through ONE rrt_transmil_backward_f32.  The parameters are passed as inputs so that
+    autograd routes their gradients; the stash lives in a tensor owned by the graph node (retain_graph works); the dropout
+    masks are regenerated in the backward from (p, seed)."""
+
+    @staticmethod
+    def forward(ctx, model, x2d, fc1_p, attn_p, seed, *params):
+        lib = _lib.load()
+        x = x2d.detach().float().contiguous()
+        n, dev = x.shape[0], x.device
+        keep = []
+        d, w = model._desc_weights(keep)
+        stash_b, ws_b = C.c_size_t(), C.c_size_t()
+        _lib.check(lib.rrt_transmil_train_sizes(C.byref(d), n, C.byref(stash_b), C.byref(ws_b)), "rrt_transmil_train_sizes")
+        stash = torch.empty(stash_b.value, dtype=torch.uint8, device=dev)
+        logits = torch.empty((1, model.n_classes), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.rrt_transmil_forward_train_f32(C.byref(d), C.byref(w), x.data_ptr(), logits.data_ptr(), n,
+                                                          stash.data_ptr(), stash.numel(), fc1_p, attn_p, seed, st),
+                       "rrt_transmil_forward_train_f32")
+        ctx.model, ctx.stash, ctx.ws_bytes, ctx.drop = model, stash, ws_b.value, (fc1_p, attn_p, seed)
+        # the backward reads the parameters through their live pointers: an in-place update between forward and backward
+        # (optimizer.step() before a second backward through a retained graph) must not go unnoticed
+        ctx.versions = [(p_.data_ptr(), p_._version) for p_ in params]
+        ctx.save_for_backward(x)
+        return logits
+
+    @staticmethod
+    def backward(ctx, d_logits):
+        lib = _lib.load()
+        model = ctx.model
+        (x,) = ctx.saved_tensors
+        params = model._step_params()
+        if ctx.versions != [(p_.data_ptr(), p_._version) for p_ in params]:
+            raise RuntimeError("TransMIL: a parameter was modified in place (or replaced) between this forward and its "
+                               "backward; the backward kernels read the live weights, so the gradients would be wrong -- "
+                               "run the forward again")
+        n, dev = x.shape[0], x.device
+        d_logits = d_logits.contiguous().float()
+        keep = []
+        d, w = model._desc_weights(keep)
+        # fresh tensors on every call: autograd (and torch.autograd.grad's caller) may keep what is returned here
+        grads = [torch.empty(p_.shape, dtype=torch.float32, device=dev) for p_ in params]
+        gstruct = _lib.TransmilGrads()
+        slots = (C.c_void_p * len(grads)).from_buffer(gstruct)      # one float* per parameter, in _step_params' order
+        for i, g in enumerate(grads):
+            slots[i] = g.data_ptr()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        ws = model._backward_workspace(ctx.ws_bytes, dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.rrt_transmil_backward_f32(C.byref(d), C.byref(w), x.data_ptr(), d_logits.data_ptr(),
+                                                     ctx.stash.data_ptr(), ctx.stash.numel(), C.byref(gstruct), _ptr(dx), n,
+                                                     ws.data_ptr(), ws.numel(), ctx.drop[0], ctx.drop[1], ctx.drop[2], st),
+                       "rrt_transmil_backward_f32")
+        return (None, dx, None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[5:]))
 
 
 class NystromAttention(HeadState, nn.Module):
@@ -264,6 +326,7 @@ class PPEG(nn.Module):
 
 class TransMIL(HeadState, nn.Module):
     """modules/transmil.py:64-125.  ``model(x)`` with x (1, N, input_dim) or (N, input_dim) -> logits (1, n_classes)."""
+    _TRANSIENT = HeadState._TRANSIENT + ("_bwd_ws",)     # the step's backward workspaces stay with the process too
 
     def __init__(self, input_dim, n_classes, dropout, act):
         super().__init__()
@@ -287,14 +350,56 @@ class TransMIL(HeadState, nn.Module):
         self._act = {"relu": _lib.ACT_RELU, "gelu": _lib.ACT_GELU}.get(act.lower(), _lib.ACT_NONE)
         self._ws = None
         self._train_enabled = False
+        self._one_call = False
 
-    def enable_training(self, mode=True):
+    def enable_training(self, mode=True, one_call=False):
         """Opt in to (or out of) the training path, here and in both attention modules (see
-        NystromAttention.enable_training).  Returns self."""
+        NystromAttention.enable_training).  With ``one_call=True`` a call that needs a graph (or ``train()`` with dropout)
+        is ONE rrt_transmil_forward_train_f32 call and its backward ONE rrt_transmil_backward_f32 call instead of torch
+        ops around the two attentions; ``return_features=True`` with a
+        graph keeps taking the layer path (the step has no feat).  Dropout then uses the library's stateless mask, seeded
+        from torch's CPU generator (``torch.manual_seed`` reproduces a run; a ``drop_seed`` attribute pins it): the
+        distribution of torch's dropout, not its bits.  Returns self."""
         self._train_enabled = bool(mode)
+        self._one_call = bool(mode) and bool(one_call)
         self.layer1.attn.enable_training(mode)
         self.layer2.attn.enable_training(mode)
         return self
+
+    def _backward_workspace(self, need, dev):
+        """the one-call step's backward workspace, kept per device and grown on demand: nothing in it outlives the call (the
+        gradients are fresh tensors, the stash belongs to the graph node), and backward calls of one model on one device are
+        ordered on the stream"""
+        cache = self.__dict__.setdefault("_bwd_ws", {})
+        ws = cache.get(dev)
+        if ws is None or ws.numel() < need:
+            ws = cache[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+        return ws
+
+    def _step_params(self):
+        """the 25 parameters in the order of rrt_transmil_grads' pointers"""
+        ps = [self._fc1[0].weight, self._fc1[0].bias, self.cls_token]
+        for layer in (self.layer1, self.layer2):
+            ps += [layer.norm.weight, layer.norm.bias, layer.attn.to_qkv.weight, layer.attn.to_out[0].weight,
+                   layer.attn.to_out[0].bias, layer.attn.res_conv.weight]
+        convs = (self.pos_layer.proj, self.pos_layer.proj1, self.pos_layer.proj2)
+        ps += [c.weight for c in convs] + [c.bias for c in convs]
+        return ps + [self.norm.weight, self.norm.bias, self._fc2.weight, self._fc2.bias]
+
+    def _forward_step(self, x2d):
+        """The one-call step under autograd -> logits (1, n_classes).  fp32 in every context."""
+        fc1_p = attn_p = 0.0
+        if self.training:
+            fc1_p = float(self._fc1[-1].p) if isinstance(self._fc1[-1], nn.Dropout) else 0.0
+            attn_p = float(self.layer1.attn.to_out[1].p)
+            if float(self.layer2.attn.to_out[1].p) != attn_p:
+                raise NotImplementedError("rrt_mil_amd.TransMIL one-call step: both attention layers must share one dropout p")
+        seed = 0
+        if fc1_p > 0. or attn_p > 0.:
+            fixed = getattr(self, "drop_seed", None)
+            seed = int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        with torch.autocast("cuda", enabled=False):
+            return _TransmilStepFn.apply(self, x2d, fc1_p, attn_p, seed, *self._step_params())
 
     def _forward_layers(self, x2d):
         """The layer path under autograd: torch ops around the two HIP attentions -> (logits (1, n_classes), the
@@ -359,6 +464,8 @@ class TransMIL(HeadState, nn.Module):
         n, in_dim = x2d.shape
         if in_dim != self._fc1[0].in_features:
             raise ValueError(f"expected feature dim {self._fc1[0].in_features}, got {in_dim}")
+        if layer_path and getattr(self, "_one_call", False) and not return_features:
+            return self._forward_step(x2d)
         if layer_path:
             logits, feat = self._forward_layers(x2d)
             return (logits, feat) if return_features else logits

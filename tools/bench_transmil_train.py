@@ -1,12 +1,19 @@
 """One TransMIL training step on the MI355X: forward + backward with all parameter gradients of the ``enable_training()`` model
-(torch ops around the HIP Nystrom attention, csrc/nystrom.hip + csrc/nystrom_bwd.hip) against the same step of the eager
-restatement (tests/nystrom_ref.py in fp32 on the same GPU under autograd), and the per-stage table of one Nystrom layer's
-backward at that size.
+(the layer path: torch ops around the HIP Nystrom attention, csrc/nystrom.hip + csrc/nystrom_bwd.hip), of the
+``enable_training(one_call=True)`` model (ONE rrt_transmil_forward_train_f32 and ONE rrt_transmil_backward_f32 call) and of the
+eager restatement (tests/nystrom_ref.py in fp32 on the same GPU under
+autograd), and the per-stage table of one Nystrom layer's backward at that size.
 
     python tools/bench_transmil_train.py [--out profiles/transmil_train.txt] [--n 9000] [--input-dim 1024] [--reps 20]
+                                         [--layer2 row|full|both]
+
+The cls-row tail's A/B drives the two export families directly, with preallocated stash, workspace and gradients and the loss
+as a torch op in between: --layer2 row is the tail (rrt_debug_transmil_*_row: layer 2's output stage and to_out for the cls row
+alone), --layer2 full the full-row stages instead (rrt_transmil_*, what the step uses); --layer2 both (the default) times both
+in the same alternation and reports the difference.
 
 Timing as tools/bench_transmil.py: HIP events on the stream around each repetition after warm-up, four distinct bags cycled,
-the two variants alternating repetition by repetition; medians (min-max) are reported.  The per-stage rows time each backward
+the variants alternating repetition by repetition; medians (min-max) are reported.  The per-stage rows time each backward
 stage entry point alone (events around batches of 5 calls, launch included) on tensors of the layer's shapes; FLOPs are counted
 from the shapes of this decomposition and the share is of the 157.3 TFLOP/s fp32 matrix peak.
 """
@@ -55,6 +62,7 @@ def main():
     ap.add_argument("--n", type=int, default=9000)
     ap.add_argument("--input-dim", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--layer2", choices=("row", "full", "both"), default="both")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_transmil_train.py needs the MI355X: no HIP device visible")
@@ -64,6 +72,9 @@ def main():
     model.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in state.items()}, strict=True)
     model = model.to(DEV).eval().enable_training()
     sd = {k: v.detach().clone().requires_grad_(True) for k, v in model.state_dict().items()}
+    import copy
+    step_model = copy.deepcopy(model).enable_training(one_call=True)      # the same parameters in a model of its own
+    kinds = ("row", "full") if a.layer2 == "both" else (a.layer2,)
     bags = [torch.from_numpy(synth.bag(N, a.input_dim, tag=f"bench/transmil{i}", nonneg=True)).to(DEV) for i in range(4)]
     label = torch.tensor([1], device=DEV)
     it = [0]
@@ -72,6 +83,54 @@ def main():
         it[0] += 1
         model.zero_grad(set_to_none=True)
         F.cross_entropy(model(bags[it[0] % 4]), label).backward()
+
+    def module_step():
+        it[0] += 1
+        step_model.zero_grad(set_to_none=True)
+        F.cross_entropy(step_model(bags[it[0] % 4]), label).backward()
+
+    def module_fwd():
+        it[0] += 1
+        return step_model(bags[it[0] % 4])
+
+    def driver(kind):
+        """the step through one export family, called directly: (run, forward only, gradients, stash bytes, workspace bytes)"""
+        lib = _lib.load()
+        sizes, fwd_fn, bwd_fn = ((lib.rrt_debug_transmil_train_sizes_row, lib.rrt_debug_transmil_forward_train_row_f32,
+                                  lib.rrt_debug_transmil_backward_row_f32) if kind == "row" else
+                                 (lib.rrt_transmil_train_sizes, lib.rrt_transmil_forward_train_f32, lib.rrt_transmil_backward_f32))
+        keep = []
+        d, w = step_model._desc_weights(keep)
+        params = step_model._step_params()
+        sb, wb = C.c_size_t(), C.c_size_t()
+        _lib.check(sizes(C.byref(d), N, C.byref(sb), C.byref(wb)), "train_sizes")
+        stash = torch.empty(sb.value, dtype=torch.uint8, device=DEV)
+        wsp = torch.empty(wb.value, dtype=torch.uint8, device=DEV)
+        grads = [torch.empty_like(p_) for p_ in params]
+        gs = _lib.TransmilGrads()
+        slots = (C.c_void_p * len(grads)).from_buffer(gs)
+        for i_, g_ in enumerate(grads):
+            slots[i_] = g_.data_ptr()
+        logits = torch.empty((1, 2), device=DEV)
+        stream = lambda: torch.cuda.current_stream().cuda_stream   # noqa: E731
+
+        def fwd():
+            it[0] += 1
+            x = bags[it[0] % 4]
+            _lib.check(fwd_fn(C.byref(d), C.byref(w), x.data_ptr(), logits.data_ptr(), N, stash.data_ptr(), stash.numel(), 0.0, 0.0,
+                              0, stream()), "forward_train")
+            return x
+
+        def run():
+            x = fwd()
+            lg = logits.detach().clone().requires_grad_(True)
+            F.cross_entropy(lg, label).backward()
+            _lib.check(bwd_fn(C.byref(d), C.byref(w), x.data_ptr(), lg.grad.data_ptr(), stash.data_ptr(), stash.numel(),
+                              C.byref(gs), None, N, wsp.data_ptr(), wsp.numel(), 0.0, 0.0, 0, stream()), "backward")
+        return run, fwd, grads, sb.value, wb.value, keep      # (keep: the weight tensors the struct points to)
+
+    drivers = {k: driver(k) for k in kinds}
+    step_fns = {k: (v[0], v[1]) for k, v in drivers.items()}
 
     def eager():
         it[0] += 1
@@ -90,18 +149,40 @@ def main():
     for _ in range(3):
         hip()
         eager()
+        module_step()
+        for run, _ in step_fns.values():
+            run()
     torch.cuda.synchronize()
     it[0] = 0
     hip()
     it[0] = 0
     eager()
     worst = max(float((p.grad - sd[k].grad).abs().max() / sd[k].grad.abs().max()) for k, p in model.named_parameters())
+    it[0] = 0
+    module_step()
+    worst_module = max(float((p.grad - sd[k].grad).abs().max() / sd[k].grad.abs().max()) for k, p in step_model.named_parameters())
+    worst_step = {}
+    by_id = {id(p_): k for k, p_ in step_model.named_parameters()}
+    for kind, (run, _) in step_fns.items():
+        it[0] = 0
+        run()
+        torch.cuda.synchronize()
+        worst_step[kind] = max(float((g_ - sd[by_id[id(p_)]].grad).abs().max() / sd[by_id[id(p_)]].grad.abs().max())
+                               for p_, g_ in zip(step_model._step_params(), drivers[kind][2]))
     t_hip, t_eager, f_hip, f_eager = [], [], [], []
-    for _ in range(reps):                                   # alternate: clock drift hits both alike
+    t_step, f_step = {k: [] for k in step_fns}, {k: [] for k in step_fns}
+    t_mod, f_mod = [], []
+    for _ in range(reps):                                   # alternate: clock drift hits all alike
         t_hip += timed(hip, 1)
         t_eager += timed(eager, 1)
+        t_mod += timed(module_step, 1)
+        for kind, (run, fwd) in step_fns.items():
+            t_step[kind] += timed(run, 1)
         f_hip += timed(fwd_hip, 1)
         f_eager += timed(fwd_eager, 1)
+        f_mod += timed(module_fwd, 1)
+        for kind, (run, fwd) in step_fns.items():
+            f_step[kind] += timed(fwd, 1)
     side = math.isqrt(N - 1) + 1
     rows = 1 + side * side
     npad = (rows + 255) // 256 * 256
@@ -113,8 +194,31 @@ def main():
              f"eager PyTorch fp32 under autograd on the same GPU (nystrom_ref)             {med(t_eager)}   {1e3 / me:7.1f} steps/s"
              f"   ratio {me / mh:.2f}x",
              f"  of which the forward with the graph recorded: HIP path {med(f_hip)}, eager {med(f_eager)}",
-             f"worst parameter-gradient difference between the two on one bag, relative to the gradient's largest entry: {worst:.2e}",
-             ""]
+             f"worst parameter-gradient difference between the two on one bag, relative to the gradient's largest entry: {worst:.2e}"]
+    def overlap(u, v):
+        return "ranges overlap" if min(u) <= max(v) and min(v) <= max(u) else "ranges do not overlap"
+
+    mm = statistics.median(t_mod)
+    sb, wb = C.c_size_t(), C.c_size_t()
+    d_t, _w = step_model._desc_weights([])
+    _lib.check(_lib.load().rrt_transmil_train_sizes(C.byref(d_t), N, C.byref(sb), C.byref(wb)), "rrt_transmil_train_sizes")
+    lines += [f"one-call step, enable_training(one_call=True) (rrt_transmil_forward_train_f32 + rrt_transmil_backward_f32)   "
+              f"{med(t_mod)}   {1e3 / mm:7.1f} steps/s   layer path / this = {mh / mm:.3f}x ({overlap(t_mod, t_hip)})",
+              f"  of which the forward with the graph recorded: {med(f_mod)}; stash {sb.value / 1e6:.1f} MB, backward workspace "
+              f"{wb.value / 1e6:.1f} MB; worst parameter-gradient difference to eager {worst_module:.2e}",
+              "the two export families called directly (preallocated stash, workspace and gradients; no dx; the loss a torch op):"]
+    names = {"row": "  layer 2 on the cls-row tail (rrt_debug_transmil_*_row)   ",
+             "full": "  layer 2 on the full-row stages (rrt_transmil_*, the step)"}
+    for kind in step_fns:
+        ms = statistics.median(t_step[kind])
+        lines += [f"{names[kind]}   {med(t_step[kind])}   {1e3 / ms:7.1f} steps/s; forward only {med(f_step[kind])}; stash "
+                  f"{drivers[kind][3] / 1e6:.1f} MB; worst parameter-gradient difference to eager {worst_step[kind]:.2e}"]
+    if len(step_fns) == 2:
+        dr, df = statistics.median(t_step["row"]), statistics.median(t_step["full"])
+        lines.append(f"cls-row tail against the full-row stages: {df - dr:+.3f} ms per step in the tail's favour "
+                     f"({overlap(t_step['row'], t_step['full'])}); the stage table's to_out linear backward + output_backward below "
+                     f"are what the tail replaces in the backward")
+    lines.append("")
 
     # ---- one Nystrom layer's backward, stage by stage
     lib, h, d, m, dim = _lib.load(), 8, 64, 256, 512

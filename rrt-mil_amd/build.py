@@ -12,8 +12,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librrt_hip.so")
 STAMP = os.path.join(HERE, "csrc", ".build_stamp")
 SOURCES = ["ln_partition.hip", "cast16.hip", "linear_f32.hip", "region_attn.hip", "region_attn_hd.hip", "rmsa_fused.hip", "rmsa_fused16.hip", "rmsa_pair16.hip", "rmsa_fused_x3.hip", "crmsa.hip", "epeg_variants.hip", "mil_pool.hip", "clam_pool.hip", "dsmil_pool.hip", "bag_pool.hip", "linear_bwd.hip", "ln_bwd.hip", "attn_bwd.hip", "crmsa_bwd.hip", "peg.hip", "nystrom.hip", "nystrom_bwd.hip", "nystrom_row.hip", "transmil_bwd.hip",
-           "api.hip"]
-HEADERS = ["common.h", "internal.h", "fused16.h", "nystrom_tiles.h", os.path.join("..", "..", "include", "rrt_hip.h")]
+           "api.hip", "api_nystrom.hip"]
+HEADERS = ["common.h", "internal.h", "api_internal.h", "fused16.h", "nystrom_tiles.h", os.path.join("..", "..", "include", "rrt_hip.h")]
 # -amdgpu-mfma-vgpr-form: gfx950 has one unified VGPR/AGPR file; keep MFMA accumulators in VGPRs so the
 # softmax / rescale VALU code does not shuttle them through v_accvgpr_read/write (hazard stalls).
 # -amdgpu-kernarg-preload-count: the leading kernel arguments (pointers, sizes: up to 16 dwords) arrive in SGPRs with the
@@ -65,7 +65,7 @@ def packed_fp32_census(obj, seen=None):
         shutil.copy(obj, local)
         subprocess.run([OBJDUMP, "--offloading", local], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         for f in sorted(os.listdir(tmp)):
-            if "amdgcn" in f:                          # (a host-only unit -- api.hip: launches only -- has none)
+            if "amdgcn" in f:                          # (a host-only unit -- api*.hip: launches only -- has none)
                 outs.append(subprocess.run([OBJDUMP, "-d", "-C", os.path.join(tmp, f)], check=True, capture_output=True,
                                            text=True).stdout)
     finally:

@@ -1,19 +1,17 @@
-// api.hip -- the C ABI of librrt_hip.so (include/rrt_hip.h): geometry, workspace
-// carving and the launch sequence of one RRTEncoder forward (modules/rrt.py:165-202).
+// api.hip -- the C ABI of librrt_hip.so (include/rrt_hip.h) around the encoder: error strings, geometry, workspace carving, the
+// kernel plan and launch sequence of one RRTEncoder forward (modules/rrt.py:165-202), the stage entries, the heads, the
+// batch-of-bags executor and the encoder's training.  Nystrom attention and TransMIL live in api_nystrom.hip.
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
 
-#include "internal.h"
+#include "api_internal.h"
+
+using namespace rrt_api;
 
 namespace {
 
 thread_local char g_detail[256] = "";
-
-int unsupported(const char* why) {
-  snprintf(g_detail, sizeof(g_detail), "%s", why);
-  return RRT_E_UNSUPPORTED;
-}
 
 int64_t ceil_sqrt(int64_t n) {
   int64_t r = (int64_t)floor(sqrt((double)n));
@@ -21,30 +19,6 @@ int64_t ceil_sqrt(int64_t n) {
   while ((r + 1) * (r + 1) <= n) ++r;
   return r * r == n ? r : r + 1;
 }
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// The one bump allocator behind every workspace carve.  A carve function states its layout once, as a sequence of take()s,
-// and serves both the size query (base = null: every pointer is null, only bytes() counts) and the real carve, so a size can
-// never disagree with the pointers handed out.  Every piece starts on a 256-byte boundary.
-struct Arena {
-  char* base;
-  size_t off = 0;
-  template <typename T = float>
-  T* take(size_t count) {
-    T* p = base ? (T*)(base + off) : nullptr;
-    off = align_up(off + count * sizeof(T), 256);
-    return p;
-  }
-  size_t bytes() const { return off; }
-};
-
-// a failed launch (or any other HIP call) ends the entry point with the HIP error as its return code
-#define RRT_TRY(call)                     \
-  do {                                    \
-    const hipError_t e_ = (call);         \
-    if (e_ != hipSuccess) return (int)e_; \
-  } while (0)
 
 struct Workspace {
   float *uo, *qkv, *xa, *xb, *mean_rstd, *logits, *wdisp, *rep, *rep_qkv, *rep_o, *rep2, *v8, *hid;
@@ -117,6 +91,29 @@ Workspace carve(const rrt_encoder_desc& d, int64_t N, const rrt_grid& g, const r
   w.bytes = a.bytes() ? a.bytes() : 256;
   return w;
 }
+
+}  // namespace
+
+// what api_nystrom.hip calls too (api_internal.h)
+namespace rrt_api {
+
+int unsupported(const char* why) {
+  snprintf(g_detail, sizeof(g_detail), "%s", why);
+  return RRT_E_UNSUPPORTED;
+}
+
+// the dropout configuration of one training call (DropCfg: api_internal.h)
+int make_drop(float p, DropCfg* d) {
+  if (!(p >= 0.f) || p >= 1.f) return RRT_E_INVALID;
+  d->thresh = p > 0.f ? (unsigned)((double)p * 4294967296.0) : 0u;
+  if (p > 0.f && d->thresh == 0) d->thresh = 1;
+  d->scale = 1.0f / (1.0f - p);
+  return RRT_OK;
+}
+
+}  // namespace rrt_api
+
+namespace {
 
 int check_desc(const rrt_encoder_desc* d, int64_t N) {
   if (!d || N <= 0) return RRT_E_INVALID;
@@ -562,22 +559,19 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
     const bool split = plan.casts == CastKind::Split;
     const size_t per_w = split ? 2 : 1;
     Cast16Jobs jobs{};
-    auto add = [&](const float* src, uint16_t* dst, size_t n) {
-      jobs.src[jobs.count] = src; jobs.dst[jobs.count] = dst; jobs.n4[jobs.count++] = n / 4;
-    };
     if (plan.casts != CastKind::None) {
       for (int li = 0; li < desc->n_rmsa_layers; ++li) {
         const rrt_attn_weights& lw = w->rmsa[li];
         if (!lw.qkv_w || !lw.proj_w) return RRT_E_INVALID;
         uint16_t* base = ws.w16 + (size_t)li * per_w * 4 * D * D;
-        add(lw.qkv_w, base, (size_t)3 * D * D);
-        add(lw.proj_w, base + per_w * 3 * D * D, (size_t)D * D);
+        jobs.add(lw.qkv_w, base, (size_t)3 * D * D);
+        jobs.add(lw.proj_w, base + per_w * 3 * D * D, (size_t)D * D);
       }
     }
     if (plan.inner16) {
       if (!w->crmsa.qkv_w || !w->crmsa.proj_w) return RRT_E_INVALID;
-      add(w->crmsa.qkv_w, ws.wcr16, (size_t)3 * D * D);
-      add(w->crmsa.proj_w, ws.wcr16 + (size_t)3 * D * D, (size_t)D * D);
+      jobs.add(w->crmsa.qkv_w, ws.wcr16, (size_t)3 * D * D);
+      jobs.add(w->crmsa.proj_w, ws.wcr16 + (size_t)3 * D * D, (size_t)D * D);
     }
     if (jobs.count && !desc->weights16_valid) RRT_TRY(split ? launch_cast_split(jobs, st) : launch_cast16(jobs, desc->compute, st));
   }
@@ -814,7 +808,7 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
     // kernel (k "regions" of 64 tokens, no EPEG), then the out-projection on 16-bit operands
     if (plan.front == FrontKind::Region) {
       Cast16Jobs cj{};
-      cj.src[0] = ws.rep; cj.dst[0] = ws.rep16; cj.n4[0] = (size_t)k * R8 * D / 4; cj.count = 1;
+      cj.add(ws.rep, ws.rep16, (size_t)k * R8 * D);
       RRT_TRY(launch_cast16(cj, desc->compute, st));
     }
     RRT_TRY(launch_rmsa_fused16(ws.rep16, ws.wcr16, cw.qkv_b, nullptr, ws.repo16, k, R8, D, desc->crmsa_heads, 0,
@@ -1116,13 +1110,44 @@ int rrt_rmsa_fused_proj_f32(const float* u, const float* qkv_w, const float* qkv
 }
 
 }  // extern "C"
+
 // the merged launch of one layer through the stage entry points (tests): optional test knobs, optional CR-MSA row records
 static int fused_proj_stage(const float* u, const float* qkv_w, const float* qkv_b, const float* pe_w,
                             const float* proj_w, const float* proj_b, const float* resid, float* out, float* o_scratch,
                             int32_t* counters, int32_t dim, int32_t heads, int32_t epeg_k, const rrt_grid* g,
                             int32_t lag, int32_t spin_limit, int32_t wait_extra, const float* ln2_gamma, const float* phi,
-                            int32_t crmsa_k, float* part, void* stream);
+                            int32_t crmsa_k, float* part, void* stream) {
+  if (!u || !qkv_w || !proj_w || !resid || !out || !o_scratch || !counters || !g || dim <= 0 || heads <= 0 || out == resid ||
+      lag < 0 || spin_limit < 0 || wait_extra < 0)
+    return RRT_E_INVALID;
+  if (handover_err_peek(false)) return RRT_E_HANDOVER;
+  const GridDev gd = to_dev(*g);
+  const int ek = pe_w ? epeg_k : 0, R = gd.rs * gd.rs;
+  if (!rmsa_fused_proj_supported(R, gd.P, dim, heads, ek, RRT_COMPUTE_F32) || !rmsa_fused_supported_rows(gd.Np, dim))
+    return unsupported("rmsa_fused_proj: needs what rmsa_fused needs (head dim 64, 64 < P <= 208, epeg_k <= 63) and at "
+                       "least two rounds of (region, head) items (heads * regions >= 2 x the CU count)");
+  RRT_TRY(hipMemsetAsync(counters, 0, (size_t)R * sizeof(int32_t), (hipStream_t)stream));
+  FusedProj pj{};
+  pj.Wp = proj_w;
+  pj.bias = proj_b;
+  pj.resid = resid;
+  pj.out = out;
+  pj.cnt = counters;
+  pj.g = gd;
+  pj.lag = lag;
+  pj.spin_limit = spin_limit;
+  pj.wait_for = wait_extra > 0 ? heads + wait_extra : 0;
+  pj.part = part;
+  pj.ln_g = ln2_gamma;
+  pj.phi = phi;
+  pj.k = crmsa_k;
+  if (lag > 0 && (lag < 8 * heads || lag > heads * R)) return unsupported("rmsa_fused_proj: lag must be in [8 * heads, heads * regions]");
+  return (int)launch_rmsa_fused(u, qkv_w, qkv_b, pe_w, o_scratch, R, gd.P, dim, heads, ek, RRT_COMPUTE_F32,
+                                (hipStream_t)stream, nullptr, &pj);
+}
+
 extern "C" {
+
 int rrt_debug_rmsa_fused_proj_f32(const float* u, const float* qkv_w, const float* qkv_b, const float* pe_w,
                                   const float* proj_w, const float* proj_b, const float* resid, float* out, float* o_scratch,
                                   int32_t* counters, int32_t dim, int32_t heads, int32_t epeg_k, const rrt_grid* g,
@@ -1148,50 +1173,13 @@ int rrt_crmsa_combine_parts_f32(const float* x1, const float* part, const float*
   if (!crmsa_combine_parts_supported(dim, k, gd)) return unsupported("crmsa_combine_parts: dim % 64 == 0, dim <= 512, 1 <= k <= 8");
   return (int)launch_crmsa_combine_parts(x1, part, gamma, beta, phi, wdisp, rep, nullptr, 0, dim, k, gd, (hipStream_t)stream);
 }
-}  // extern "C"
-
-static int fused_proj_stage(const float* u, const float* qkv_w, const float* qkv_b, const float* pe_w,
-                            const float* proj_w, const float* proj_b, const float* resid, float* out, float* o_scratch,
-                            int32_t* counters, int32_t dim, int32_t heads, int32_t epeg_k, const rrt_grid* g,
-                            int32_t lag, int32_t spin_limit, int32_t wait_extra, const float* ln2_gamma, const float* phi,
-                            int32_t crmsa_k, float* part, void* stream) {
-  if (!u || !qkv_w || !proj_w || !resid || !out || !o_scratch || !counters || !g || dim <= 0 || heads <= 0 || out == resid ||
-      lag < 0 || spin_limit < 0 || wait_extra < 0)
-    return RRT_E_INVALID;
-  if (handover_err_peek(false)) return RRT_E_HANDOVER;
-  const GridDev gd = to_dev(*g);
-  const int ek = pe_w ? epeg_k : 0, R = gd.rs * gd.rs;
-  if (!rmsa_fused_proj_supported(R, gd.P, dim, heads, ek, RRT_COMPUTE_F32) || !rmsa_fused_supported_rows(gd.Np, dim))
-    return unsupported("rmsa_fused_proj: needs what rmsa_fused needs (head dim 64, 64 < P <= 208, epeg_k <= 63) and at "
-                       "least two rounds of (region, head) items (heads * regions >= 2 x the CU count)");
-  hipError_t e = hipMemsetAsync(counters, 0, (size_t)R * sizeof(int32_t), (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  FusedProj pj{};
-  pj.Wp = proj_w;
-  pj.bias = proj_b;
-  pj.resid = resid;
-  pj.out = out;
-  pj.cnt = counters;
-  pj.g = gd;
-  pj.lag = lag;
-  pj.spin_limit = spin_limit;
-  pj.wait_for = wait_extra > 0 ? heads + wait_extra : 0;
-  pj.part = part;
-  pj.ln_g = ln2_gamma;
-  pj.phi = phi;
-  pj.k = crmsa_k;
-  if (lag > 0 && (lag < 8 * heads || lag > heads * R)) return unsupported("rmsa_fused_proj: lag must be in [8 * heads, heads * regions]");
-  return (int)launch_rmsa_fused(u, qkv_w, qkv_b, pe_w, o_scratch, R, gd.P, dim, heads, ek, RRT_COMPUTE_F32,
-                                (hipStream_t)stream, nullptr, &pj);
-}
-extern "C" {
 
 // ---- 16-bit operand stages of the reduced-precision modes (cast16.hip, linear_f32.hip IN16, rmsa_fused16.hip)
 int rrt_cast16(const float* src, uint16_t* dst, int64_t n, int32_t compute, void* stream) {
   if (!src || !dst || n <= 0 || n % 4) return RRT_E_INVALID;
   if (compute != RRT_COMPUTE_BF16 && compute != RRT_COMPUTE_F16) return unsupported("cast16: compute must be BF16 or F16");
   Cast16Jobs jobs{};
-  jobs.src[0] = src; jobs.dst[0] = dst; jobs.n4[0] = (size_t)n / 4; jobs.count = 1;
+  jobs.add(src, dst, (size_t)n);
   return (int)launch_cast16(jobs, compute, (hipStream_t)stream);
 }
 
@@ -1241,8 +1229,7 @@ int rrt_rmsa_pair16_proj(const uint16_t* u, const uint16_t* qkv_w, const float* 
   if (!rmsa_pair16_proj_supported(R, gd.P, dim, heads, ek))
     return unsupported("rmsa_pair16_proj: head dim 64, regions of 65..96 or 113..128 tokens, a multiple of 16 regions, "
                        "at least two rounds of (pair, head) items");
-  hipError_t e = hipMemsetAsync(cnt, 0, (size_t)(R / 2) * sizeof(int), (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
+  RRT_TRY(hipMemsetAsync(cnt, 0, (size_t)(R / 2) * sizeof(int), (hipStream_t)stream));
   PairProj pj{};
   pj.Wp = proj_w;
   pj.bias = proj_b;
@@ -1257,7 +1244,7 @@ int rrt_rmsa_pair16_proj(const uint16_t* u, const uint16_t* qkv_w, const float* 
 int rrt_cast_split(const float* src, void* dst, int64_t n, void* stream) {
   if (!src || !dst || n <= 0 || n % 32) return RRT_E_INVALID;
   Cast16Jobs jobs{};
-  jobs.src[0] = src; jobs.dst[0] = (uint16_t*)dst; jobs.n4[0] = (size_t)n / 4; jobs.count = 1;
+  jobs.add(src, (uint16_t*)dst, (size_t)n);
   return (int)launch_cast_split(jobs, (hipStream_t)stream);
 }
 
@@ -1326,8 +1313,7 @@ int rrt_crmsa_region4_f32(const float* x1, const float* gamma, const float* beta
   const GridDev gd = to_dev(*g8);
   if (!crmsa_region4_supported(dim, k, gd)) return unsupported("crmsa_region4: dim = 512, k <= 8, regions of 4..576 tokens");
   if (scratch_bytes < 256 + crmsa_region4_scratch_floats(gd, k) * sizeof(float)) return RRT_E_WORKSPACE;
-  hipError_t e = hipMemsetAsync(scratch, 0, 256, (hipStream_t)stream);      // the arrival counters
-  if (e != hipSuccess) return (int)e;
+  RRT_TRY(hipMemsetAsync(scratch, 0, 256, (hipStream_t)stream));      // the arrival counters
   return (int)launch_crmsa_region4(x1, gamma, beta, phi, mean_rstd, logits, wdisp, rep, nullptr, 0,
                                    (float*)((char*)scratch + 256), (int*)scratch, k, gd, (hipStream_t)stream);
 }
@@ -1340,8 +1326,7 @@ int rrt_crmsa_stream4_f32(const float* x1, const float* gamma, const float* beta
   if (!crmsa_stream4_supported(dim, k, gd) || !crmsa_region4_supported(dim, k, gd))
     return unsupported("crmsa_stream4: dim = 512, k <= 8, regions of 16..576 tokens");
   if (scratch_bytes < 256 + crmsa_region4_scratch_floats(gd, k) * sizeof(float)) return RRT_E_WORKSPACE;
-  hipError_t e = hipMemsetAsync(scratch, 0, 256, (hipStream_t)stream);      // the arrival counters
-  if (e != hipSuccess) return (int)e;
+  RRT_TRY(hipMemsetAsync(scratch, 0, 256, (hipStream_t)stream));      // the arrival counters
   return (int)launch_crmsa_stream4(x1, gamma, beta, phi, mean_rstd, logits, wdisp, rep, nullptr, 0,
                                    (float*)((char*)scratch + 256), (int*)scratch, k, gd, (hipStream_t)stream);
 }
@@ -1480,33 +1465,27 @@ int head_front_forward(const HeadFront& f, const HeadWs& ws, const float* x, con
   if (f.input16 != 0 && (f.input16 != gemm_prec || !fc16))
     return unsupported("rrt_mil_forward: 16-bit features (input16) need enc.compute == input16 (bf16 / f16) and input_dim % 64 == 0");
   bool pool16 = false, y16_done = false;
-  hipError_t e;
   if (fc16) {
     const uint16_t* x16 = ws.x16;
     Cast16Jobs cj{};
     if (f.input16) {                 // the caller's features ARE the 16-bit operand: only the weight is cast
       x16 = (const uint16_t*)x;
     } else {
-      cj.src[0] = x; cj.dst[0] = ws.x16; cj.n4[0] = (size_t)N * f.input_dim / 4;
-      cj.count = 1;
+      cj.add(x, ws.x16, (size_t)N * f.input_dim);
     }
-    cj.src[cj.count] = emb_w; cj.dst[cj.count] = ws.w16; cj.n4[cj.count++] = (size_t)D * f.input_dim / 4;
+    cj.add(emb_w, ws.w16, (size_t)D * f.input_dim);
     // the head's first Linears' weights in the same launch (their 16-bit-operand product reads the encoder's y16)
     pool16 = pool_a_w && ws.y16 && !(tuning && env_no_pool16) && f.has_rrt && D % 64 == 0 &&
              ((size_t)pool_hidden * D) % 4 == 0 && cj.count + 2 <= CAST16_MAX_JOBS;
     if (pool16) {
-      cj.src[cj.count] = pool_a_w; cj.dst[cj.count] = ws.pa16; cj.n4[cj.count++] = (size_t)pool_hidden * D / 4;
-      if (pool_b_w) {
-        cj.src[cj.count] = pool_b_w; cj.dst[cj.count] = ws.pb16; cj.n4[cj.count++] = (size_t)pool_hidden * D / 4;
-      }
+      cj.add(pool_a_w, ws.pa16, (size_t)pool_hidden * D);
+      if (pool_b_w) cj.add(pool_b_w, ws.pb16, (size_t)pool_hidden * D);
     }
-    e = launch_cast16(cj, gemm_prec, st);
-    if (e != hipSuccess) return (int)e;
-    e = launch_linear16(x16, ws.w16, ws.emb, (int)N, D, f.input_dim, ep, st);
+    RRT_TRY(launch_cast16(cj, gemm_prec, st));
+    RRT_TRY(launch_linear16(x16, ws.w16, ws.emb, (int)N, D, f.input_dim, ep, st));
   } else {
-    e = launch_linear(x, emb_w, ws.emb, (int)N, D, f.input_dim, ep, st);
+    RRT_TRY(launch_linear(x, emb_w, ws.emb, (int)N, D, f.input_dim, ep, st));
   }
-  if (e != hipSuccess) return (int)e;
   if (f.has_rrt) {
     int rc = encoder_forward(f.enc, enc_w, ws.emb, y_out ? y_out : ws.y, N, ws.enc_ws, ws.enc_bytes, stream, nullptr, nullptr,
                              nullptr, pool16 ? ws.y16 : nullptr, &y16_done);
@@ -1546,7 +1525,6 @@ int pool_predict(const float* y, const float* a_w, const float* a_b, const float
                  float* logits, float* attn, int no_norm, int64_t N, int dim, int hidden, int act,
                  int n_classes, int compute, const PoolWs& ws, hipStream_t st, const uint16_t* y16 = nullptr,
                  const uint16_t* a_w16 = nullptr, const uint16_t* b_w16 = nullptr) {
-  hipError_t e;
   LinearEpilogue ep{};
   ep.prec = compute;
   ep.bias = a_b;
@@ -1558,22 +1536,16 @@ int pool_predict(const float* y, const float* a_w, const float* a_b, const float
   // 23 us for 1.2 GFLOP: 142 blocks on 256 CUs, twice the bytes through the LDS-DMA path -- becomes a 16-bit-operand one)
   const bool p16 = y16 != nullptr && a_w16 != nullptr && (!b_w || b_w16 != nullptr) && dim % 64 == 0 &&
                    (compute == RRT_COMPUTE_BF16 || compute == RRT_COMPUTE_F16);
-  e = p16 ? launch_linear16(y16, a_w16, ws.hid_a, (int)N, hidden, dim, ep, st)
-          : launch_linear(y, a_w, ws.hid_a, (int)N, hidden, dim, ep, st);
-  if (e != hipSuccess) return (int)e;
+  RRT_TRY(p16 ? launch_linear16(y16, a_w16, ws.hid_a, (int)N, hidden, dim, ep, st)
+              : launch_linear(y, a_w, ws.hid_a, (int)N, hidden, dim, ep, st));
   if (b_w) {
     ep.bias = b_b;
     ep.act = RRT_ACT_SIGMOID;
-    e = p16 ? launch_linear16(y16, b_w16, ws.hid_b, (int)N, hidden, dim, ep, st)
-            : launch_linear(y, b_w, ws.hid_b, (int)N, hidden, dim, ep, st);
-    if (e != hipSuccess) return (int)e;
+    RRT_TRY(p16 ? launch_linear16(y16, b_w16, ws.hid_b, (int)N, hidden, dim, ep, st)
+                : launch_linear(y, b_w, ws.hid_b, (int)N, hidden, dim, ep, st));
   }
-  e = launch_pool_partial(y, ws.hid_a, b_w ? ws.hid_b : nullptr, c_w, c_b, ws.a_raw, ws.part, (int)N, dim,
-                          hidden, st);
-  if (e != hipSuccess) return (int)e;
-  e = launch_pool_merge(ws.part, ws.a_raw, pred_w, pred_b, pooled, logits, attn, no_norm, (int)N, dim,
-                        n_classes, st);
-  return (int)e;
+  RRT_TRY(launch_pool_partial(y, ws.hid_a, b_w ? ws.hid_b : nullptr, c_w, c_b, ws.a_raw, ws.part, (int)N, dim, hidden, st));
+  return (int)launch_pool_merge(ws.part, ws.a_raw, pred_w, pred_b, pooled, logits, attn, no_norm, (int)N, dim, n_classes, st);
 }
 
 int check_mil(const rrt_mil_desc* d, int64_t N) {
@@ -1882,9 +1854,7 @@ int rrt_attn_pool_f32(const float* y, const float* hid_a, const float* hid_b, co
   size_t need = 0;
   (void)rrt_attn_pool_workspace_size(n_tokens, dim, hidden, &need);
   if (!workspace || workspace_bytes < need) return RRT_E_WORKSPACE;
-  hipError_t e = launch_pool_partial(y, hid_a, hid_b, c_w, c_b, a_raw, (float*)workspace, (int)n_tokens, dim, hidden,
-                                     (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
+  RRT_TRY(launch_pool_partial(y, hid_a, hid_b, c_w, c_b, a_raw, (float*)workspace, (int)n_tokens, dim, hidden, (hipStream_t)stream));
   return (int)launch_pool_merge((const float*)workspace, a_raw, nullptr, nullptr, pooled, nullptr, attn, 0, (int)n_tokens, dim, 0,
                                 (hipStream_t)stream);
 }
@@ -2025,24 +1995,21 @@ int rrt_clam_forward_f32(const rrt_clam_desc* desc, const rrt_clam_weights* w, c
   ep.prec = gemm_precision(desc->enc.compute);
   ep.bias = w->a_b;
   ep.act = RRT_ACT_TANH;
-  hipError_t e = p16 ? launch_linear16(hw.y16, hw.pa16, cws.hid_a, (int)n_tokens, H, D, ep, st)
-                     : launch_linear(y, w->a_w, cws.hid_a, (int)n_tokens, H, D, ep, st);
-  if (e != hipSuccess) return (int)e;
+  RRT_TRY(p16 ? launch_linear16(hw.y16, hw.pa16, cws.hid_a, (int)n_tokens, H, D, ep, st)
+              : launch_linear(y, w->a_w, cws.hid_a, (int)n_tokens, H, D, ep, st));
   if (desc->gated) {
     ep.bias = w->b_b;
     ep.act = RRT_ACT_SIGMOID;
-    e = p16 ? launch_linear16(hw.y16, hw.pb16, cws.hid_b, (int)n_tokens, H, D, ep, st)
-            : launch_linear(y, w->b_w, cws.hid_b, (int)n_tokens, H, D, ep, st);
-    if (e != hipSuccess) return (int)e;
+    RRT_TRY(p16 ? launch_linear16(hw.y16, hw.pb16, cws.hid_b, (int)n_tokens, H, D, ep, st)
+                : launch_linear(y, w->b_w, cws.hid_b, (int)n_tokens, H, D, ep, st));
   }
   float* raw = a_raw ? a_raw : cws.a_raw;
   float* at = attn ? attn : (topk_idx ? cws.attn : nullptr);
-  e = launch_branch_pool(y, cws.hid_a, desc->gated ? cws.hid_b : nullptr, w->c_w, w->c_b, w->cls_w, w->cls_b,
-                         features ? features : cws.pooled, logits, at, raw, cws.part, desc->per_branch, desc->n_classes,
-                         (int)n_tokens, D, H, K, st);
-  if (e != hipSuccess) return (int)e;
-  if (topk_idx) e = launch_topk_rows(at, (long long*)topk_idx, K, (int)n_tokens, desc->k_sample, st);
-  return (int)e;
+  RRT_TRY(launch_branch_pool(y, cws.hid_a, desc->gated ? cws.hid_b : nullptr, w->c_w, w->c_b, w->cls_w, w->cls_b,
+                             features ? features : cws.pooled, logits, at, raw, cws.part, desc->per_branch, desc->n_classes,
+                             (int)n_tokens, D, H, K, st));
+  if (topk_idx) RRT_TRY(launch_topk_rows(at, (long long*)topk_idx, K, (int)n_tokens, desc->k_sample, st));
+  return RRT_OK;
 }
 
 // ---- DSMIL head: the instance stream and the bag stream alone, and the one-call MILNet forward
@@ -2119,8 +2086,7 @@ int rrt_dsmil_forward_f32(const rrt_dsmil_desc* desc, const rrt_dsmil_weights* w
   rc = head_front_forward(head_front(desc), hw, x, w->emb_w, w->emb_b, &w->enc, nullptr, nullptr, 0, nullptr, /*tuning=*/false,
                           n_tokens, stream, &p16);
   if (rc) return rc;
-  hipError_t e = launch_instance_max(hw.y, w->icls_w, w->icls_b, nullptr, cm, am, ds.imax.pv, ds.imax.pi, (int)n_tokens, D, K, st);
-  if (e != hipSuccess) return (int)e;
+  RRT_TRY(launch_instance_max(hw.y, w->icls_w, w->icls_b, nullptr, cm, am, ds.imax.pv, ds.imax.pi, (int)n_tokens, D, K, st));
   // (feats = the embedding: the bag stream reads it AFTER the encoder has run)
   return (int)launch_dsmil_pool(hw.emb, am, w->q_w, w->q_b, w->fcc_w, w->fcc_b, logits, A, B, ds.pool.raw, ds.pool.v, ds.pool.vb,
                                 ds.pool.lpart, ds.pool.part, (int)n_tokens, D, desc->q_dim, K, st);
@@ -2355,10 +2321,7 @@ int rrt_executor_forward(rrt_executor* ex, const rrt_encoder_weights* w, const r
   for (int s = 1; s < S; ++s) sts[s] = ex->streams[s];
   hipError_t e = hipSuccess;
   // (the previous call may have come from ANOTHER stream: its slot-0 work, on that stream, owns workspace 0 until it is done)
-  if (ex->has_done0) {
-    e = hipStreamWaitEvent(caller, ex->done0, 0);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (ex->has_done0) RRT_TRY(hipStreamWaitEvent(caller, ex->done0, 0));
   static const bool no_fork = rrt_tune_env("RRT_EXEC_NOFORK") != nullptr;      // (bisecting, tuning build only)
   if (S > 1 && !no_fork) {
     e = hipEventRecord(ex->fork, caller);
@@ -2572,9 +2535,8 @@ int rrt_reduce_partials_f32(const float* part, float* out, float* out_tr, int32_
   if (copies < 1 || copies > REDUCE_MAX_JOBS) return RRT_E_INVALID;
   ReduceJobs rj{};
   for (int c = 0; c < copies; ++c) {
-    hipError_t e = reduce_or_defer(&rj, part, out + (size_t)c * n, S, (size_t)n, st, (size_t)(out_tr ? split : 0),
-                                   out_tr ? out_tr + (size_t)c * tr_dim * tr_k : nullptr, tr_dim, tr_k);
-    if (e != hipSuccess) return (int)e;
+    RRT_TRY(reduce_or_defer(&rj, part, out + (size_t)c * n, S, (size_t)n, st, (size_t)(out_tr ? split : 0),
+                            out_tr ? out_tr + (size_t)c * tr_dim * tr_k : nullptr, tr_dim, tr_k));
   }
   return (int)launch_reduce_jobs(rj, st);
 }
@@ -2784,18 +2746,6 @@ int rrt_encoder_train_sizes(const rrt_encoder_desc* desc, int64_t n_tokens, size
 }
 
 namespace {
-struct DropCfg {
-  unsigned thresh;
-  float scale;
-  unsigned seed(uint64_t base, int layer) const { return (unsigned)(base ^ (base >> 32)) + 0x9E3779B9u * (unsigned)(layer + 1); }
-};
-int make_drop(float p, DropCfg* d) {
-  if (!(p >= 0.f) || p >= 1.f) return RRT_E_INVALID;
-  d->thresh = p > 0.f ? (unsigned)((double)p * 4294967296.0) : 0u;
-  if (p > 0.f && d->thresh == 0) d->thresh = 1;
-  d->scale = 1.0f / (1.0f - p);
-  return RRT_OK;
-}
 constexpr int DROP_LAYER_CRMSA = 100;
 // stochastic depth (TransLayer.drop_path, rrt.py:102,125,129): per-call multipliers of the residual branches,
 // host array [2][RRT_MAX_RMSA_LAYERS + 1] = {attention branches, FFN branches}, index n_rmsa_layers = CR-MSA's
@@ -2991,17 +2941,14 @@ int rrt_encoder_forward_train_f32(const rrt_encoder_desc* desc, const rrt_encode
   const GridDev gid = identity_grid(N);
   auto train_ffn = [&](const rrt_attn_weights& lw, const float* xi, int idx) -> int {
     if (!lw.norm2_w || !lw.norm2_b || !lw.fc1_w || !lw.fc1_b || !lw.fc2_w || !lw.fc2_b) return RRT_E_INVALID;
-    hipError_t fe = launch_layernorm(xi, nullptr, lw.norm2_w, lw.norm2_b, s.ffn_u[idx], (int)N, D, st);
-    if (fe != hipSuccess) return (int)fe;
+    RRT_TRY(launch_layernorm(xi, nullptr, lw.norm2_w, lw.norm2_b, s.ffn_u[idx], (int)N, D, st));
     LinearEpilogue e1{};
     e1.prec = desc->compute;
     e1.bias = lw.fc1_b;
-    fe = launch_linear(s.ffn_u[idx], lw.fc1_w, s.ffn_hpre[idx], (int)N, desc->ffn_hidden, D, e1, st);
-    if (fe != hipSuccess) return (int)fe;
+    RRT_TRY(launch_linear(s.ffn_u[idx], lw.fc1_w, s.ffn_hpre[idx], (int)N, desc->ffn_hidden, D, e1, st));
     // the Mlp's two dropouts (rrt.py:38-40): after the activation and after fc2 (before the residual)
-    fe = launch_act_forward(s.ffn_hpre[idx], s.hscr, (size_t)N * desc->ffn_hidden, desc->ffn_act, dc.thresh,
-                            dc.seed(drop_seed, 200 + 2 * idx), dc.scale, st);
-    if (fe != hipSuccess) return (int)fe;
+    RRT_TRY(launch_act_forward(s.ffn_hpre[idx], s.hscr, (size_t)N * desc->ffn_hidden, desc->ffn_act, dc.thresh,
+                               dc.seed(drop_seed, 200 + 2 * idx), dc.scale, st));
     LinearEpilogue e2 = proj_epilogue(lw.fc2_b, xi, gid, RRT_COMPUTE_F32);      // (fc2 of the training FFN: exact fp32 in every mode)
     const float bsf = br.ffn[idx < RRT_MAX_RMSA_LAYERS ? idx : desc->n_rmsa_layers];
     e2.drop_thresh = dc.thresh;
@@ -3178,26 +3125,20 @@ int rrt_encoder_backward_f32(const rrt_encoder_desc* desc, const rrt_encoder_wei
   auto ffn_backward = [&](const rrt_attn_weights& lw, const rrt_attn_grads& lg, const float* xi, int idx) -> int {
     if (!lg.norm2 || !lg.fc1_w || !lg.fc1_b || !lg.fc2_w || !lg.fc2_b) return RRT_E_INVALID;
     const int Hd = desc->ffn_hidden;
-    hipError_t fe = launch_act_forward(s.ffn_hpre[idx], b.fh, (size_t)N * Hd, desc->ffn_act, dc.thresh,
-                                       dc.seed(drop_seed, 200 + 2 * idx), dc.scale, st);
-    if (fe != hipSuccess) return (int)fe;
+    RRT_TRY(launch_act_forward(s.ffn_hpre[idx], b.fh, (size_t)N * Hd, desc->ffn_act, dc.thresh, dc.seed(drop_seed, 200 + 2 * idx),
+                               dc.scale, st));
     const float* dyf = cur;                        // d(fc2 output): the residual's gradient through the second mask
     const float bsf = br.ffn[idx < RRT_MAX_RMSA_LAYERS ? idx : desc->n_rmsa_layers];
     if (dc.thresh || bsf != 1.0f) {
-      fe = launch_copy_drop_mask(cur, b.fdu, (size_t)N * D, dc.thresh, dc.seed(drop_seed, 201 + 2 * idx), dc.scale * bsf, st);
-      if (fe != hipSuccess) return (int)fe;
+      RRT_TRY(launch_copy_drop_mask(cur, b.fdu, (size_t)N * D, dc.thresh, dc.seed(drop_seed, 201 + 2 * idx), dc.scale * bsf, st));
       dyf = b.fdu;
     }
-    fe = launch_linear_backward(dyf, b.fh, lw.fc2_w, b.fdh, lg.fc2_w, lg.fc2_b, N, D, Hd, desc->compute, b.lin, st);
-    if (fe != hipSuccess) return (int)fe;
-    fe = launch_act_backward(b.fdh, s.ffn_hpre[idx], (size_t)N * Hd, desc->ffn_act, dc.thresh,
-                             dc.seed(drop_seed, 200 + 2 * idx), dc.scale, st);
-    if (fe != hipSuccess) return (int)fe;
-    fe = launch_linear_backward(b.fdh, s.ffn_u[idx], lw.fc1_w, b.fdu, lg.fc1_w, lg.fc1_b, N, Hd, D, desc->compute, b.lin, st);
-    if (fe != hipSuccess) return (int)fe;
+    RRT_TRY(launch_linear_backward(dyf, b.fh, lw.fc2_w, b.fdh, lg.fc2_w, lg.fc2_b, N, D, Hd, desc->compute, b.lin, st));
+    RRT_TRY(launch_act_backward(b.fdh, s.ffn_hpre[idx], (size_t)N * Hd, desc->ffn_act, dc.thresh, dc.seed(drop_seed, 200 + 2 * idx),
+                                dc.scale, st));
+    RRT_TRY(launch_linear_backward(b.fdh, s.ffn_u[idx], lw.fc1_w, b.fdu, lg.fc1_w, lg.fc1_b, N, Hd, D, desc->compute, b.lin, st));
     float* nxt = (cur == b.dxa) ? b.dxb : b.dxa;
-    fe = launch_ln_backward(b.fdu, xi, lw.norm2_w, cur, nxt, lg.norm2, ln_part(), N, D, nullptr, st, defer);
-    if (fe != hipSuccess) return (int)fe;
+    RRT_TRY(launch_ln_backward(b.fdu, xi, lw.norm2_w, cur, nxt, lg.norm2, ln_part(), N, D, nullptr, st, defer));
     cur = nxt;
     return RRT_OK;
   };
@@ -3209,9 +3150,7 @@ int rrt_encoder_backward_f32(const rrt_encoder_desc* desc, const rrt_encoder_wei
     float* nxt = (cur == b.dxa) ? b.dxb : b.dxa;
     float* dbp[3] = {w->pos_b[0] ? gr->pos_b[0] : nullptr, w->pos_b[1] ? gr->pos_b[1] : nullptr,
                      w->pos_b[2] ? gr->pos_b[2] : nullptr};
-    hipError_t pe = launch_peg_backward(xstage_in, cur, w->pos_w, nxt, gr->pos_w, dbp, N, D, desc->peg_k,
-                                        desc->peg_1d, ppeg, b.pegws, st);
-    if (pe != hipSuccess) return (int)pe;
+    RRT_TRY(launch_peg_backward(xstage_in, cur, w->pos_w, nxt, gr->pos_w, dbp, N, D, desc->peg_k, desc->peg_1d, ppeg, b.pegws, st));
     cur = nxt;
     return RRT_OK;
   };
@@ -3334,958 +3273,6 @@ int rrt_encoder_backward_f32(const rrt_encoder_desc* desc, const rrt_encoder_wei
   if (dx) RRT_TRY(launch_layernorm(cur, desc->all_shortcut ? b.dx2 : nullptr, nullptr, nullptr, dx, N, D, st));
   RRT_TRY(launch_reduce_jobs(rj, st));
   return RRT_OK;
-}
-
-}  // extern "C"
-
-// ---- Nystrom attention and the TransMIL baseline (nystrom.hip)
-namespace {
-
-int check_nystrom_heads(int32_t heads) {
-  if (heads < 1 || heads > 16) return unsupported("nystrom: heads must be in 1..16");
-  return RRT_OK;
-}
-int check_nystrom_np(int64_t np) {
-  if (np <= 0) return RRT_E_INVALID;
-  if (np % 256) return unsupported("nystrom: n_padded must be a multiple of num_landmarks = 256");
-  if (np > 1000000 + 255) return unsupported("nystrom: n above 1e6");
-  return RRT_OK;
-}
-int check_nystrom(const rrt_nystrom_desc* d, int64_t n) {
-  if (!d || n <= 0) return RRT_E_INVALID;
-  if (d->dim_head != 64) return unsupported("nystrom: dim_head must be 64");
-  if (d->num_landmarks != 256) return unsupported("nystrom: num_landmarks must be 256");
-  if (d->residual && (d->residual_conv_kernel < 1 || d->residual_conv_kernel % 2 == 0 || d->residual_conv_kernel > 63))
-    return unsupported("nystrom: residual_conv_kernel must be odd and <= 63");
-  if (d->pinv_iterations < 1 || d->pinv_iterations > 16) return unsupported("nystrom: pinv_iterations must be in 1..16");
-  int rc = check_nystrom_heads(d->heads);
-  if (rc) return rc;
-  if (d->dim <= 0 || d->dim % 32 || d->dim > 1024) return unsupported("nystrom: dim must be a multiple of 32, at most 1024");
-  if (n > 1000000) return unsupported("nystrom: n above 1e6");
-  return RRT_OK;
-}
-
-struct NystromWs {
-  float *qkv, *ql, *kl, *a2, *z, *av, *wz, *o, *lattn, *pinv;
-  int64_t np;
-  size_t bytes;
-};
-// with_o = false: without o (the one-call TransMIL step's layer 2 needs one row of it, kept elsewhere)
-NystromWs carve_nystrom(const rrt_nystrom_desc* d, int64_t n, char* base, bool with_o = true) {
-  NystromWs ws{};
-  const int64_t np = (n + 255) / 256 * 256;
-  const size_t hd = (size_t)d->heads * 64, lm = (size_t)d->heads * 256 * 64, mm = (size_t)d->heads * 256 * 256;
-  Arena a{base};
-  ws.np = np;
-  ws.qkv = a.take((size_t)np * 3 * hd);
-  ws.ql = a.take(lm);
-  ws.kl = a.take(lm);
-  ws.a2 = a.take(mm);
-  ws.z = a.take(mm);
-  ws.av = a.take(lm);
-  ws.wz = a.take(lm);
-  if (with_o) ws.o = a.take((size_t)np * hd);
-  ws.lattn = a.take(nystrom_lattn_floats((long)np, d->heads));
-  ws.pinv = a.take(nystrom_pinv_floats(d->heads));
-  ws.bytes = a.bytes();
-  return ws;
-}
-
-// the stages in front of the output: to_qkv, the landmarks, both landmark softmaxes, the pseudo-inverse and wz = z av
-int nystrom_front(const rrt_nystrom_desc* d, const rrt_nystrom_weights* w, const float* x, int64_t n, const NystromWs& ws,
-                  hipStream_t st, float* lse) {
-  const int hd = d->heads * 64;
-  const int64_t pad = ws.np - n;
-  if (pad) RRT_TRY(hipMemsetAsync(ws.qkv, 0, (size_t)pad * 3 * hd * sizeof(float), st));
-  LinearEpilogue ep{};
-  ep.q_cols = hd;
-  ep.q_scale = 0.125f;                       // dim_head^-0.5, dim_head = 64
-  RRT_TRY(launch_linear(x, w->qkv_w, ws.qkv + (size_t)pad * 3 * hd, (int)n, 3 * hd, d->dim, ep, st));
-  RRT_TRY(launch_nystrom_landmarks(ws.qkv, ws.ql, ws.kl, (long)ws.np, d->heads, st));
-  RRT_TRY(launch_nystrom_sim2(ws.ql, ws.kl, ws.a2, d->heads, st));
-  RRT_TRY(launch_nystrom_lattn(ws.qkv, ws.ql, ws.av, ws.lattn, (long)ws.np, d->heads, st, lse));
-  RRT_TRY(launch_nystrom_pinv(ws.a2, ws.z, ws.pinv, d->heads, d->pinv_iterations, st));
-  RRT_TRY(launch_nystrom_zav(ws.z, ws.av, ws.wz, d->heads, st));
-  return RRT_OK;
-}
-
-// y [n, dim] = NystromAttention(x); everything checked by the caller
-int nystrom_forward(const rrt_nystrom_desc* d, const rrt_nystrom_weights* w, const float* x, float* y, int64_t n,
-                    const NystromWs& ws, hipStream_t st, float* lse = nullptr) {
-  const int hd = d->heads * 64;
-  const int64_t pad = ws.np - n;
-  const int rc = nystrom_front(d, w, x, n, ws, st, lse);
-  if (rc) return rc;
-  RRT_TRY(launch_nystrom_output(ws.qkv, ws.kl, ws.wz, d->residual ? w->conv_w : nullptr, ws.o, (long)ws.np, d->heads,
-                                d->residual_conv_kernel, st));
-  LinearEpilogue eo{};
-  eo.bias = w->out_b;
-  RRT_TRY(launch_linear(ws.o + (size_t)pad * hd, w->out_w, y, (int)n, d->dim, hd, eo, st));
-  return RRT_OK;
-}
-
-bool nystrom_weights_ok(const rrt_nystrom_desc* d, const rrt_nystrom_weights* w) {
-  return w->qkv_w && w->out_w && w->out_b && (!d->residual || w->conv_w);
-}
-
-int ceil_sqrt_i64(int64_t n) {
-  int64_t h = (int64_t)ceil(sqrt((double)n));
-  while (h * h < n) ++h;
-  while (h > 1 && (h - 1) * (h - 1) >= n) --h;
-  return (int)h;
-}
-
-int check_transmil(const rrt_transmil_desc* d, int64_t N) {
-  if (!d || N <= 0) return RRT_E_INVALID;
-  if (N > 998001) return unsupported("transmil: n_tokens above 998001 (the 1 + H * H rows must stay within nystrom's n <= 1e6)");
-  int rc = check_nystrom(&d->attn, N);
-  if (rc) return rc;
-  if (d->input_dim <= 0 || d->input_dim % 32) return unsupported("input_dim must be a positive multiple of 32");
-  if (d->act != RRT_ACT_NONE && d->act != RRT_ACT_RELU && d->act != RRT_ACT_GELU) return unsupported("transmil: act must be none/relu/gelu");
-  if (d->n_classes < 1 || d->n_classes > 64) return unsupported("transmil: n_classes must be in 1..64");
-  return RRT_OK;
-}
-
-struct TransmilWs {
-  float *emb, *seq, *seq2, *ln, *att;
-  char* nys;
-  int64_t rows;
-  int side;
-  size_t bytes;
-};
-TransmilWs carve_transmil(const rrt_transmil_desc* d, int64_t N, char* base) {
-  TransmilWs ws{};
-  ws.side = ceil_sqrt_i64(N);
-  ws.rows = 1 + (int64_t)ws.side * ws.side;
-  const size_t D = (size_t)d->attn.dim;
-  Arena a{base};
-  ws.emb = a.take((size_t)N * D);
-  ws.seq = a.take((size_t)ws.rows * D);
-  ws.seq2 = a.take((size_t)ws.rows * D);
-  ws.ln = a.take((size_t)ws.rows * D);
-  ws.att = a.take((size_t)ws.rows * D);
-  ws.nys = a.take<char>(carve_nystrom(&d->attn, ws.rows, nullptr).bytes);
-  ws.bytes = a.bytes();
-  return ws;
-}
-
-// what a query row of the attention matrix needs on top of a forward's workspace of `front` bytes: lse | r, [heads, 256] each
-struct RowWs {
-  float *lse, *r;
-  size_t bytes;
-};
-RowWs carve_row(size_t front, int heads, char* base) {
-  RowWs ws{};
-  Arena a{base};
-  a.take<char>(front);
-  ws.lse = a.take((size_t)heads * 256);
-  ws.r = a.take((size_t)heads * 256);
-  ws.bytes = a.bytes();
-  return ws;
-}
-
-// row `row` (of the n unpadded rows) of the approximated attention matrix, columns 0 .. n - 1 -> attn [heads, n]; ws is as
-// nystrom_forward left it, with rw.lse filled by the same forward
-int nystrom_row(const rrt_nystrom_desc* d, int64_t row, float* attn, int64_t n, const NystromWs& ws, const RowWs& rw,
-                hipStream_t st) {
-  const int64_t pad = ws.np - n;
-  RRT_TRY(launch_nystrom_attn_row(ws.qkv, ws.ql, ws.kl, ws.z, rw.lse, rw.r, attn, (long)(pad + row), (long)ws.np, (long)pad,
-                                  (long)n, d->heads, st));
-  return RRT_OK;
-}
-
-// TransMIL.forward for both exports; everything checked by the caller.  attn1 / attn2 (either may be NULL; rw is read only
-// when one is not): the cls token's row of layer 1 / layer 2, [heads, 1 + H * H].  Without them the launches are those of
-// the plain forward, and logits / feat have the same bits either way (lse is one more store of the landmark merge).
-int transmil_forward(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, const float* x, float* logits, float* feat,
-                     float* attn1, float* attn2, int64_t n_tokens, const TransmilWs& ws, const RowWs& rw, hipStream_t st) {
-  const NystromWs nws = carve_nystrom(&desc->attn, ws.rows, ws.nys);
-  const int D = desc->attn.dim, R = (int)ws.rows;
-  int rc;
-  LinearEpilogue ep{};
-  ep.bias = w->fc1_b;
-  ep.act = desc->act;
-  RRT_TRY(launch_linear(x, w->fc1_w, ws.emb, (int)n_tokens, D, desc->input_dim, ep, st));
-  RRT_TRY(launch_transmil_assemble(ws.emb, w->cls_token, ws.seq, (int)n_tokens, R, D, st));
-  // layer 1: seq += Nystrom(LN(seq))
-  RRT_TRY(launch_layernorm(ws.seq, nullptr, w->layer[0].norm_w, w->layer[0].norm_b, ws.ln, R, D, st));
-  rc = nystrom_forward(&desc->attn, &w->layer[0].attn, ws.ln, ws.att, ws.rows, nws, st, attn1 ? rw.lse : nullptr);
-  if (!rc && attn1) rc = nystrom_row(&desc->attn, 0, attn1, ws.rows, nws, rw, st);
-  if (rc) return rc;
-  RRT_TRY(launch_add_cols(ws.seq, ws.att, (size_t)R, D, D, st));
-  // PPEG: row 0 passes through
-  RRT_TRY(hipMemcpyAsync(ws.seq2, ws.seq, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, st));
-  RRT_TRY(launch_ppeg_side(ws.seq + D, w->pos_w, w->pos_b, ws.seq2 + D, ws.side, D, st));
-  // layer 2
-  RRT_TRY(launch_layernorm(ws.seq2, nullptr, w->layer[1].norm_w, w->layer[1].norm_b, ws.ln, R, D, st));
-  rc = nystrom_forward(&desc->attn, &w->layer[1].attn, ws.ln, ws.att, ws.rows, nws, st, attn2 ? rw.lse : nullptr);
-  if (!rc && attn2) rc = nystrom_row(&desc->attn, 0, attn2, ws.rows, nws, rw, st);
-  if (rc) return rc;
-  RRT_TRY(launch_add_cols(ws.seq2, ws.att, (size_t)R, D, D, st));
-  if (feat) RRT_TRY(hipMemcpyAsync(feat, ws.seq2, (size_t)R * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-  // the head reads row 0 only
-  RRT_TRY(launch_layernorm(ws.seq2, nullptr, w->norm_w, w->norm_b, ws.ln, 1, D, st));
-  RRT_TRY(launch_transmil_head(ws.ln, w->fc2_w, w->fc2_b, logits, D, desc->n_classes, st));
-  return RRT_OK;
-}
-
-bool transmil_weights_ok(const rrt_transmil_desc* desc, const rrt_transmil_weights* w) {
-  if (!w->fc1_w || !w->cls_token || !w->norm_w || !w->norm_b || !w->fc2_w || !w->pos_w[0] || !w->pos_w[1] || !w->pos_w[2])
-    return false;
-  for (int i = 0; i < 2; ++i)
-    if (!w->layer[i].norm_w || !w->layer[i].norm_b || !nystrom_weights_ok(&desc->attn, &w->layer[i].attn)) return false;
-  return true;
-}
-
-}  // namespace
-
-extern "C" {
-
-int rrt_nystrom_workspace_size(const rrt_nystrom_desc* desc, int64_t n, size_t* bytes) {
-  if (!bytes) return RRT_E_INVALID;
-  int rc = check_nystrom(desc, n);
-  if (rc) return rc;
-  *bytes = carve_nystrom(desc, n, nullptr).bytes;
-  return RRT_OK;
-}
-
-int rrt_nystrom_attention_f32(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w, const float* x, float* y, int64_t n,
-                              void* workspace, size_t workspace_bytes, void* stream) {
-  if (!desc || !w || !x || !y) return RRT_E_INVALID;
-  int rc = check_nystrom(desc, n);
-  if (rc) return rc;
-  if (!nystrom_weights_ok(desc, w)) return RRT_E_INVALID;
-  if (!workspace || workspace_bytes < carve_nystrom(desc, n, nullptr).bytes) return RRT_E_WORKSPACE;
-  return nystrom_forward(desc, w, x, y, n, carve_nystrom(desc, n, (char*)workspace), (hipStream_t)stream);
-}
-
-int rrt_nystrom_landmarks_f32(const float* qkv, float* ql, float* kl, int64_t n_padded, int32_t heads, void* stream) {
-  if (!qkv || !ql || !kl) return RRT_E_INVALID;
-  int rc = check_nystrom_np(n_padded);
-  if (!rc) rc = check_nystrom_heads(heads);
-  if (rc) return rc;
-  return (int)launch_nystrom_landmarks(qkv, ql, kl, (long)n_padded, heads, (hipStream_t)stream);
-}
-
-int rrt_nystrom_landmark_sim_f32(const float* ql, const float* kl, float* a2, int32_t heads, void* stream) {
-  if (!ql || !kl || !a2) return RRT_E_INVALID;
-  int rc = check_nystrom_heads(heads);
-  if (rc) return rc;
-  return (int)launch_nystrom_sim2(ql, kl, a2, heads, (hipStream_t)stream);
-}
-
-int rrt_nystrom_landmark_attn_workspace_size(int64_t n_padded, int32_t heads, size_t* bytes) {
-  if (!bytes) return RRT_E_INVALID;
-  int rc = check_nystrom_np(n_padded);
-  if (!rc) rc = check_nystrom_heads(heads);
-  if (rc) return rc;
-  *bytes = nystrom_lattn_floats((long)n_padded, heads) * sizeof(float);
-  return RRT_OK;
-}
-
-int rrt_nystrom_landmark_attn_f32(const float* qkv, const float* ql, float* av, int64_t n_padded, int32_t heads,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
-  if (!qkv || !ql || !av) return RRT_E_INVALID;
-  int rc = check_nystrom_np(n_padded);
-  if (!rc) rc = check_nystrom_heads(heads);
-  if (rc) return rc;
-  if (!workspace || workspace_bytes < nystrom_lattn_floats((long)n_padded, heads) * sizeof(float)) return RRT_E_WORKSPACE;
-  return (int)launch_nystrom_lattn(qkv, ql, av, (float*)workspace, (long)n_padded, heads, (hipStream_t)stream);
-}
-
-int rrt_nystrom_pinv_workspace_size(int32_t heads, size_t* bytes) {
-  if (!bytes) return RRT_E_INVALID;
-  int rc = check_nystrom_heads(heads);
-  if (rc) return rc;
-  *bytes = nystrom_pinv_floats(heads) * sizeof(float);
-  return RRT_OK;
-}
-
-int rrt_nystrom_pinv_f32(const float* a2, float* z, int32_t heads, int32_t iterations, void* workspace, size_t workspace_bytes,
-                         void* stream) {
-  if (!a2 || !z) return RRT_E_INVALID;
-  int rc = check_nystrom_heads(heads);
-  if (rc) return rc;
-  if (iterations < 1 || iterations > 16) return unsupported("nystrom: pinv_iterations must be in 1..16");
-  if (!workspace || workspace_bytes < nystrom_pinv_floats(heads) * sizeof(float)) return RRT_E_WORKSPACE;
-  return (int)launch_nystrom_pinv(a2, z, (float*)workspace, heads, iterations, (hipStream_t)stream);
-}
-
-int rrt_nystrom_zav_f32(const float* z, const float* av, float* wz, int32_t heads, void* stream) {
-  if (!z || !av || !wz) return RRT_E_INVALID;
-  int rc = check_nystrom_heads(heads);
-  if (rc) return rc;
-  return (int)launch_nystrom_zav(z, av, wz, heads, (hipStream_t)stream);
-}
-
-int rrt_nystrom_output_f32(const float* qkv, const float* kl, const float* wz, const float* conv_w, float* o, int64_t n_padded,
-                           int32_t heads, int32_t conv_k, void* stream) {
-  if (!qkv || !kl || !wz || !o) return RRT_E_INVALID;
-  int rc = check_nystrom_np(n_padded);
-  if (!rc) rc = check_nystrom_heads(heads);
-  if (rc) return rc;
-  if (conv_w && (conv_k < 1 || conv_k % 2 == 0 || conv_k > 63)) return unsupported("nystrom: residual_conv_kernel must be odd and <= 63");
-  return (int)launch_nystrom_output(qkv, kl, wz, conv_w, o, (long)n_padded, heads, conv_k, (hipStream_t)stream);
-}
-
-int rrt_ppeg_side_f32(const float* x, const float* const* w, const float* const* b, float* y, int32_t side, int32_t dim,
-                      void* stream) {
-  if (!x || !y || !w || !w[0] || !w[1] || !w[2] || side <= 0 || dim <= 0) return RRT_E_INVALID;
-  if (dim % 4) return unsupported("ppeg: dim must be a multiple of 4");
-  if (side > 1000) return unsupported("ppeg: side above 1000");
-  const float* nob[3] = {nullptr, nullptr, nullptr};
-  hipStream_t st = (hipStream_t)stream;
-  RRT_TRY(hipMemcpyAsync(y, x, (size_t)dim * sizeof(float), hipMemcpyDeviceToDevice, st));
-  return (int)launch_ppeg_side(x + dim, w, b ? b : nob, y + dim, side, dim, st);
-}
-
-int rrt_transmil_workspace_size(const rrt_transmil_desc* desc, int64_t n_tokens, size_t* bytes) {
-  if (!bytes) return RRT_E_INVALID;
-  int rc = check_transmil(desc, n_tokens);
-  if (rc) return rc;
-  *bytes = carve_transmil(desc, n_tokens, nullptr).bytes;
-  return RRT_OK;
-}
-
-int rrt_transmil_forward_f32(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, const float* x, float* logits,
-                             float* feat, int64_t n_tokens, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!desc || !w || !x || !logits) return RRT_E_INVALID;
-  int rc = check_transmil(desc, n_tokens);
-  if (rc) return rc;
-  if (!transmil_weights_ok(desc, w)) return RRT_E_INVALID;
-  if (!workspace || workspace_bytes < carve_transmil(desc, n_tokens, nullptr).bytes) return RRT_E_WORKSPACE;
-  return transmil_forward(desc, w, x, logits, feat, nullptr, nullptr, n_tokens, carve_transmil(desc, n_tokens, (char*)workspace),
-                          RowWs{}, (hipStream_t)stream);
-}
-
-int rrt_transmil_attn_workspace_size(const rrt_transmil_desc* desc, int64_t n_tokens, size_t* bytes) {
-  if (!bytes) return RRT_E_INVALID;
-  int rc = check_transmil(desc, n_tokens);
-  if (rc) return rc;
-  *bytes = carve_row(carve_transmil(desc, n_tokens, nullptr).bytes, desc->attn.heads, nullptr).bytes;
-  return RRT_OK;
-}
-
-int rrt_transmil_forward_attn_f32(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, const float* x, float* logits,
-                                  float* feat, float* attn1, float* attn2, int64_t n_tokens, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
-  if (!desc || !w || !x || !logits) return RRT_E_INVALID;
-  int rc = check_transmil(desc, n_tokens);
-  if (rc) return rc;
-  if (!transmil_weights_ok(desc, w)) return RRT_E_INVALID;
-  const size_t front = carve_transmil(desc, n_tokens, nullptr).bytes;
-  if (!workspace || workspace_bytes < carve_row(front, desc->attn.heads, nullptr).bytes) return RRT_E_WORKSPACE;
-  return transmil_forward(desc, w, x, logits, feat, attn1, attn2, n_tokens, carve_transmil(desc, n_tokens, (char*)workspace),
-                          carve_row(front, desc->attn.heads, (char*)workspace), (hipStream_t)stream);
-}
-
-int rrt_nystrom_attn_row_f32(const float* qkv, const float* ql, const float* kl, const float* z, const float* lse3, float* r,
-                             float* attn, int64_t row_padded, int64_t n_padded, int32_t heads, void* stream) {
-  if (!qkv || !ql || !kl || !z || !lse3 || !r || !attn) return RRT_E_INVALID;
-  int rc = check_nystrom_np(n_padded);
-  if (!rc) rc = check_nystrom_heads(heads);
-  if (rc) return rc;
-  if (row_padded < 0 || row_padded >= n_padded) return unsupported("nystrom: row_padded must be in [0, n_padded)");
-  return (int)launch_nystrom_attn_row(qkv, ql, kl, z, lse3, r, attn, (long)row_padded, (long)n_padded, 0, (long)n_padded, heads,
-                                      (hipStream_t)stream);
-}
-
-int rrt_nystrom_attention_row_workspace_size(const rrt_nystrom_desc* desc, int64_t n, size_t* bytes) {
-  if (!bytes) return RRT_E_INVALID;
-  int rc = check_nystrom(desc, n);
-  if (rc) return rc;
-  *bytes = carve_row(carve_nystrom(desc, n, nullptr).bytes, desc->heads, nullptr).bytes;
-  return RRT_OK;
-}
-
-int rrt_nystrom_attention_row_f32(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w, const float* x, float* y,
-                                  int64_t row, float* attn, int64_t n, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!desc || !w || !x || !y || !attn) return RRT_E_INVALID;
-  int rc = check_nystrom(desc, n);
-  if (rc) return rc;
-  if (!nystrom_weights_ok(desc, w)) return RRT_E_INVALID;
-  if (row < 0 || row >= n) return unsupported("nystrom: row must be in [0, n)");
-  const size_t front = carve_nystrom(desc, n, nullptr).bytes;
-  if (!workspace || workspace_bytes < carve_row(front, desc->heads, nullptr).bytes) return RRT_E_WORKSPACE;
-  const NystromWs ws = carve_nystrom(desc, n, (char*)workspace);
-  const RowWs rw = carve_row(front, desc->heads, (char*)workspace);
-  rc = nystrom_forward(desc, w, x, y, n, ws, (hipStream_t)stream, rw.lse);
-  if (rc) return rc;
-  return nystrom_row(desc, row, attn, n, ws, rw, (hipStream_t)stream);
-}
-
-}  // extern "C"
-
-// ---- Nystrom attention: training (nystrom_bwd.hip)
-namespace {
-
-// the forward's workspace kept whole (what the backward reads: qkv, ql, kl, a2, z, av, wz, o) | lse [heads, 256]
-struct NystromStash {
-  NystromWs f;
-  float* lse;
-  size_t bytes;
-};
-NystromStash carve_nystrom_stash(const rrt_nystrom_desc* d, int64_t n, char* base, bool with_o = true) {
-  NystromStash s{};
-  s.f = carve_nystrom(d, n, base, with_o);
-  Arena a{base};
-  a.take<char>(s.f.bytes);
-  s.lse = a.take((size_t)d->heads * 256);
-  s.bytes = a.bytes();
-  return s;
-}
-
-size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
-
-struct NystromBwdWs {
-  float *d_o, *d_qkv, *d_ql, *d_kl, *d_wz, *d_av, *d_z, *part, *pinv;
-  char* lin;
-  size_t bytes;
-};
-NystromBwdWs carve_nystrom_bwd(const rrt_nystrom_desc* d, int64_t n, char* base) {
-  NystromBwdWs ws{};
-  const int64_t np = (n + 255) / 256 * 256;
-  const int hd = d->heads * 64;
-  const size_t lm = (size_t)d->heads * 256 * 64, mm = (size_t)d->heads * 256 * 256;
-  Arena a{base};
-  ws.d_o = a.take((size_t)np * hd);
-  ws.d_qkv = a.take((size_t)np * 3 * hd);
-  ws.d_ql = a.take(lm);
-  ws.d_kl = a.take(lm);
-  ws.d_wz = a.take(lm);
-  ws.d_av = a.take(lm);
-  ws.d_z = a.take(mm);
-  ws.part = a.take(max_sz(nystrom_output_bwd_floats((long)np, d->heads), nystrom_lattn_bwd_floats((long)np, d->heads)));
-  ws.pinv = a.take(nystrom_pinv_bwd_floats(d->heads, d->pinv_iterations));
-  ws.lin = a.take<char>(max_sz(linear_bwd_workspace((int)n, d->dim, hd), linear_bwd_workspace((int)n, 3 * hd, d->dim)));
-  ws.bytes = a.bytes();
-  return ws;
-}
-
-struct LattnBwdWs {
-  float *fwd, *av, *lse, *bwd;
-  size_t bytes;
-};
-LattnBwdWs carve_lattn_bwd(int64_t np, int heads, char* base) {
-  LattnBwdWs ws{};
-  Arena a{base};
-  ws.fwd = a.take(nystrom_lattn_floats((long)np, heads));
-  ws.av = a.take((size_t)heads * 256 * 64);
-  ws.lse = a.take((size_t)heads * 256);
-  ws.bwd = a.take(nystrom_lattn_bwd_floats((long)np, heads));
-  ws.bytes = a.bytes();
-  return ws;
-}
-
-struct PinvSimBwdWs {
-  float *a2, *bwd;
-  size_t bytes;
-};
-PinvSimBwdWs carve_pinv_sim_bwd(int heads, int iters, char* base) {
-  PinvSimBwdWs ws{};
-  Arena a{base};
-  ws.a2 = a.take((size_t)heads * 256 * 256);
-  ws.bwd = a.take(nystrom_pinv_bwd_floats(heads, iters));
-  ws.bytes = a.bytes();
-  return ws;
-}
-
-int check_pinv_iterations(int32_t iterations) {
-  if (iterations < 1 || iterations > 16) return unsupported("nystrom: pinv_iterations must be in 1..16");
-  return RRT_OK;
-}
-int check_np_heads(int64_t np, int32_t heads) {
-  int rc = check_nystrom_np(np);
-  if (!rc) rc = check_nystrom_heads(heads);
-  return rc;
-}
-
-// the backward behind d_qkv (q and v thirds written, k third zeroed), d_kl and d_wz, which the output stage's adjoint left in
-// b: wz = z av, both landmark softmaxes, the pseudo-inverse, the landmarks and to_qkv.  Writes grads->qkv_w and, unless NULL, dx.
-int nystrom_backward_rest(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w, const float* x, const NystromStash& s,
-                          const NystromBwdWs& b, const rrt_nystrom_grads* grads, float* dx, int64_t n, hipStream_t st) {
-  const int heads = desc->heads, hd = heads * 64;
-  const long np = (long)s.f.np;
-  const int64_t pad = s.f.np - n;
-  RRT_TRY(launch_nystrom_zav_backward(s.f.z, s.f.av, b.d_wz, b.d_z, b.d_av, heads, st));
-  RRT_TRY(launch_nystrom_lattn_backward(s.f.qkv, s.f.ql, s.f.av, s.lse, b.d_av, b.d_qkv, b.d_ql, b.part, np, heads, st));
-  RRT_TRY(launch_nystrom_pinv_sim_backward(s.f.ql, s.f.kl, s.f.a2, b.d_z, b.d_ql, b.d_kl, 1, b.pinv, heads,
-                                           desc->pinv_iterations, st));
-  RRT_TRY(launch_nystrom_landmarks_backward(b.d_ql, b.d_kl, b.d_qkv, np, heads, st));
-  // to_qkv: the forward scales q in the linear's epilogue; the pad rows of dx are dropped
-  float* d_rows = b.d_qkv + (size_t)pad * 3 * hd;
-  RRT_TRY(launch_nystrom_scale_q(d_rows, (long)n, heads, st));
-  RRT_TRY(launch_linear_backward(d_rows, x, w->qkv_w, dx, grads->qkv_w, nullptr, (int)n, 3 * hd, desc->dim, RRT_COMPUTE_F32,
-                                 b.lin, st));
-  return RRT_OK;
-}
-
-// rrt_nystrom_attention_backward_f32 on carved structs; everything checked by the caller
-int nystrom_backward(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w, const float* x, const float* dy,
-                     const NystromStash& s, const NystromBwdWs& b, const rrt_nystrom_grads* grads, float* dx, int64_t n,
-                     hipStream_t st) {
-  const int heads = desc->heads, hd = heads * 64;
-  const long np = (long)s.f.np;
-  const int64_t pad = s.f.np - n;
-  // to_out: the pad rows of d_o are zero
-  if (pad) RRT_TRY(hipMemsetAsync(b.d_o, 0, (size_t)pad * hd * sizeof(float), st));
-  RRT_TRY(launch_linear_backward(dy, s.f.o + (size_t)pad * hd, w->out_w, b.d_o + (size_t)pad * hd, grads->out_w, grads->out_b,
-                                 (int)n, desc->dim, hd, RRT_COMPUTE_F32, b.lin, st));
-  RRT_TRY(launch_nystrom_output_backward(s.f.qkv, s.f.kl, s.f.wz, desc->residual ? w->conv_w : nullptr, b.d_o, b.d_qkv, b.d_kl,
-                                         b.d_wz, grads->conv_w, b.part, np, heads, desc->residual_conv_kernel, st));
-  return nystrom_backward_rest(desc, w, x, s, b, grads, dx, n, st);
-}
-
-}  // namespace
-
-extern "C" {
-
-int rrt_nystrom_train_sizes(const rrt_nystrom_desc* desc, int64_t n, size_t* stash_bytes, size_t* backward_workspace_bytes) {
-  if (!stash_bytes || !backward_workspace_bytes) return RRT_E_INVALID;
-  int rc = check_nystrom(desc, n);
-  if (rc) return rc;
-  *stash_bytes = carve_nystrom_stash(desc, n, nullptr).bytes;
-  *backward_workspace_bytes = carve_nystrom_bwd(desc, n, nullptr).bytes;
-  return RRT_OK;
-}
-
-int rrt_nystrom_attention_forward_train_f32(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w, const float* x, float* y,
-                                            int64_t n, void* stash, size_t stash_bytes, void* stream) {
-  if (!desc || !w || !x || !y) return RRT_E_INVALID;
-  int rc = check_nystrom(desc, n);
-  if (rc) return rc;
-  if (!nystrom_weights_ok(desc, w)) return RRT_E_INVALID;
-  if (!stash || stash_bytes < carve_nystrom_stash(desc, n, nullptr).bytes) return RRT_E_WORKSPACE;
-  const NystromStash s = carve_nystrom_stash(desc, n, (char*)stash);
-  return nystrom_forward(desc, w, x, y, n, s.f, (hipStream_t)stream, s.lse);
-}
-
-int rrt_nystrom_attention_backward_f32(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w, const float* x,
-                                       const float* dy, const void* stash, size_t stash_bytes, const rrt_nystrom_grads* grads,
-                                       float* dx, int64_t n, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!desc || !w || !x || !dy || !grads) return RRT_E_INVALID;
-  int rc = check_nystrom(desc, n);
-  if (rc) return rc;
-  if (!nystrom_weights_ok(desc, w)) return RRT_E_INVALID;
-  if (!grads->qkv_w || !grads->out_w || !grads->out_b || (desc->residual && !grads->conv_w)) return RRT_E_INVALID;
-  if (!stash || stash_bytes < carve_nystrom_stash(desc, n, nullptr).bytes) return RRT_E_WORKSPACE;
-  if (!workspace || workspace_bytes < carve_nystrom_bwd(desc, n, nullptr).bytes) return RRT_E_WORKSPACE;
-  return nystrom_backward(desc, w, x, dy, carve_nystrom_stash(desc, n, (char*)stash), carve_nystrom_bwd(desc, n, (char*)workspace),
-                          grads, dx, n, (hipStream_t)stream);
-}
-
-int rrt_nystrom_output_backward_workspace_size(int64_t n_padded, int32_t heads, size_t* bytes) {
-  if (!bytes) return RRT_E_INVALID;
-  int rc = check_np_heads(n_padded, heads);
-  if (rc) return rc;
-  Arena a{nullptr};
-  a.take(nystrom_output_bwd_floats((long)n_padded, heads));
-  *bytes = a.bytes();
-  return RRT_OK;
-}
-
-int rrt_nystrom_output_backward_f32(const float* qkv, const float* kl, const float* wz, const float* conv_w, const float* d_o,
-                                    float* d_qkv, float* d_kl, float* d_wz, float* d_conv_w, int64_t n_padded, int32_t heads,
-                                    int32_t conv_k, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!qkv || !kl || !wz || !d_o || !d_qkv || !d_kl || !d_wz || (conv_w && !d_conv_w)) return RRT_E_INVALID;
-  int rc = check_np_heads(n_padded, heads);
-  if (rc) return rc;
-  if (conv_w && (conv_k < 1 || conv_k % 2 == 0 || conv_k > 63)) return unsupported("nystrom: residual_conv_kernel must be odd and <= 63");
-  Arena a{(char*)workspace};
-  float* part = a.take(nystrom_output_bwd_floats((long)n_padded, heads));
-  if (!workspace || workspace_bytes < a.bytes()) return RRT_E_WORKSPACE;
-  return (int)launch_nystrom_output_backward(qkv, kl, wz, conv_w, d_o, d_qkv, d_kl, d_wz, d_conv_w, part, (long)n_padded, heads,
-                                             conv_k, (hipStream_t)stream);
-}
-
-int rrt_nystrom_zav_backward_f32(const float* z, const float* av, const float* d_wz, float* d_z, float* d_av, int32_t heads,
-                                 void* stream) {
-  if (!z || !av || !d_wz || !d_z || !d_av) return RRT_E_INVALID;
-  int rc = check_nystrom_heads(heads);
-  if (rc) return rc;
-  return (int)launch_nystrom_zav_backward(z, av, d_wz, d_z, d_av, heads, (hipStream_t)stream);
-}
-
-int rrt_nystrom_landmark_attn_backward_workspace_size(int64_t n_padded, int32_t heads, size_t* bytes) {
-  if (!bytes) return RRT_E_INVALID;
-  int rc = check_np_heads(n_padded, heads);
-  if (rc) return rc;
-  *bytes = carve_lattn_bwd(n_padded, heads, nullptr).bytes;
-  return RRT_OK;
-}
-
-int rrt_nystrom_landmark_attn_backward_f32(const float* qkv, const float* ql, const float* d_av, float* d_qkv, float* d_ql,
-                                           int64_t n_padded, int32_t heads, void* workspace, size_t workspace_bytes,
-                                           void* stream) {
-  if (!qkv || !ql || !d_av || !d_qkv || !d_ql) return RRT_E_INVALID;
-  int rc = check_np_heads(n_padded, heads);
-  if (rc) return rc;
-  if (!workspace || workspace_bytes < carve_lattn_bwd(n_padded, heads, nullptr).bytes) return RRT_E_WORKSPACE;
-  const LattnBwdWs ws = carve_lattn_bwd(n_padded, heads, (char*)workspace);
-  hipStream_t st = (hipStream_t)stream;
-  RRT_TRY(launch_nystrom_lattn(qkv, ql, ws.av, ws.fwd, (long)n_padded, heads, st, ws.lse));
-  return (int)launch_nystrom_lattn_backward(qkv, ql, ws.av, ws.lse, d_av, d_qkv, d_ql, ws.bwd, (long)n_padded, heads, st);
-}
-
-int rrt_nystrom_pinv_sim_backward_workspace_size(int32_t heads, int32_t iterations, size_t* bytes) {
-  if (!bytes) return RRT_E_INVALID;
-  int rc = check_nystrom_heads(heads);
-  if (!rc) rc = check_pinv_iterations(iterations);
-  if (rc) return rc;
-  *bytes = carve_pinv_sim_bwd(heads, iterations, nullptr).bytes;
-  return RRT_OK;
-}
-
-int rrt_nystrom_pinv_sim_backward_f32(const float* ql, const float* kl, const float* d_z, float* d_ql, float* d_kl,
-                                      int32_t heads, int32_t iterations, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!ql || !kl || !d_z || !d_ql || !d_kl) return RRT_E_INVALID;
-  int rc = check_nystrom_heads(heads);
-  if (!rc) rc = check_pinv_iterations(iterations);
-  if (rc) return rc;
-  if (!workspace || workspace_bytes < carve_pinv_sim_bwd(heads, iterations, nullptr).bytes) return RRT_E_WORKSPACE;
-  const PinvSimBwdWs ws = carve_pinv_sim_bwd(heads, iterations, (char*)workspace);
-  hipStream_t st = (hipStream_t)stream;
-  RRT_TRY(launch_nystrom_sim2(ql, kl, ws.a2, heads, st));
-  return (int)launch_nystrom_pinv_sim_backward(ql, kl, ws.a2, d_z, d_ql, d_kl, 0, ws.bwd, heads, iterations, st);
-}
-
-int rrt_nystrom_landmarks_backward_f32(const float* d_ql, const float* d_kl, float* d_qkv, int64_t n_padded, int32_t heads,
-                                       void* stream) {
-  if (!d_ql || !d_kl || !d_qkv) return RRT_E_INVALID;
-  int rc = check_np_heads(n_padded, heads);
-  if (rc) return rc;
-  return (int)launch_nystrom_landmarks_backward(d_ql, d_kl, d_qkv, (long)n_padded, heads, (hipStream_t)stream);
-}
-
-}  // extern "C"
-
-// ---- TransMIL: the one-call training step (transmil_bwd.hip; the stages of nystrom.hip / nystrom_bwd.hip, linear_bwd.hip,
-// ln_bwd.hip and peg.hip composed on carved structs)
-namespace {
-
-constexpr int DROP_TAG_FC1 = 200, DROP_TAG_ATTN1 = 201, DROP_TAG_ATTN2 = 202;
-
-// tail = false (the step): layer 2 is the full-row forward into att2, of which the head reads row 0.  tail = true (the
-// rrt_debug_transmil_*_row twins, the other side of tools/bench_transmil_train.py's A/B): layer 2 runs its output stage and
-// to_out for the cls row alone, and its attention stash holds no o
-struct TransmilStash {
-  float *hpre, *seq0, *ln1, *seq1, *seq2, *ln2, *hrow, *stats, *orow, *yrow, *att2;
-  float* emb;        // forward scratch: the place of ln1, which is written after emb has been read
-  char *nys1, *nys2;
-  int64_t rows;
-  int side;
-  size_t bytes;
-};
-TransmilStash carve_transmil_stash(const rrt_transmil_desc* d, int64_t N, char* base, bool tail) {
-  TransmilStash s{};
-  s.side = ceil_sqrt_i64(N);
-  s.rows = 1 + (int64_t)s.side * s.side;
-  const size_t D = (size_t)d->attn.dim, RD = (size_t)s.rows * D;
-  Arena a{base};
-  if (d->act != RRT_ACT_NONE) s.hpre = a.take((size_t)N * D);
-  s.seq0 = a.take(RD);
-  s.ln1 = a.take(RD);
-  s.emb = s.ln1;
-  s.seq1 = a.take(RD);
-  s.seq2 = a.take(RD);
-  s.ln2 = a.take(RD);
-  s.hrow = a.take(D);
-  s.stats = a.take(2);
-  s.orow = a.take((size_t)d->attn.heads * 64);
-  s.yrow = a.take(D);
-  s.nys1 = a.take<char>(carve_nystrom_stash(&d->attn, s.rows, nullptr).bytes);
-  s.nys2 = a.take<char>(carve_nystrom_stash(&d->attn, s.rows, nullptr, !tail).bytes);
-  if (!tail) s.att2 = a.take(RD);
-  s.bytes = a.bytes();
-  return s;
-}
-
-struct TransmilBwdWs {
-  float *dgb, *d_hrow, *d_yrow, *d_orow, *A, *B, *C;
-  char *nys, *lnp, *ppeg, *lin;
-  size_t bytes;
-};
-TransmilBwdWs carve_transmil_bwd(const rrt_transmil_desc* d, int64_t N, char* base) {
-  TransmilBwdWs ws{};
-  const int side = ceil_sqrt_i64(N);
-  const int64_t rows = 1 + (int64_t)side * side;
-  const size_t D = (size_t)d->attn.dim, RD = (size_t)rows * D;
-  Arena a{base};
-  ws.dgb = a.take(2 * D);
-  ws.d_hrow = a.take(D);
-  ws.d_yrow = a.take(D);
-  ws.d_orow = a.take((size_t)d->attn.heads * 64);
-  ws.A = a.take(RD);
-  ws.B = a.take(RD);
-  ws.C = a.take(RD);
-  ws.nys = a.take<char>(carve_nystrom_bwd(&d->attn, rows, nullptr).bytes);
-  ws.lnp = a.take<char>(ln_bwd_workspace((int)D));
-  ws.ppeg = a.take<char>(ppeg_side_bwd_workspace(side, (int)D));
-  ws.lin = a.take<char>(linear_bwd_workspace((int)N, (int)D, d->input_dim));
-  ws.bytes = a.bytes();
-  return ws;
-}
-
-bool transmil_grads_ok(const rrt_transmil_desc* desc, const rrt_transmil_grads* g) {
-  if (!g->fc1_w || !g->fc1_b || !g->cls_token || !g->norm_w || !g->norm_b || !g->fc2_w || !g->fc2_b) return false;
-  for (int i = 0; i < 3; ++i)
-    if (!g->pos_w[i] || !g->pos_b[i]) return false;
-  for (int i = 0; i < 2; ++i) {
-    const rrt_transmil_layer_grads& l = g->layer[i];
-    if (!l.norm_w || !l.norm_b || !l.attn.qkv_w || !l.attn.out_w || !l.attn.out_b || (desc->attn.residual && !l.attn.conv_w))
-      return false;
-  }
-  return true;
-}
-
-// arguments of both calls that are checked the same way; fills the two mask configurations
-int check_transmil_step(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, int64_t n_tokens, float fc1_drop_p,
-                        float attn_drop_p, DropCfg* d1, DropCfg* da) {
-  int rc = check_transmil(desc, n_tokens);
-  if (rc) return rc;
-  if (!transmil_weights_ok(desc, w) || !w->fc1_b || !w->fc2_b || !w->pos_b[0] || !w->pos_b[1] || !w->pos_b[2]) return RRT_E_INVALID;
-  if (make_drop(fc1_drop_p, d1) || make_drop(attn_drop_p, da)) return RRT_E_INVALID;
-  return RRT_OK;
-}
-
-int transmil_forward_train(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, const float* x, float* logits,
-                           int64_t N, const TransmilStash& S, const DropCfg& d1, const DropCfg& da, uint64_t seed, bool tail,
-                           hipStream_t st) {
-  const rrt_nystrom_desc* ad = &desc->attn;
-  const NystromStash s1 = carve_nystrom_stash(ad, S.rows, S.nys1), s2 = carve_nystrom_stash(ad, S.rows, S.nys2, !tail);
-  const int D = ad->dim, R = (int)S.rows, hd = ad->heads * 64;
-  int rc;
-  // _fc1: Linear (+ activation as a pass over the kept pre-activation) + Dropout
-  LinearEpilogue ep{};
-  ep.bias = w->fc1_b;
-  if (desc->act != RRT_ACT_NONE) {
-    RRT_TRY(launch_linear(x, w->fc1_w, S.hpre, (int)N, D, desc->input_dim, ep, st));
-    RRT_TRY(launch_act_forward(S.hpre, S.emb, (size_t)N * D, desc->act, d1.thresh, d1.seed(seed, DROP_TAG_FC1), d1.scale, st));
-  } else {
-    RRT_TRY(launch_linear(x, w->fc1_w, S.emb, (int)N, D, desc->input_dim, ep, st));
-    RRT_TRY(launch_apply_drop_mask(S.emb, (int)N, D, d1.thresh, d1.seed(seed, DROP_TAG_FC1), d1.scale, st));
-  }
-  RRT_TRY(launch_transmil_assemble(S.emb, w->cls_token, S.seq0, (int)N, R, D, st));
-  // layer 1: seq1 = seq0 + drop(Nystrom(LN(seq0)))
-  RRT_TRY(launch_layernorm(S.seq0, nullptr, w->layer[0].norm_w, w->layer[0].norm_b, S.ln1, R, D, st));
-  rc = nystrom_forward(ad, &w->layer[0].attn, S.ln1, S.seq1, S.rows, s1.f, st, s1.lse);
-  if (rc) return rc;
-  RRT_TRY(launch_apply_drop_mask(S.seq1, R, D, da.thresh, da.seed(seed, DROP_TAG_ATTN1), da.scale, st));
-  RRT_TRY(launch_add_cols(S.seq1, S.seq0, (size_t)R, D, D, st));
-  // PPEG: row 0 passes through
-  RRT_TRY(hipMemcpyAsync(S.seq2, S.seq1, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, st));
-  RRT_TRY(launch_ppeg_side(S.seq1 + D, w->pos_w, w->pos_b, S.seq2 + D, S.side, D, st));
-  // layer 2: only row 0 of seq2 + drop(Nystrom(LN(seq2))) is read
-  RRT_TRY(launch_layernorm(S.seq2, nullptr, w->layer[1].norm_w, w->layer[1].norm_b, S.ln2, R, D, st));
-  const float* yrow = S.yrow;
-  if (tail) {
-    rc = nystrom_front(ad, &w->layer[1].attn, S.ln2, S.rows, s2.f, st, s2.lse);
-    if (rc) return rc;
-    RRT_TRY(launch_nystrom_output_row(s2.f.qkv, s2.f.kl, s2.f.wz, ad->residual ? w->layer[1].attn.conv_w : nullptr, S.orow,
-                                      (long)(s2.f.np - S.rows), (long)s2.f.np, ad->heads, ad->residual_conv_kernel, st));
-    RRT_TRY(launch_row_linear(S.orow, w->layer[1].attn.out_w, w->layer[1].attn.out_b, S.yrow, D, hd, st));
-  } else {
-    rc = nystrom_forward(ad, &w->layer[1].attn, S.ln2, S.att2, S.rows, s2.f, st, s2.lse);
-    if (rc) return rc;
-    yrow = S.att2;
-  }
-  // mask + residual on row 0, the last LayerNorm, _fc2
-  RRT_TRY(launch_transmil_row_head(S.seq2, yrow, w->norm_w, w->norm_b, w->fc2_w, w->fc2_b, S.hrow, S.stats, logits, D,
-                                   desc->n_classes, da.thresh, da.seed(seed, DROP_TAG_ATTN2), da.scale, st));
-  return RRT_OK;
-}
-
-int transmil_backward(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, const float* x, const float* d_logits,
-                      const TransmilStash& S, const TransmilBwdWs& W, const rrt_transmil_grads* g, float* dx, int64_t N,
-                      const DropCfg& d1, const DropCfg& da, uint64_t seed, bool tail, hipStream_t st) {
-  const rrt_nystrom_desc* ad = &desc->attn;
-  const NystromStash s1 = carve_nystrom_stash(ad, S.rows, S.nys1), s2 = carve_nystrom_stash(ad, S.rows, S.nys2, !tail);
-  const NystromBwdWs nb = carve_nystrom_bwd(ad, S.rows, W.nys);
-  const int D = ad->dim, R = (int)S.rows, hd = ad->heads * 64;
-  const size_t row_bytes = (size_t)D * sizeof(float);
-  int rc;
-  // the head: _fc2, the last LayerNorm, and the one nonzero row of layer 2's output cotangent
-  RRT_TRY(launch_transmil_row_head_backward(d_logits, S.hrow, S.stats, w->norm_w, w->norm_b, w->fc2_w, g->fc2_w, g->fc2_b,
-                                            g->norm_w, g->norm_b, W.d_hrow, W.d_yrow, D, desc->n_classes, da.thresh,
-                                            da.seed(seed, DROP_TAG_ATTN2), da.scale, st));
-  // layer 2's attention -> A = d ln2
-  const rrt_nystrom_grads* g2 = &g->layer[1].attn;
-  if (tail) {
-    RRT_TRY(launch_row_linear_backward(W.d_yrow, S.orow, w->layer[1].attn.out_w, g2->out_w, g2->out_b, W.d_orow, D, hd, st));
-    RRT_TRY(launch_nystrom_output_row_backward(s2.f.qkv, s2.f.kl, s2.f.wz, ad->residual ? w->layer[1].attn.conv_w : nullptr,
-                                               W.d_orow, nb.d_qkv, nb.d_kl, nb.d_wz, g2->conv_w, (long)(s2.f.np - S.rows),
-                                               (long)s2.f.np, ad->heads, ad->residual_conv_kernel, st));
-    rc = nystrom_backward_rest(ad, &w->layer[1].attn, S.ln2, s2, nb, g2, W.A, S.rows, st);
-  } else {
-    RRT_TRY(hipMemsetAsync(W.C, 0, (size_t)R * row_bytes, st));
-    RRT_TRY(hipMemcpyAsync(W.C, W.d_yrow, row_bytes, hipMemcpyDeviceToDevice, st));
-    rc = nystrom_backward(ad, &w->layer[1].attn, S.ln2, W.C, s2, nb, g2, W.A, S.rows, st);
-  }
-  if (rc) return rc;
-  // LayerNorm 2 -> B = d seq2; the residual reaches row 0 alone
-  RRT_TRY(launch_ln_backward(W.A, S.seq2, w->layer[1].norm_w, nullptr, W.B, W.dgb, (float*)W.lnp, R, D, nullptr, st));
-  RRT_TRY(hipMemcpyAsync(g->layer[1].norm_w, W.dgb, row_bytes, hipMemcpyDeviceToDevice, st));
-  RRT_TRY(hipMemcpyAsync(g->layer[1].norm_b, W.dgb + D, row_bytes, hipMemcpyDeviceToDevice, st));
-  RRT_TRY(launch_add_cols(W.B, W.d_hrow, 1, D, D, st));
-  // PPEG -> A = d seq1 (row 0 passes through)
-  RRT_TRY(hipMemcpyAsync(W.A, W.B, row_bytes, hipMemcpyDeviceToDevice, st));
-  RRT_TRY(launch_ppeg_side_backward(S.seq1 + D, W.B + D, w->pos_w, W.A + D, g->pos_w, g->pos_b, S.side, D, W.ppeg, st));
-  // layer 1: the attention branch under its mask -> B = d ln1; LayerNorm 1 with the residual branch -> C = d seq0
-  const float* dy1 = W.A;
-  if (da.thresh) {
-    RRT_TRY(launch_copy_drop_mask(W.A, W.C, (size_t)R * D, da.thresh, da.seed(seed, DROP_TAG_ATTN1), da.scale, st));
-    dy1 = W.C;
-  }
-  rc = nystrom_backward(ad, &w->layer[0].attn, S.ln1, dy1, s1, nb, &g->layer[0].attn, W.B, S.rows, st);
-  if (rc) return rc;
-  RRT_TRY(launch_ln_backward(W.B, S.seq0, w->layer[0].norm_w, W.A, W.C, W.dgb, (float*)W.lnp, R, D, nullptr, st));
-  RRT_TRY(hipMemcpyAsync(g->layer[0].norm_w, W.dgb, row_bytes, hipMemcpyDeviceToDevice, st));
-  RRT_TRY(hipMemcpyAsync(g->layer[0].norm_b, W.dgb + D, row_bytes, hipMemcpyDeviceToDevice, st));
-  // the assembly, _fc1's mask and activation -> A = d (_fc1.0's output); then _fc1.0 (dx == NULL: no dX product)
-  RRT_TRY(launch_transmil_assemble_backward(W.C, S.hpre, W.A, g->cls_token, (int)N, S.side, D, desc->act, d1.thresh,
-                                            d1.seed(seed, DROP_TAG_FC1), d1.scale, st));
-  RRT_TRY(launch_linear_backward(W.A, x, w->fc1_w, dx, g->fc1_w, g->fc1_b, (int)N, D, desc->input_dim, RRT_COMPUTE_F32, W.lin,
-                                 st));
-  return RRT_OK;
-}
-
-int transmil_train_sizes(const rrt_transmil_desc* desc, int64_t n_tokens, size_t* stash_bytes, size_t* bwd_bytes, bool tail) {
-  if (!stash_bytes || !bwd_bytes) return RRT_E_INVALID;
-  int rc = check_transmil(desc, n_tokens);
-  if (rc) return rc;
-  *stash_bytes = carve_transmil_stash(desc, n_tokens, nullptr, tail).bytes;
-  *bwd_bytes = carve_transmil_bwd(desc, n_tokens, nullptr).bytes;
-  return RRT_OK;
-}
-
-int transmil_forward_train_entry(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, const float* x, float* logits,
-                                 int64_t n_tokens, void* stash, size_t stash_bytes, float fc1_drop_p, float attn_drop_p,
-                                 uint64_t drop_seed, void* stream, bool tail) {
-  if (!desc || !w || !x || !logits) return RRT_E_INVALID;
-  DropCfg d1{}, da{};
-  int rc = check_transmil_step(desc, w, n_tokens, fc1_drop_p, attn_drop_p, &d1, &da);
-  if (rc) return rc;
-  if (!stash || stash_bytes < carve_transmil_stash(desc, n_tokens, nullptr, tail).bytes) return RRT_E_WORKSPACE;
-  return transmil_forward_train(desc, w, x, logits, n_tokens, carve_transmil_stash(desc, n_tokens, (char*)stash, tail), d1, da,
-                                drop_seed, tail, (hipStream_t)stream);
-}
-
-int transmil_backward_entry(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, const float* x, const float* d_logits,
-                            const void* stash, size_t stash_bytes, const rrt_transmil_grads* grads, float* dx, int64_t n_tokens,
-                            void* workspace, size_t workspace_bytes, float fc1_drop_p, float attn_drop_p, uint64_t drop_seed,
-                            void* stream, bool tail) {
-  if (!desc || !w || !x || !d_logits || !grads) return RRT_E_INVALID;
-  DropCfg d1{}, da{};
-  int rc = check_transmil_step(desc, w, n_tokens, fc1_drop_p, attn_drop_p, &d1, &da);
-  if (rc) return rc;
-  if (!transmil_grads_ok(desc, grads)) return RRT_E_INVALID;
-  if (!stash || stash_bytes < carve_transmil_stash(desc, n_tokens, nullptr, tail).bytes) return RRT_E_WORKSPACE;
-  if (!workspace || workspace_bytes < carve_transmil_bwd(desc, n_tokens, nullptr).bytes) return RRT_E_WORKSPACE;
-  return transmil_backward(desc, w, x, d_logits, carve_transmil_stash(desc, n_tokens, (char*)stash, tail),
-                           carve_transmil_bwd(desc, n_tokens, (char*)workspace), grads, dx, n_tokens, d1, da, drop_seed, tail,
-                           (hipStream_t)stream);
-}
-
-int check_output_row(int64_t row, int64_t np, int32_t heads, const float* conv_w, int32_t conv_k) {
-  int rc = check_np_heads(np, heads);
-  if (rc) return rc;
-  if (row < 0 || row >= np) return unsupported("nystrom: row must be in [0, n_padded)");
-  if (conv_w && (conv_k < 1 || conv_k % 2 == 0 || conv_k > 63)) return unsupported("nystrom: residual_conv_kernel must be odd and <= 63");
-  return RRT_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int rrt_transmil_train_sizes(const rrt_transmil_desc* desc, int64_t n_tokens, size_t* stash_bytes, size_t* backward_workspace_bytes) {
-  return transmil_train_sizes(desc, n_tokens, stash_bytes, backward_workspace_bytes, false);
-}
-
-int rrt_transmil_forward_train_f32(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, const float* x, float* logits,
-                                   int64_t n_tokens, void* stash, size_t stash_bytes, float fc1_drop_p, float attn_drop_p,
-                                   uint64_t drop_seed, void* stream) {
-  return transmil_forward_train_entry(desc, w, x, logits, n_tokens, stash, stash_bytes, fc1_drop_p, attn_drop_p, drop_seed, stream,
-                                      false);
-}
-
-int rrt_transmil_backward_f32(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, const float* x, const float* d_logits,
-                              const void* stash, size_t stash_bytes, const rrt_transmil_grads* grads, float* dx, int64_t n_tokens,
-                              void* workspace, size_t workspace_bytes, float fc1_drop_p, float attn_drop_p, uint64_t drop_seed,
-                              void* stream) {
-  return transmil_backward_entry(desc, w, x, d_logits, stash, stash_bytes, grads, dx, n_tokens, workspace, workspace_bytes,
-                                 fc1_drop_p, attn_drop_p, drop_seed, stream, false);
-}
-
-int rrt_debug_transmil_train_sizes_row(const rrt_transmil_desc* desc, int64_t n_tokens, size_t* stash_bytes,
-                                        size_t* backward_workspace_bytes) {
-  return transmil_train_sizes(desc, n_tokens, stash_bytes, backward_workspace_bytes, true);
-}
-
-int rrt_debug_transmil_forward_train_row_f32(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, const float* x,
-                                              float* logits, int64_t n_tokens, void* stash, size_t stash_bytes, float fc1_drop_p,
-                                              float attn_drop_p, uint64_t drop_seed, void* stream) {
-  return transmil_forward_train_entry(desc, w, x, logits, n_tokens, stash, stash_bytes, fc1_drop_p, attn_drop_p, drop_seed, stream,
-                                      true);
-}
-
-int rrt_debug_transmil_backward_row_f32(const rrt_transmil_desc* desc, const rrt_transmil_weights* w, const float* x,
-                                         const float* d_logits, const void* stash, size_t stash_bytes,
-                                         const rrt_transmil_grads* grads, float* dx, int64_t n_tokens, void* workspace,
-                                         size_t workspace_bytes, float fc1_drop_p, float attn_drop_p, uint64_t drop_seed,
-                                         void* stream) {
-  return transmil_backward_entry(desc, w, x, d_logits, stash, stash_bytes, grads, dx, n_tokens, workspace, workspace_bytes,
-                                 fc1_drop_p, attn_drop_p, drop_seed, stream, true);
-}
-
-int rrt_ppeg_side_backward_workspace_size(int32_t side, int32_t dim, size_t* bytes) {
-  if (!bytes || side <= 0 || dim <= 0) return RRT_E_INVALID;
-  if (dim % 4) return unsupported("ppeg: dim must be a multiple of 4");
-  if (side > 1000) return unsupported("ppeg: side above 1000");
-  *bytes = ppeg_side_bwd_workspace(side, dim);
-  return RRT_OK;
-}
-
-int rrt_ppeg_side_backward_f32(const float* x, const float* dy, const float* const* w, float* dx, float* const* dw,
-                               float* const* db, int32_t side, int32_t dim, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!x || !dy || !dx || !w || !w[0] || !w[1] || !w[2] || !dw || !dw[0] || !dw[1] || !dw[2] || side <= 0 || dim <= 0)
-    return RRT_E_INVALID;
-  if (dim % 4) return unsupported("ppeg: dim must be a multiple of 4");
-  if (side > 1000) return unsupported("ppeg: side above 1000");
-  if (!workspace || workspace_bytes < ppeg_side_bwd_workspace(side, dim)) return RRT_E_WORKSPACE;
-  float* const nob[3] = {nullptr, nullptr, nullptr};
-  return (int)launch_ppeg_side_backward(x, dy, w, dx, dw, db ? db : nob, side, dim, workspace, (hipStream_t)stream);
-}
-
-int rrt_transmil_assemble_backward_f32(const float* d_seq, const float* hpre, float* d_emb, float* d_cls, int64_t n_tokens,
-                                       int32_t dim, int32_t act, float drop_p, uint64_t drop_seed, void* stream) {
-  if (!d_seq || !d_emb || !d_cls || n_tokens <= 0 || dim <= 0) return RRT_E_INVALID;
-  if (n_tokens > 998001) return unsupported("transmil: n_tokens above 998001");
-  if (dim % 4) return unsupported("transmil: dim must be a multiple of 4");
-  if (act != RRT_ACT_NONE && act != RRT_ACT_RELU && act != RRT_ACT_GELU) return unsupported("transmil: act must be none/relu/gelu");
-  if (act != RRT_ACT_NONE && !hpre) return RRT_E_INVALID;
-  DropCfg dc{};
-  if (make_drop(drop_p, &dc)) return RRT_E_INVALID;
-  return (int)launch_transmil_assemble_backward(d_seq, hpre, d_emb, d_cls, (int)n_tokens, ceil_sqrt_i64(n_tokens), dim, act,
-                                                dc.thresh, dc.seed(drop_seed, DROP_TAG_FC1), dc.scale, (hipStream_t)stream);
-}
-
-int rrt_nystrom_output_row_f32(const float* qkv, const float* kl, const float* wz, const float* conv_w, float* o_row, int64_t row,
-                               int64_t n_padded, int32_t heads, int32_t conv_k, void* stream) {
-  if (!qkv || !kl || !wz || !o_row) return RRT_E_INVALID;
-  int rc = check_output_row(row, n_padded, heads, conv_w, conv_k);
-  if (rc) return rc;
-  return (int)launch_nystrom_output_row(qkv, kl, wz, conv_w, o_row, (long)row, (long)n_padded, heads, conv_k, (hipStream_t)stream);
-}
-
-int rrt_nystrom_output_row_backward_f32(const float* qkv, const float* kl, const float* wz, const float* conv_w,
-                                        const float* d_o_row, float* d_qkv, float* d_kl, float* d_wz, float* d_conv_w, int64_t row,
-                                        int64_t n_padded, int32_t heads, int32_t conv_k, void* stream) {
-  if (!qkv || !kl || !wz || !d_o_row || !d_qkv || !d_kl || !d_wz || (conv_w && !d_conv_w)) return RRT_E_INVALID;
-  int rc = check_output_row(row, n_padded, heads, conv_w, conv_k);
-  if (rc) return rc;
-  return (int)launch_nystrom_output_row_backward(qkv, kl, wz, conv_w, d_o_row, d_qkv, d_kl, d_wz, d_conv_w, (long)row,
-                                                 (long)n_padded, heads, conv_k, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,0 +1,44 @@
+// api_internal.h -- what the host-only units behind include/rrt_hip.h (api.hip, api_nystrom.hip) share: the workspace bump
+// allocator, the HIP-error early return, and the declarations of the helpers of api.hip that api_nystrom.hip calls.  Each is
+// defined once; everything else of a unit stays in that unit's anonymous namespace.
+#pragma once
+#include "internal.h"
+
+// a failed launch (or any other HIP call) ends the entry point with the HIP error as its return code
+#define RRT_TRY(call)                     \
+  do {                                    \
+    const hipError_t e_ = (call);         \
+    if (e_ != hipSuccess) return (int)e_; \
+  } while (0)
+
+namespace rrt_api {
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// The one bump allocator behind every workspace carve.  A carve function states its layout once, as a sequence of take()s,
+// and serves both the size query (base = null: every pointer is null, only bytes() counts) and the real carve, so a size can
+// never disagree with the pointers handed out.  Every piece starts on a 256-byte boundary.
+struct Arena {
+  char* base;
+  size_t off = 0;
+  template <typename T = float>
+  T* take(size_t count) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off = align_up(off + count * sizeof(T), 256);
+    return p;
+  }
+  size_t bytes() const { return off; }
+};
+
+// RRT_E_UNSUPPORTED with `why` as the calling thread's detail string, which rrt_strerror reports (defined in api.hip, beside
+// the string itself)
+int unsupported(const char* why);
+
+// dropout of one training call -- keep threshold and rescale; seed(): one layer's mask word (tests/hip_util.py)
+struct DropCfg {
+  unsigned thresh;
+  float scale;
+  unsigned seed(uint64_t base, int layer) const { return (unsigned)(base ^ (base >> 32)) + 0x9E3779B9u * (unsigned)(layer + 1); }
+};
+// fills it from a probability; RRT_E_INVALID outside [0, 1) (defined in api.hip, beside unsupported)
+int make_drop(float p, DropCfg* d);
+}  // namespace rrt_api

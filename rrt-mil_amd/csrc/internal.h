@@ -1,4 +1,4 @@
-// internal.h -- host-side launch functions shared between the kernel files and api.cpp
+// internal.h -- host-side launch functions shared between the kernel files and the C ABI units (api*.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "common.h"
@@ -88,7 +88,14 @@ struct Cast16Jobs {
   uint16_t* dst[CAST16_MAX_JOBS];
   size_t n4[CAST16_MAX_JOBS];       // float4 groups (element count / 4)
   int count;
+  // host side: append one job of n_elems floats (the caller keeps count < CAST16_MAX_JOBS)
+  void add(const float* s, uint16_t* d, size_t n_elems) {
+    src[count] = s;
+    dst[count] = d;
+    n4[count++] = n_elems / 4;
+  }
 };
+static_assert(sizeof(Cast16Jobs) == 440, "Cast16Jobs is a kernel argument: three 18-entry tables of 8 bytes and the count");
 hipError_t launch_cast16(const Cast16Jobs& jobs, int prec, hipStream_t st);
 hipError_t launch_ln_partition16(const float* x, const float* gamma, const float* beta, uint16_t* u, int dim,
                                  const GridDev& g, int prec, hipStream_t st, int* zero = nullptr, int n_zero = 0);

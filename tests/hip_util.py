@@ -109,7 +109,7 @@ def region_attention_backward_guarded(qkv, pe_w, o, dO, n_regions, P, dim, heads
 def dropout_keep(seed, layer, rows, cols, p):
     """numpy replica of csrc/common.h::rrt_drop_keep for one layer's proj output [rows, cols]: the boolean keep
     mask that rrt_encoder_forward_train_f32 applies for (drop_p = p, drop_seed = seed); layer = index of the R-MSA
-    layer, 100 for CR-MSA's inner attention (api.hip DropCfg::seed)."""
+    layer, 100 for CR-MSA's inner attention (api_internal.h DropCfg::seed)."""
     M32 = np.uint64(0xFFFFFFFF)
     base = np.uint64(seed)
     lseed = ((base ^ (base >> np.uint64(32))) + np.uint64(0x9E3779B9) * np.uint64(layer + 1)) & M32

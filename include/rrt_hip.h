@@ -968,6 +968,52 @@ int rrt_nystrom_zav_f32(const float *z, const float *av, float *wz, int32_t head
 int rrt_nystrom_output_f32(const float *qkv, const float *kl, const float *wz, const float *conv_w, float *o,
                            int64_t n_padded, int32_t heads, int32_t conv_k, void *stream);
 
+/* ---- Batched Nystrom attention (exports added under ABI 29; nothing above changes).  b sequences of n tokens each in ONE launch
+ * per stage -- no host loop over b.  Every layout above gains a leading b: qkv [b, np, 3 * heads * 64] (each item's np - n zero
+ * rows in FRONT of that item), ql / kl / av / wz [b, heads, 256, 64], a2 / z [b, heads, 256, 256], o [b, np, heads * 64].  The
+ * conv runs along each item's own padded sequence.  The pseudo-inverse's initial scale is ONE scalar, max row abs sum * max
+ * column abs sum over all b * heads matrices of a2 (the reference's torch.max over the whole batch), reduced without atomics in
+ * a fixed order.  Envelope: the single-sequence one plus 1 <= b <= 4096.  Two calls give the same bits, and with b = 1 every
+ * entry gives the bits of its single-sequence counterpart.
+ * attention_batched: x [b, n, dim] -> y [b, n, dim]. */
+int rrt_nystrom_batched_workspace_size(const rrt_nystrom_desc *desc, int64_t b, int64_t n, size_t *bytes);
+int rrt_nystrom_attention_batched_f32(const rrt_nystrom_desc *desc, const rrt_nystrom_weights *w, const float *x, float *y,
+                                      int64_t b, int64_t n, void *workspace, size_t workspace_bytes, void *stream);
+int rrt_nystrom_landmarks_batched_f32(const float *qkv, float *ql, float *kl, int64_t b, int64_t n_padded, int32_t heads,
+                                      void *stream);
+int rrt_nystrom_landmark_sim_batched_f32(const float *ql, const float *kl, float *a2, int64_t b, int32_t heads, void *stream);
+int rrt_nystrom_landmark_attn_batched_workspace_size(int64_t b, int64_t n_padded, int32_t heads, size_t *bytes);
+int rrt_nystrom_landmark_attn_batched_f32(const float *qkv, const float *ql, float *av, int64_t b, int64_t n_padded,
+                                          int32_t heads, void *workspace, size_t workspace_bytes, void *stream);
+int rrt_nystrom_pinv_batched_workspace_size(int64_t b, int32_t heads, size_t *bytes);
+int rrt_nystrom_pinv_batched_f32(const float *a2, float *z, int64_t b, int32_t heads, int32_t iterations, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int rrt_nystrom_zav_batched_f32(const float *z, const float *av, float *wz, int64_t b, int32_t heads, void *stream);
+int rrt_nystrom_output_batched_f32(const float *qkv, const float *kl, const float *wz, const float *conv_w, float *o, int64_t b,
+                                   int64_t n_padded, int32_t heads, int32_t conv_k, void *stream);
+
+/* ---- The reference's Nystrom ablations of RRTEncoder (modules/rrt.py:49-58 `--attn ntrans`, modules/rmsa.py:167-173
+ * `--region_attn ntrans`; exports added under ABI 29).  One call per bag, inference, exact fp32 (desc->compute other than
+ * RRT_COMPUTE_F32 is RRT_E_UNSUPPORTED).  rrt_encoder_desc describes everything but the n_rmsa_layers attention layers, whose
+ * parameters ride in the rrt_attn_weights slots: norm_* the TransLayer's LayerNorm, qkv_w = to_qkv.weight (qkv_b NULL),
+ * proj_w / proj_b = to_out.0.*, pe_w = res_conv.weight [heads, k], norm2 / fc* the optional FFN.  nys->attn.dim must be
+ * desc->dim and attn.heads * attn.dim_head == dim; the epeg* fields are ignored.
+ *  RRT_NYSTROM_BAG     : each layer is x + NystromAttention(LN(x)) over the whole bag (b = 1);
+ *  RRT_NYSTROM_REGIONS : LN(x), zero rows appended to H * H, partitioned by rrt_region_grid into R regions of P tokens, the
+ *                        batched attention with b = R, n = P (ONE pseudo-inverse scale over all regions and heads),
+ *                        un-partitioned, the appended rows dropped, + x.
+ * PEG / PPEG, CR-MSA, all_shortcut and the final LayerNorm are those of rrt_encoder_forward_f32. */
+enum { RRT_NYSTROM_BAG = 1, RRT_NYSTROM_REGIONS = 2 };
+typedef struct rrt_encoder_nystrom_desc {
+  int32_t mode;
+  rrt_nystrom_desc attn;
+} rrt_encoder_nystrom_desc;
+int rrt_encoder_nystrom_workspace_size(const rrt_encoder_desc *desc, const rrt_encoder_nystrom_desc *nys, int64_t n_tokens,
+                                       size_t *bytes);
+int rrt_encoder_nystrom_forward_f32(const rrt_encoder_desc *desc, const rrt_encoder_nystrom_desc *nys,
+                                    const rrt_encoder_weights *w, const float *x, float *y, int64_t n_tokens, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+
 /* ---- Nystrom attention, training (exports added under ABI 29, no existing struct or signature touched).  Exact fp32 on the
  * fp32 matrix cores, no atomics: two runs give the same bits.  The same envelope as the forward above.
  *

@@ -198,6 +198,18 @@ class _BagMean(torch.autograd.Function):
         return dy, dw, db
 
 
+def copy_encoder_desc(dst, enc, who):
+    """The ONE place a head copies its encoder's descriptor into its own (RRTMIL, CLAM, DSMIL and the BagHead family): the
+    one-call head kernels run the plain R-MSA layers, so an encoder built with attn='ntrans' / region_attn='ntrans' -- whose
+    layers hold NystromAttention parameters in other slots -- must never reach them."""
+    if getattr(enc, "_nys_mode", 0):
+        raise NotImplementedError(f"rrt_mil_amd.{who}: the one-call head entries (forward_bag, forward_bags) run the R-MSA "
+                                  "kernels and do not cover an RRTEncoder with attn='ntrans' / region_attn='ntrans' "
+                                  "(NystromAttention layers); call the encoder itself in eval() under torch.no_grad() "
+                                  "(RRTMIL: the module call)")
+    C.memmove(C.byref(dst), C.byref(enc._desc), C.sizeof(_lib.EncoderDesc))
+
+
 class BagHead(HeadState):
     """What the reference's plain MIL heads share (modules/attmil.py, attmil_ibmil.py, mean_max.py): a front -- embedding
     Linear + activation (+ Dropout) (+ ``rrt``) -- and a pool-specific tail.  In ``eval()`` without a graph a bag is ONE
@@ -255,7 +267,7 @@ class BagHead(HeadState):
         enc, p = self._enc(), RRTEncoder._ptr
         d, w = _lib.BagmilDesc(), _lib.BagmilWeights()
         if enc is not None:
-            C.memmove(C.byref(d.enc), C.byref(enc._desc), C.sizeof(_lib.EncoderDesc))
+            copy_encoder_desc(d.enc, enc, self._NAME)
             w.enc = enc._weights()
         d.enc.dim = 512
         d.enc.compute = self._compute()

@@ -105,6 +105,13 @@ class NystromDesc(C.Structure):
                                          "residual_conv_kernel")]
 
 
+NYSTROM_BAG, NYSTROM_REGIONS = 1, 2      # rrt_encoder_nystrom_desc.mode
+
+
+class EncoderNystromDesc(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("attn", NystromDesc)]
+
+
 class NystromWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("qkv_w", "out_w", "out_b", "conv_w")]
 
@@ -357,6 +364,25 @@ SIGNATURES = {
                                                                         C.c_void_p]),
     "rrt_nystrom_output_row_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "rrt_nystrom_output_row_backward_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    # b sequences per launch (every stage entry with b in front of the sizes) and the encoder's Nystrom ablations
+    "rrt_nystrom_batched_workspace_size": (C.c_int, [C.POINTER(NystromDesc), C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_attention_batched_f32": (C.c_int, [C.POINTER(NystromDesc), C.POINTER(NystromWeights), C.c_void_p, C.c_void_p,
+                                                    C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_nystrom_landmarks_batched_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
+    "rrt_nystrom_landmark_sim_batched_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_void_p]),
+    "rrt_nystrom_landmark_attn_batched_workspace_size": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_landmark_attn_batched_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t,
+                                                                           C.c_void_p]),
+    "rrt_nystrom_pinv_batched_workspace_size": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_pinv_batched_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                                                  C.c_void_p]),
+    "rrt_nystrom_zav_batched_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_void_p]),
+    "rrt_nystrom_output_batched_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "rrt_encoder_nystrom_workspace_size": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderNystromDesc), C.c_int64,
+                                                     C.POINTER(C.c_size_t)]),
+    "rrt_encoder_nystrom_forward_f32": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderNystromDesc),
+                                                  C.POINTER(EncoderWeights), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                  C.c_size_t, C.c_void_p]),
 }
 
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32X3 = 0, 1, 2, 3

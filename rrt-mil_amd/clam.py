@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from ._head import HeadState, head_compute
+from ._head import HeadState, copy_encoder_desc, head_compute
 from .encoder import RRTEncoder
 from .mil import lib_linear
 
@@ -271,7 +271,7 @@ class CLAM_SB(HeadState, nn.Module):
         enc, p = self.rrt, RRTEncoder._ptr
         d, w = _lib.ClamDesc(), _lib.ClamWeights()
         if enc is not None:
-            C.memmove(C.byref(d.enc), C.byref(enc._desc), C.sizeof(_lib.EncoderDesc))
+            copy_encoder_desc(d.enc, enc, "CLAM")
             w.enc = enc._weights()
         d.enc.dim = 512
         d.enc.compute = self._compute()

@@ -502,7 +502,9 @@ static int ffn_apply(const rrt_encoder_desc* desc, const rrt_attn_weights& lw, c
 static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_weights* w, const float* x,
                            float* y, int64_t n_tokens, void* workspace, size_t workspace_bytes,
                            void* stream, void** events, rrt_phase_gate* gate = nullptr, float* rmsa_out = nullptr,
-                           uint16_t* y16 = nullptr, bool* y16_done = nullptr, int rows_w_forced = -1) {
+                           uint16_t* y16 = nullptr, bool* y16_done = nullptr, int rows_w_forced = -1,
+                           const float* shortcut = nullptr) {
+  // shortcut (rrt_api::encoder_tail): what all_shortcut adds, when it is not this call's x
   // rows_w_forced >= 0 (rrt_debug_encoder_forward_rows_f32): the width of the row-looping K1 / K7 instead of the plan's
   // y16 / y16_done (the slide classifier, 16-bit modes): where the forward's last kernel is CR-MSA's dispatch + LayerNorm it
   // also leaves the output rows as 16-bit values there and sets the flag
@@ -743,7 +745,7 @@ static int encoder_forward(const rrt_encoder_desc* desc_in, const rrt_encoder_we
     if (xin != rmsa_out) RRT_TRY(hipMemcpyAsync(rmsa_out, xin, (size_t)N * D * sizeof(float), hipMemcpyDeviceToDevice, st));
     return RRT_OK;
   }
-  const float* x0 = desc->all_shortcut ? x : nullptr;
+  const float* x0 = desc->all_shortcut ? (shortcut ? shortcut : x) : nullptr;
   if (!w->norm_w || !w->norm_b) return RRT_E_INVALID;
   if (!desc->cr_msa) {
     RRT_TRY(launch_layernorm(xin, x0, w->norm_w, w->norm_b, y, (int)N, D, st, plan.rows_w));
@@ -858,6 +860,31 @@ int rrt_debug_encoder_forward_rows_f32(const rrt_encoder_desc* desc, const rrt_e
                          rows_w);
 }
 
+}  // extern "C"
+
+// what api_nystrom.hip composes its encoder forward on (api_internal.h): the forward without attention layers and without
+// PEG / PPEG, on a copy of the descriptor
+namespace rrt_api {
+static rrt_encoder_desc tail_desc(const rrt_encoder_desc* desc) {
+  rrt_encoder_desc t = *desc;
+  t.n_rmsa_layers = 0;
+  t.pos = RRT_POS_NONE;
+  t.weights16_valid = 0;
+  return t;
+}
+int encoder_tail_workspace_size(const rrt_encoder_desc* desc, int64_t n_tokens, size_t* bytes) {
+  const rrt_encoder_desc t = tail_desc(desc);
+  return rrt_encoder_workspace_size(&t, n_tokens, bytes);
+}
+int encoder_tail(const rrt_encoder_desc* desc, const rrt_encoder_weights* w, const float* x1, const float* x0, float* y,
+                 int64_t n_tokens, void* workspace, size_t workspace_bytes, void* stream) {
+  const rrt_encoder_desc t = tail_desc(desc);
+  return encoder_forward(&t, w, x1, y, n_tokens, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, nullptr,
+                         -1, x0);
+}
+}  // namespace rrt_api
+
+extern "C" {
 int rrt_phase_gate_create(rrt_phase_gate** out) {
   if (!out) return RRT_E_INVALID;
   rrt_phase_gate* g = new rrt_phase_gate();

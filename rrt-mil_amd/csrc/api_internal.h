@@ -41,4 +41,11 @@ struct DropCfg {
 };
 // fills it from a probability; RRT_E_INVALID outside [0, 1) (defined in api.hip, beside unsupported)
 int make_drop(float p, DropCfg* d);
+
+// The part of an encoder forward behind its attention layers -- CR-MSA, all_shortcut, the final LayerNorm -- exactly as
+// rrt_encoder_forward_f32 runs it on a descriptor with n_rmsa_layers = 0 and pos = none: x1 [n_tokens, dim] the layers' result,
+// x0 what all_shortcut adds (the forward's original input), workspace of encoder_tail_workspace_size bytes (defined in api.hip)
+int encoder_tail_workspace_size(const rrt_encoder_desc* desc, int64_t n_tokens, size_t* bytes);
+int encoder_tail(const rrt_encoder_desc* desc, const rrt_encoder_weights* w, const float* x1, const float* x0, float* y,
+                 int64_t n_tokens, void* workspace, size_t workspace_bytes, void* stream);
 }  // namespace rrt_api

@@ -32,28 +32,40 @@ int check_nystrom(const rrt_nystrom_desc* d, int64_t n) {
   return RRT_OK;
 }
 
+int check_nystrom_batch(int64_t b) {
+  if (b < 1 || b > 4096) return unsupported("nystrom: batch b must be in 1..4096");
+  return RRT_OK;
+}
+
 struct NystromWs {
   float *qkv, *ql, *kl, *a2, *z, *av, *wz, *o, *lattn, *pinv;
-  int64_t np;
+  float *qkv_c, *o_c;      // b > 1 with front padding: the two linears' compact [b * n] rows (nystrom_batched_front)
+  int64_t np, b;
   size_t bytes;
 };
 // with_o = false: without o (the one-call TransMIL step's layer 2 needs one row of it, kept elsewhere)
-NystromWs carve_nystrom(const rrt_nystrom_desc* d, int64_t n, char* base, bool with_o = true) {
+// b sequences: every piece b times as large, in the same order (b = 1 is the single-sequence layout)
+NystromWs carve_nystrom(const rrt_nystrom_desc* d, int64_t n, char* base, bool with_o = true, int64_t b = 1) {
   NystromWs ws{};
   const int64_t np = (n + 255) / 256 * 256;
-  const size_t hd = (size_t)d->heads * 64, lm = (size_t)d->heads * 256 * 64, mm = (size_t)d->heads * 256 * 256;
+  const size_t hd = (size_t)d->heads * 64, lm = (size_t)b * d->heads * 256 * 64, mm = (size_t)b * d->heads * 256 * 256;
   Arena a{base};
   ws.np = np;
-  ws.qkv = a.take((size_t)np * 3 * hd);
+  ws.b = b;
+  ws.qkv = a.take((size_t)b * np * 3 * hd);
   ws.ql = a.take(lm);
   ws.kl = a.take(lm);
   ws.a2 = a.take(mm);
   ws.z = a.take(mm);
   ws.av = a.take(lm);
   ws.wz = a.take(lm);
-  if (with_o) ws.o = a.take((size_t)np * hd);
-  ws.lattn = a.take(nystrom_lattn_floats((long)np, d->heads));
-  ws.pinv = a.take(nystrom_pinv_floats(d->heads));
+  if (with_o) ws.o = a.take((size_t)b * np * hd);
+  ws.lattn = a.take(nystrom_lattn_floats((long)np, d->heads, (int)b));
+  ws.pinv = a.take(nystrom_pinv_floats(d->heads, (int)b));
+  if (b > 1 && np != n) {
+    ws.qkv_c = a.take((size_t)b * n * 3 * hd);
+    ws.o_c = a.take((size_t)b * n * hd);
+  }
   ws.bytes = a.bytes();
   return ws;
 }
@@ -93,6 +105,45 @@ int nystrom_forward(const rrt_nystrom_desc* d, const rrt_nystrom_weights* w, con
 
 bool nystrom_weights_ok(const rrt_nystrom_desc* d, const rrt_nystrom_weights* w) {
   return w->qkv_w && w->out_w && w->out_b && (!d->residual || w->conv_w);
+}
+
+// ---- b > 1 sequences of n tokens, x [b * n, dim] -> the attention output in front of to_out, o [b * n, heads * 64] COMPACT (the
+// returned pointer: ws.o itself when n is a multiple of 256).  One launch per stage.  The front-padded layout: to_qkv runs on the
+// b * n real rows alone (the pad rows are zero whatever the weights: no bias), and two strided copies move its rows behind each
+// item's zeroed pad rows and the output's real rows back -- a quarter more traffic than the attention's own, against up to
+// np / n times the flops of both linears on zero rows.
+int nystrom_batched_front(const rrt_nystrom_desc* d, const rrt_nystrom_weights* w, const float* x, int64_t n, const NystromWs& ws,
+                          hipStream_t st, const float** o_compact) {
+  const int hd = d->heads * 64, b = (int)ws.b;
+  const int64_t pad = ws.np - n;
+  const size_t row3 = (size_t)3 * hd * sizeof(float), row1 = (size_t)hd * sizeof(float);
+  LinearEpilogue ep{};
+  ep.q_cols = hd;
+  ep.q_scale = 0.125f;                       // dim_head^-0.5, dim_head = 64
+  RRT_TRY(launch_linear(x, w->qkv_w, pad ? ws.qkv_c : ws.qkv, (int)(b * n), 3 * hd, d->dim, ep, st));
+  if (pad) {
+    RRT_TRY(hipMemset2DAsync(ws.qkv, (size_t)ws.np * row3, 0, (size_t)pad * row3, (size_t)b, st));
+    RRT_TRY(hipMemcpy2DAsync(ws.qkv + (size_t)pad * 3 * hd, (size_t)ws.np * row3, ws.qkv_c, (size_t)n * row3, (size_t)n * row3,
+                             (size_t)b, hipMemcpyDeviceToDevice, st));
+  }
+  RRT_TRY(launch_nystrom_landmarks(ws.qkv, ws.ql, ws.kl, (long)ws.np, d->heads, st, b));
+  RRT_TRY(launch_nystrom_sim2(ws.ql, ws.kl, ws.a2, d->heads, st, b));
+  RRT_TRY(launch_nystrom_lattn(ws.qkv, ws.ql, ws.av, ws.lattn, (long)ws.np, d->heads, st, nullptr, b));
+  RRT_TRY(launch_nystrom_pinv(ws.a2, ws.z, ws.pinv, d->heads, d->pinv_iterations, st, b));
+  RRT_TRY(launch_nystrom_zav(ws.z, ws.av, ws.wz, d->heads, st, b));
+  RRT_TRY(launch_nystrom_output(ws.qkv, ws.kl, ws.wz, d->residual ? w->conv_w : nullptr, ws.o, (long)ws.np, d->heads,
+                                d->residual_conv_kernel, st, b));
+  if (pad)
+    RRT_TRY(hipMemcpy2DAsync(ws.o_c, (size_t)n * row1, ws.o + (size_t)pad * hd, (size_t)ws.np * row1, (size_t)n * row1, (size_t)b,
+                             hipMemcpyDeviceToDevice, st));
+  *o_compact = pad ? ws.o_c : ws.o;
+  return RRT_OK;
+}
+
+// the product b * n of a batched call stays within what one linear takes
+int check_nystrom_rows(int64_t b, int64_t n) {
+  if (b * n > 4000000) return unsupported("nystrom: b * n above 4e6");
+  return RRT_OK;
 }
 
 // what a query row of the attention matrix needs on top of a forward's workspace of `front` bytes: lse | r, [heads, 256] each
@@ -555,6 +606,150 @@ int transmil_backward_entry(const rrt_transmil_desc* desc, const rrt_transmil_we
                            carve_transmil_bwd(desc, n_tokens, (char*)workspace), grads, dx, n_tokens, d1, da, drop_seed, tail,
                            (hipStream_t)stream);
 }
+
+// ---- the Nystrom ablations of RRTEncoder (modules/rrt.py:49-58, modules/rmsa.py:167-230)
+int check_encoder_nystrom(const rrt_encoder_desc* d, const rrt_encoder_nystrom_desc* nys, int64_t N, rrt_grid* g) {
+  if (!d || !nys || N <= 0) return RRT_E_INVALID;
+  if (nys->mode != RRT_NYSTROM_BAG && nys->mode != RRT_NYSTROM_REGIONS)
+    return unsupported("encoder_nystrom: mode must be RRT_NYSTROM_BAG or RRT_NYSTROM_REGIONS");
+  if (d->compute != RRT_COMPUTE_F32) return unsupported("encoder_nystrom: compute must be RRT_COMPUTE_F32 (exact fp32 only)");
+  if (d->n_rmsa_layers < 1 || d->n_rmsa_layers > RRT_MAX_RMSA_LAYERS) return unsupported("encoder_nystrom: n_rmsa_layers out of range");
+  if (nys->attn.dim != d->dim) return unsupported("encoder_nystrom: attn.dim must be the encoder's dim");
+  if (N > 1000000) return unsupported("encoder_nystrom: n_tokens above 1e6");
+  *g = rrt_grid{};
+  int64_t n = N;
+  if (nys->mode == RRT_NYSTROM_REGIONS) {
+    int rc = rrt_region_grid(N, d->region_num, d->region_size, d->min_region_num, d->min_region_ratio, g);
+    if (rc) return rc == RRT_E_INVALID && d->region_size <= 0 && d->region_num <= 0 ? unsupported("region_num must be positive") : rc;
+    n = (int64_t)g->s * g->s;
+    rc = check_nystrom_batch((int64_t)g->regions_side * g->regions_side);
+    if (rc) return rc;
+  }
+  int rc = check_nystrom(&nys->attn, n);
+  if (rc) return rc;
+  if (nys->attn.heads * nys->attn.dim_head != d->dim) return unsupported("encoder_nystrom: attn.heads * attn.dim_head must equal dim");
+  if (d->pos) {
+    if (d->pos != RRT_POS_PEG && d->pos != RRT_POS_PPEG) return unsupported("pos must be none / peg / ppeg");
+    if (d->peg_k <= 0 || d->peg_k % 2 == 0 || d->peg_k > 11) return unsupported("peg_k must be odd and <= 11");
+    if (d->pos_pos != -1 && d->pos_pos != 0) return unsupported("pos_pos must be -1 or 0");
+  }
+  if (d->ffn) {
+    if (d->ffn_hidden <= 0 || d->ffn_hidden % 32 != 0)
+      return unsupported("ffn: hidden width int(dim * mlp_ratio) must be a positive multiple of 32");
+    if (d->ffn_act != RRT_ACT_GELU && d->ffn_act != RRT_ACT_RELU) return unsupported("ffn_act must be gelu or relu");
+  }
+  return RRT_OK;
+}
+
+struct EncoderNystromWs {
+  char *tail, *nys;
+  float *xa, *xb, *u, *att, *hid;
+  size_t tail_bytes, bytes;
+};
+EncoderNystromWs carve_encoder_nystrom(const rrt_encoder_desc* d, const rrt_encoder_nystrom_desc* nys, int64_t N, const rrt_grid& g,
+                                       size_t tail_bytes, char* base) {
+  EncoderNystromWs ws{};
+  const size_t D = (size_t)d->dim;
+  const bool regions = nys->mode == RRT_NYSTROM_REGIONS;
+  const size_t Np = regions ? (size_t)g.H * g.H : (size_t)N;
+  Arena a{base};
+  ws.tail = a.take<char>(tail_bytes);
+  ws.tail_bytes = tail_bytes;
+  ws.xa = a.take((size_t)N * D);
+  ws.xb = a.take((size_t)N * D);
+  ws.u = a.take(Np * D);               // LN(x) (region mode: partitioned, its appended rows zero)
+  ws.att = a.take((size_t)N * D);      // an attention's or an FFN's output in front of its residual
+  if (d->ffn) ws.hid = a.take((size_t)N * d->ffn_hidden);
+  ws.nys = a.take<char>(regions ? carve_nystrom(&nys->attn, (int64_t)g.s * g.s, nullptr, true, (int64_t)g.regions_side * g.regions_side).bytes
+                                : carve_nystrom(&nys->attn, N, nullptr).bytes);
+  ws.bytes = a.bytes();
+  return ws;
+}
+
+// everything checked by the caller.  cur is the activations' own buffer (xa or xb): the residuals are added in place, a stage
+// that cannot run in place writes the other buffer.
+int encoder_nystrom_forward(const rrt_encoder_desc* desc, const rrt_encoder_nystrom_desc* nys, const rrt_encoder_weights* w,
+                            const float* x, float* y, int64_t N, const rrt_grid& g, const EncoderNystromWs& ws, hipStream_t st) {
+  const rrt_nystrom_desc* ad = &nys->attn;
+  const int D = desc->dim;
+  const bool regions = nys->mode == RRT_NYSTROM_REGIONS;
+  float* cur = ws.xa;
+  float* other = ws.xb;
+  auto swap = [&]() {
+    float* t = cur;
+    cur = other;
+    other = t;
+  };
+  auto pos_embed = [&](const float* in, float* out) -> int {
+    if (!w->pos_w[0] || (desc->pos == RRT_POS_PPEG && (!w->pos_w[1] || !w->pos_w[2]))) return RRT_E_INVALID;
+    RRT_TRY(launch_peg(in, w->pos_w, w->pos_b, out, (int)N, D, desc->peg_k, desc->peg_1d, desc->pos == RRT_POS_PPEG, st));
+    return RRT_OK;
+  };
+  int rc;
+  if (desc->pos && desc->pos_pos == -1) {
+    rc = pos_embed(x, cur);
+    if (rc) return rc;
+  } else {
+    RRT_TRY(hipMemcpyAsync(cur, x, (size_t)N * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+  }
+  for (int li = 0; li < desc->n_rmsa_layers; ++li) {
+    if (li == 1 && desc->pos && desc->pos_pos == 0) {
+      rc = pos_embed(cur, other);
+      if (rc) return rc;
+      swap();
+    }
+    const rrt_attn_weights& lw = w->rmsa[li];
+    if (!lw.norm_w || !lw.norm_b) return RRT_E_INVALID;
+    rrt_nystrom_weights aw{lw.qkv_w, lw.proj_w, lw.proj_b, lw.pe_w};
+    if (!nystrom_weights_ok(ad, &aw)) return RRT_E_INVALID;
+    if (!regions) {
+      // x += NystromAttention(LN(x)) over the whole bag
+      RRT_TRY(launch_layernorm(cur, nullptr, lw.norm_w, lw.norm_b, ws.u, (int)N, D, st));
+      rc = nystrom_forward(ad, &aw, ws.u, ws.att, N, carve_nystrom(ad, N, ws.nys), st);
+      if (rc) return rc;
+      RRT_TRY(launch_add_cols(cur, ws.att, (size_t)N, D, D, st));
+    } else {
+      // LN + zero rows to H * H + partition -> u [R, P, D]; the attention over the R regions; to_out with the un-partition,
+      // the drop of the appended rows and the residual in its epilogue (slot -> token, as R-MSA's out-projection)
+      const GridDev gd = to_dev(g);
+      const int64_t R = gd.Rt, P = gd.P;
+      const NystromWs nws = carve_nystrom(ad, P, ws.nys, true, R);
+      RRT_TRY(launch_ln_partition(cur, lw.norm_w, lw.norm_b, ws.u, D, gd, st));
+      const float* o = nullptr;
+      if (R == 1) {
+        // one region: the single-sequence stages; its output rows are the padded buffer's last P
+        rc = nystrom_front(ad, &aw, ws.u, P, nws, st, nullptr);
+        if (rc) return rc;
+        RRT_TRY(launch_nystrom_output(nws.qkv, nws.kl, nws.wz, ad->residual ? aw.conv_w : nullptr, nws.o, (long)nws.np, ad->heads,
+                                      ad->residual_conv_kernel, st));
+        o = nws.o + (size_t)(nws.np - P) * D;
+      } else {
+        rc = nystrom_batched_front(ad, &aw, ws.u, P, nws, st, &o);
+        if (rc) return rc;
+      }
+      LinearEpilogue ep{};
+      ep.bias = aw.out_b;
+      ep.resid = cur;
+      ep.g = gd;
+      RRT_TRY(launch_linear(o, aw.out_w, other, gd.Np, D, D, ep, st));
+      swap();
+    }
+    if (desc->ffn) {
+      // x += fc2(act(fc1(LN2(x))))
+      if (!lw.norm2_w || !lw.norm2_b || !lw.fc1_w || !lw.fc1_b || !lw.fc2_w || !lw.fc2_b) return RRT_E_INVALID;
+      RRT_TRY(launch_layernorm(cur, nullptr, lw.norm2_w, lw.norm2_b, ws.u, (int)N, D, st));
+      LinearEpilogue e1{};
+      e1.bias = lw.fc1_b;
+      e1.act = desc->ffn_act;
+      RRT_TRY(launch_linear(ws.u, lw.fc1_w, ws.hid, (int)N, desc->ffn_hidden, D, e1, st));
+      LinearEpilogue e2{};
+      e2.bias = lw.fc2_b;
+      RRT_TRY(launch_linear(ws.hid, lw.fc2_w, ws.att, (int)N, D, desc->ffn_hidden, e2, st));
+      RRT_TRY(launch_add_cols(cur, ws.att, (size_t)N, D, D, st));
+    }
+  }
+  return encoder_tail(desc, w, cur, x, y, N, ws.tail, ws.tail_bytes, st);
+}
 }  // namespace
 
 extern "C" {
@@ -679,6 +874,141 @@ int rrt_nystrom_attention_row_f32(const rrt_nystrom_desc* desc, const rrt_nystro
   rc = nystrom_forward(desc, w, x, y, n, ws, (hipStream_t)stream, rw.lse);
   if (rc) return rc;
   return nystrom_row(desc, row, attn, n, ws, rw, (hipStream_t)stream);
+}
+
+// ---- ... b sequences per launch: the forward and its stages (the b = 1 calls are the single-sequence ones, launch for launch)
+int rrt_nystrom_batched_workspace_size(const rrt_nystrom_desc* desc, int64_t b, int64_t n, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_nystrom(desc, n);
+  if (!rc) rc = check_nystrom_batch(b);
+  if (!rc) rc = check_nystrom_rows(b, n);
+  if (rc) return rc;
+  *bytes = carve_nystrom(desc, n, nullptr, true, b).bytes;
+  return RRT_OK;
+}
+
+int rrt_nystrom_attention_batched_f32(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w, const float* x, float* y,
+                                      int64_t b, int64_t n, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!desc || !w || !x || !y) return RRT_E_INVALID;
+  int rc = check_nystrom(desc, n);
+  if (!rc) rc = check_nystrom_batch(b);
+  if (!rc) rc = check_nystrom_rows(b, n);
+  if (rc) return rc;
+  if (!nystrom_weights_ok(desc, w)) return RRT_E_INVALID;
+  if (!workspace || workspace_bytes < carve_nystrom(desc, n, nullptr, true, b).bytes) return RRT_E_WORKSPACE;
+  const NystromWs ws = carve_nystrom(desc, n, (char*)workspace, true, b);
+  hipStream_t st = (hipStream_t)stream;
+  if (b == 1) return nystrom_forward(desc, w, x, y, n, ws, st);
+  const float* o = nullptr;
+  rc = nystrom_batched_front(desc, w, x, n, ws, st, &o);
+  if (rc) return rc;
+  LinearEpilogue eo{};
+  eo.bias = w->out_b;
+  RRT_TRY(launch_linear(o, w->out_w, y, (int)(b * n), desc->dim, desc->heads * 64, eo, st));
+  return RRT_OK;
+}
+
+int rrt_nystrom_landmarks_batched_f32(const float* qkv, float* ql, float* kl, int64_t b, int64_t n_padded, int32_t heads,
+                                      void* stream) {
+  if (!qkv || !ql || !kl) return RRT_E_INVALID;
+  int rc = check_np_heads(n_padded, heads);
+  if (!rc) rc = check_nystrom_batch(b);
+  if (rc) return rc;
+  return (int)launch_nystrom_landmarks(qkv, ql, kl, (long)n_padded, heads, (hipStream_t)stream, (int)b);
+}
+
+int rrt_nystrom_landmark_sim_batched_f32(const float* ql, const float* kl, float* a2, int64_t b, int32_t heads, void* stream) {
+  if (!ql || !kl || !a2) return RRT_E_INVALID;
+  int rc = check_nystrom_heads(heads);
+  if (!rc) rc = check_nystrom_batch(b);
+  if (rc) return rc;
+  return (int)launch_nystrom_sim2(ql, kl, a2, heads, (hipStream_t)stream, (int)b);
+}
+
+int rrt_nystrom_landmark_attn_batched_workspace_size(int64_t b, int64_t n_padded, int32_t heads, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_np_heads(n_padded, heads);
+  if (!rc) rc = check_nystrom_batch(b);
+  if (rc) return rc;
+  *bytes = nystrom_lattn_floats((long)n_padded, heads, (int)b) * sizeof(float);
+  return RRT_OK;
+}
+
+int rrt_nystrom_landmark_attn_batched_f32(const float* qkv, const float* ql, float* av, int64_t b, int64_t n_padded,
+                                          int32_t heads, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!qkv || !ql || !av) return RRT_E_INVALID;
+  int rc = check_np_heads(n_padded, heads);
+  if (!rc) rc = check_nystrom_batch(b);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < nystrom_lattn_floats((long)n_padded, heads, (int)b) * sizeof(float)) return RRT_E_WORKSPACE;
+  return (int)launch_nystrom_lattn(qkv, ql, av, (float*)workspace, (long)n_padded, heads, (hipStream_t)stream, nullptr, (int)b);
+}
+
+int rrt_nystrom_pinv_batched_workspace_size(int64_t b, int32_t heads, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_nystrom_heads(heads);
+  if (!rc) rc = check_nystrom_batch(b);
+  if (rc) return rc;
+  *bytes = nystrom_pinv_floats(heads, (int)b) * sizeof(float);
+  return RRT_OK;
+}
+
+int rrt_nystrom_pinv_batched_f32(const float* a2, float* z, int64_t b, int32_t heads, int32_t iterations, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  if (!a2 || !z) return RRT_E_INVALID;
+  int rc = check_nystrom_heads(heads);
+  if (!rc) rc = check_pinv_iterations(iterations);
+  if (!rc) rc = check_nystrom_batch(b);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < nystrom_pinv_floats(heads, (int)b) * sizeof(float)) return RRT_E_WORKSPACE;
+  return (int)launch_nystrom_pinv(a2, z, (float*)workspace, heads, iterations, (hipStream_t)stream, (int)b);
+}
+
+int rrt_nystrom_zav_batched_f32(const float* z, const float* av, float* wz, int64_t b, int32_t heads, void* stream) {
+  if (!z || !av || !wz) return RRT_E_INVALID;
+  int rc = check_nystrom_heads(heads);
+  if (!rc) rc = check_nystrom_batch(b);
+  if (rc) return rc;
+  return (int)launch_nystrom_zav(z, av, wz, heads, (hipStream_t)stream, (int)b);
+}
+
+int rrt_nystrom_output_batched_f32(const float* qkv, const float* kl, const float* wz, const float* conv_w, float* o, int64_t b,
+                                   int64_t n_padded, int32_t heads, int32_t conv_k, void* stream) {
+  if (!qkv || !kl || !wz || !o) return RRT_E_INVALID;
+  int rc = check_np_heads(n_padded, heads);
+  if (!rc) rc = check_nystrom_batch(b);
+  if (rc) return rc;
+  if (conv_w && (conv_k < 1 || conv_k % 2 == 0 || conv_k > 63)) return unsupported("nystrom: residual_conv_kernel must be odd and <= 63");
+  return (int)launch_nystrom_output(qkv, kl, wz, conv_w, o, (long)n_padded, heads, conv_k, (hipStream_t)stream, (int)b);
+}
+
+// ---- ... the Nystrom ablations of RRTEncoder: the attention layers here, the rest of the forward is api.hip's (encoder_tail)
+int rrt_encoder_nystrom_workspace_size(const rrt_encoder_desc* desc, const rrt_encoder_nystrom_desc* nys, int64_t n_tokens,
+                                       size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  rrt_grid g{};
+  int rc = check_encoder_nystrom(desc, nys, n_tokens, &g);
+  if (rc) return rc;
+  size_t tail = 0;
+  rc = encoder_tail_workspace_size(desc, n_tokens, &tail);
+  if (rc) return rc;
+  *bytes = carve_encoder_nystrom(desc, nys, n_tokens, g, tail, nullptr).bytes;
+  return RRT_OK;
+}
+
+int rrt_encoder_nystrom_forward_f32(const rrt_encoder_desc* desc, const rrt_encoder_nystrom_desc* nys,
+                                    const rrt_encoder_weights* w, const float* x, float* y, int64_t n_tokens, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  if (!desc || !nys || !w || !x || !y || x == y) return RRT_E_INVALID;
+  rrt_grid g{};
+  int rc = check_encoder_nystrom(desc, nys, n_tokens, &g);
+  if (rc) return rc;
+  size_t tail = 0;
+  rc = encoder_tail_workspace_size(desc, n_tokens, &tail);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < carve_encoder_nystrom(desc, nys, n_tokens, g, tail, nullptr).bytes) return RRT_E_WORKSPACE;
+  return encoder_nystrom_forward(desc, nys, w, x, y, n_tokens, g, carve_encoder_nystrom(desc, nys, n_tokens, g, tail, (char*)workspace),
+                                 (hipStream_t)stream);
 }
 
 // ---- ... training: the stashing forward, the backward and its stages (nystrom_bwd.hip)

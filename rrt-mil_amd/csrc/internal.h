@@ -399,18 +399,19 @@ hipError_t launch_peg_backward(const float* x, const float* dy, const float* con
 
 // ---- Nystrom attention and the TransMIL baseline around it (nystrom.hip; modules/nystrom_attention.py, transmil.py), inference.
 // qkv [np, 3 * heads * 64] (q scaled, the first np - n rows zero), np a multiple of 256; ql / kl / av / wz [heads, 256, 64];
-// a2 / z [heads, 256, 256]; o [np, heads * 64]
+// a2 / z [heads, 256, 256]; o [np, heads * 64].  b > 1: that many sequences in one launch per stage, every layout with a leading
+// b (each item's zero rows in front of it), and ONE pseudo-inverse scale over all b * heads matrices
 void nystrom_chunks(long np, int* nsub, int* sub_per_chunk, int* nch);
-size_t nystrom_lattn_floats(long np, int heads);
-size_t nystrom_pinv_floats(int heads);
-hipError_t launch_nystrom_landmarks(const float* qkv, float* ql, float* kl, long np, int heads, hipStream_t st);
-hipError_t launch_nystrom_sim2(const float* ql, const float* kl, float* a2, int heads, hipStream_t st);
+size_t nystrom_lattn_floats(long np, int heads, int b = 1);
+size_t nystrom_pinv_floats(int heads, int b = 1);
+hipError_t launch_nystrom_landmarks(const float* qkv, float* ql, float* kl, long np, int heads, hipStream_t st, int b = 1);
+hipError_t launch_nystrom_sim2(const float* ql, const float* kl, float* a2, int heads, hipStream_t st, int b = 1);
 hipError_t launch_nystrom_lattn(const float* qkv, const float* ql, float* av, float* ws, long np, int heads, hipStream_t st,
-                                float* lse = nullptr);     // lse [heads, 256] (optional): the row log-sum-exp of ql k^T
-hipError_t launch_nystrom_pinv(const float* a2, float* z, float* ws, int heads, int iters, hipStream_t st);
-hipError_t launch_nystrom_zav(const float* z, const float* av, float* wz, int heads, hipStream_t st);
+                                float* lse = nullptr, int b = 1);     // lse [heads, 256] (optional): the row log-sum-exp of ql k^T
+hipError_t launch_nystrom_pinv(const float* a2, float* z, float* ws, int heads, int iters, hipStream_t st, int b = 1);
+hipError_t launch_nystrom_zav(const float* z, const float* av, float* wz, int heads, hipStream_t st, int b = 1);
 hipError_t launch_nystrom_output(const float* qkv, const float* kl, const float* wz, const float* conv_w, float* o, long np,
-                                 int heads, int ks, hipStream_t st);
+                                 int heads, int ks, hipStream_t st, int b = 1);
 // One query row of the approximated attention matrix (nystrom_row.hip): r [heads, 256] = softmax(q[row_padded] kl^T) z and
 // attn [heads, out_ld], whose entry key - col0 is sum_i r_i exp(ql_i . k_key - lse3_i) for the keys col0 .. np - 1
 hipError_t launch_nystrom_attn_row(const float* qkv, const float* ql, const float* kl, const float* z, const float* lse3,

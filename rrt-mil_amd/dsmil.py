@@ -24,7 +24,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from ._head import HeadState, _InstanceMax, head_compute, instance_max  # noqa: F401  (both live in _head.py: MaxMIL shares them)
+from ._head import HeadState, _InstanceMax, copy_encoder_desc, head_compute, instance_max  # noqa: F401  (both live in _head.py: MaxMIL shares them)
 from .clam import _BranchPool
 from .encoder import RRTEncoder
 from .mil import lib_linear
@@ -110,7 +110,7 @@ class MILNet(HeadState, nn.Module):
         enc, p = self._enc(), RRTEncoder._ptr
         d, w = _lib.DsmilDesc(), _lib.DsmilWeights()
         if enc is not None:
-            C.memmove(C.byref(d.enc), C.byref(enc._desc), C.sizeof(_lib.EncoderDesc))
+            copy_encoder_desc(d.enc, enc, "DSMIL")
             w.enc = enc._weights()
         d.enc.dim = 512
         d.enc.compute = self._compute()

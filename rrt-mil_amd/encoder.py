@@ -71,15 +71,25 @@ class RegionAttntion(nn.Module):
                  region_num=8, epeg=False, min_region_num=0, min_region_ratio=0., region_attn='native',
                  **kwargs):
         super().__init__()
-        if region_attn != 'native':
-            raise NotImplementedError("region_attn='ntrans' is not wired into RRTEncoder; the Nystrom attention itself is "
-                                      "rrt_mil_amd.NystromAttention (rrt_mil_amd/transmil.py)")
+        if region_attn not in ('native', 'ntrans'):
+            raise NotImplementedError(f"region_attn={region_attn!r}")
         self.dim, self.num_heads = dim, num_heads
         self.region_size = region_size if region_size > 0 else None
         self.region_num = region_num
         self.min_region_num, self.min_region_ratio = min_region_num, min_region_ratio
-        self.attn = InnerAttention(dim, head_dim=head_dim, num_heads=num_heads, qkv_bias=qkv_bias,
-                                   proj_drop=drop, epeg=epeg, **kwargs)
+        self.region_attn = region_attn
+        if region_attn == 'ntrans':
+            # modules/rmsa.py:167-173: NystromAttention inside the regions, the regions as its batch
+            head_dim = head_dim or dim // num_heads
+            if head_dim != 64 or head_dim * num_heads != dim:
+                raise NotImplementedError(f"region_attn='ntrans' runs rrt_mil_amd.NystromAttention inside the regions, whose "
+                                          f"kernels take dim_head = 64 and heads * dim_head == dim: got dim {dim}, {num_heads} "
+                                          f"heads (head dim {head_dim})")
+            from .transmil import NystromAttention
+            self.attn = NystromAttention(dim=dim, dim_head=head_dim, heads=num_heads, dropout=drop)
+        else:
+            self.attn = InnerAttention(dim, head_dim=head_dim, num_heads=num_heads, qkv_bias=qkv_bias,
+                                       proj_drop=drop, epeg=epeg, **kwargs)
 
 
 class CrossRegionAttntion(nn.Module):
@@ -158,8 +168,14 @@ class TransLayer(nn.Module):
         elif attn == 'crmsa':
             self.attn = CrossRegionAttntion(crmsa_k=crmsa_k, **common, **kwargs)
         elif attn == 'ntrans':
-            raise NotImplementedError("attn='ntrans' is not wired into RRTEncoder; the Nystrom attention itself is "
-                                      "rrt_mil_amd.NystromAttention (rrt_mil_amd/transmil.py)")
+            # modules/rrt.py:49-58: a whole-bag NystromAttention in place of R-MSA
+            if trans_dim != 64 or head * trans_dim != dim:
+                raise NotImplementedError(f"attn='ntrans' runs rrt_mil_amd.NystromAttention over the bag, whose kernels take "
+                                          f"dim_head = trans_dim = 64 and n_heads * trans_dim == mlp_dim: got mlp_dim {dim}, "
+                                          f"{head} heads, trans_dim {trans_dim}")
+            from .transmil import NystromAttention
+            self.attn = NystromAttention(dim=dim, dim_head=trans_dim, heads=head, num_landmarks=256, pinv_iterations=6,
+                                         residual=True, dropout=drop_out)
         else:
             raise NotImplementedError
         # timm's DropPath (rrt.py:102) holds no parameters: at batch size 1 it keeps or drops a whole residual
@@ -313,6 +329,12 @@ class RRTEncoder(nn.Module):
             peg_1d=int(bool(peg_1d)), epeg_2d=int(bool(kwargs.get('epeg_2d', False))),
             epeg_type={'attn': _lib.EPEG_ATTN, 'value_bf': _lib.EPEG_VALUE_BF,
                        'value_af': _lib.EPEG_VALUE_AF}[kwargs.get('epeg_type', 'attn')])
+        # the reference's Nystrom ablations: the layers hold NystromAttention parameters and the forward is
+        # rrt_encoder_nystrom_forward_f32 (inference, exact fp32); 0 = the R-MSA encoder
+        self._nys_mode = 0
+        if n_layers - 1 > 0:
+            self._nys_mode = (_lib.NYSTROM_BAG if attn == 'ntrans' else
+                              _lib.NYSTROM_REGIONS if kwargs.get('region_attn', 'native') == 'ntrans' else 0)
         if self._desc.pos and (pos_pos not in (-1, 0) or (pos_pos == 0 and n_layers - 1 < 2)):
             # the reference only applies pos_embedding before the first layer (pos_pos = -1) or before layer index 1
             # (pos_pos = 0, which needs a second R-MSA layer: the default `--pos ppeg` run with n_layers = 2 never
@@ -339,6 +361,7 @@ class RRTEncoder(nn.Module):
     def __setstate__(self, st):
         self.__dict__.update(st)
         self.__dict__.setdefault("_ws", None)
+        self.__dict__.setdefault("_nys_mode", 0)
 
     # ------------------------------------------------------------------ C-ABI plumbing
     @staticmethod
@@ -350,14 +373,28 @@ class RRTEncoder(nn.Module):
                                    "torch.autocast or compute_dtype, not by casting the module)")
         return t.data_ptr()
 
+    def _nystrom_of(self, layer):
+        """the NystromAttention of an R-MSA-slot layer of the two ablations (None: an R-MSA / CR-MSA layer)"""
+        if not self._nys_mode or layer is getattr(self, "cr_msa", None):
+            return None
+        return layer.attn if self._nys_mode == _lib.NYSTROM_BAG else layer.attn.attn
+
     def _attn_weights(self, layer):
-        ia = layer.attn.attn
         w = _lib.AttnWeights()
         w.norm_w, w.norm_b = self._ptr(layer.norm.weight), self._ptr(layer.norm.bias)
-        w.qkv_w, w.qkv_b = self._ptr(ia.qkv.weight), self._ptr(ia.qkv.bias)
-        w.proj_w, w.proj_b = self._ptr(ia.proj.weight), self._ptr(ia.proj.bias)
-        if ia.pe is not None:
-            w.pe_w, w.pe_b = self._ptr(ia.pe.weight), self._ptr(ia.pe.bias)   # [h,1,k,1] == [h,k]
+        na = self._nystrom_of(layer)
+        if na is not None:
+            # rrt_encoder_nystrom_forward_f32's slots: to_qkv (no bias), to_out.0, res_conv [h,1,k,1] == [h,k]
+            w.qkv_w = self._ptr(na.to_qkv.weight)
+            w.proj_w, w.proj_b = self._ptr(na.to_out[0].weight), self._ptr(na.to_out[0].bias)
+            if na.residual:
+                w.pe_w = self._ptr(na.res_conv.weight)
+        else:
+            ia = layer.attn.attn
+            w.qkv_w, w.qkv_b = self._ptr(ia.qkv.weight), self._ptr(ia.qkv.bias)
+            w.proj_w, w.proj_b = self._ptr(ia.proj.weight), self._ptr(ia.proj.bias)
+            if ia.pe is not None:
+                w.pe_w, w.pe_b = self._ptr(ia.pe.weight), self._ptr(ia.pe.bias)   # [h,1,k,1] == [h,k]
         if layer.ffn:
             w.norm2_w, w.norm2_b = self._ptr(layer.norm2.weight), self._ptr(layer.norm2.bias)
             w.fc1_w, w.fc1_b = self._ptr(layer.mlp.fc1.weight), self._ptr(layer.mlp.fc1.bias)
@@ -525,6 +562,8 @@ class RRTEncoder(nn.Module):
         return ws
 
     def _compute_mode(self):
+        if self._nys_mode:            # exact fp32 in every context (no 16-bit path for the pseudo-inverse iteration)
+            return _lib.COMPUTE_F32
         dt = self.compute_dtype
         if dt is None and torch.is_autocast_enabled("cuda"):
             dt = torch.get_autocast_dtype("cuda")
@@ -546,6 +585,8 @@ class RRTEncoder(nn.Module):
         if d != self.final_dim:
             raise ValueError(f"expected feature dim {self.final_dim}, got {d}")
         y = out if out is not None else torch.empty_like(x2d)
+        if self._nys_mode:
+            return self._forward_bag_nystrom(x2d, y)
         if self._stochastic():
             # train() without a graph (torch.no_grad(): MC dropout, EMA / teacher forwards, frozen models): the
             # reference still applies proj dropout and stochastic depth; same kernels as the training forward, the
@@ -576,9 +617,48 @@ class RRTEncoder(nn.Module):
             _lib.check(rc, "rrt_encoder_forward_f32")
         return y
 
+    def _nystrom_desc(self):
+        first = next(iter(self.layers.children()))
+        d = _lib.EncoderNystromDesc()
+        d.mode, d.attn = self._nys_mode, self._nystrom_of(first)._desc()
+        return d
+
+    def _forward_bag_nystrom(self, x2d, y):
+        """attn='ntrans' / region_attn='ntrans': ONE rrt_encoder_nystrom_forward_f32 call.  Inference only."""
+        if self._stochastic():
+            raise NotImplementedError("rrt_mil_amd.RRTEncoder with NystromAttention layers (attn='ntrans' / region_attn="
+                                      "'ntrans') in train() with dropout: inference only, call eval() under torch.no_grad()")
+        if torch.is_grad_enabled() and (x2d.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("rrt_mil_amd.RRTEncoder with NystromAttention layers (attn='ntrans' / region_attn="
+                                      "'ntrans') has no backward: call it in eval() under torch.no_grad()")
+        lib = _lib.load()
+        n, dev = x2d.shape[0], x2d.device
+        desc, nd = self._desc, self._nystrom_desc()
+        desc.compute, desc.weights16_valid, desc.solo = _lib.COMPUTE_F32, 0, int(self.__dict__.get("solo", True))
+        cache = self.__dict__.setdefault("_ws_need", {})
+        need = cache.get(("nys", n))
+        if need is None:
+            c_need = C.c_size_t()
+            _lib.check(lib.rrt_encoder_nystrom_workspace_size(C.byref(desc), C.byref(nd), n, C.byref(c_need)),
+                       "rrt_encoder_nystrom_workspace_size")
+            need = cache[("nys", n)] = int(c_need.value)
+        ws = self._ws
+        if ws is None or ws.device != dev or ws.numel() < need:
+            ws = self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        w = self._weights()
+        with torch.cuda.device(dev):
+            rc = lib.rrt_encoder_nystrom_forward_f32(C.byref(desc), C.byref(nd), C.byref(w), x2d.data_ptr(), y.data_ptr(), n,
+                                                     ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, "rrt_encoder_nystrom_forward_f32")
+        return y
+
     def forward_batch(self, x3d):
         """(B, N, D) -> (B, N, D) with the reference's batch semantics (CR-MSA's inner attention over the representatives
         of ALL bags of the batch, modules/rmsa.py:316-322).  Inference; one library call on the current stream."""
+        if self._nys_mode:
+            raise NotImplementedError("rrt_mil_amd.RRTEncoder with NystromAttention layers (attn='ntrans' / region_attn="
+                                      "'ntrans') takes one bag per call: at batch > 1 the regions of all bags would share one "
+                                      "pseudo-inverse scale and CR-MSA couples the bags; loop over the bags (forward_bags)")
         lib = _lib.load()
         if not x3d.is_cuda:
             raise _lib.RRTHipError("rrt_mil_amd.RRTEncoder runs on MI355X only; there is no CPU fallback")
@@ -706,6 +786,10 @@ class RRTEncoder(nn.Module):
         n_bags = len(bags)
         if not n_bags:
             return []
+        if self._nys_mode:              # a plain loop: the executor takes only the R-MSA encoder's descriptor
+            ys = [self.forward_bag(b[0] if b.dim() == 3 else b, None if outs is None else outs[i].view(-1, self.final_dim))
+                  for i, b in enumerate(bags)]
+            return [y.unsqueeze(0) if b.dim() == 3 else y for b, y in zip(bags, ys)] if outs is None else outs
         if self._stochastic():          # train() under no_grad: dropout / stochastic depth per bag, one bag at a time
             return [self.forward_bag(b[0]).unsqueeze(0) if b.dim() == 3 else self.forward_bag(b) for b in bags]
         dev = bags[0].device
@@ -832,6 +916,8 @@ class RRTEncoder(nn.Module):
         return False
 
     def forward(self, x):
+        if self._nys_mode:              # inference only: _forward_bag_nystrom raises on a graph or dropout
+            return self._forward_impl(x, False)
         if self._wants_grad(x):
             return self._forward_impl(x, True)
         with torch.no_grad():
@@ -841,6 +927,9 @@ class RRTEncoder(nn.Module):
         """One bag with an autograd graph (rrt_encoder_forward_train_f32 / rrt_encoder_backward_f32)."""
         if not x2d.is_cuda:
             raise _lib.RRTHipError("rrt_mil_amd.RRTEncoder runs on MI355X only; there is no CPU fallback")
+        if self._nys_mode:
+            raise NotImplementedError("rrt_mil_amd.RRTEncoder with NystromAttention layers (attn='ntrans' / region_attn="
+                                      "'ntrans') has no backward: call it in eval() under torch.no_grad()")
         x2d = x2d.float().contiguous()
         if x2d.shape[1] != self.final_dim:
             raise ValueError(f"expected feature dim {self.final_dim}, got {x2d.shape[1]}")

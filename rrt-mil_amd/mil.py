@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from ._head import HeadState
+from ._head import HeadState, copy_encoder_desc
 from .encoder import RRTEncoder, initialize_weights
 
 
@@ -264,7 +264,7 @@ class RRTMIL(HeadState, nn.Module):
     def _mil_desc(self, input_dim, solo=True):
         enc = self.online_encoder
         d = _lib.MilDesc()
-        C.memmove(C.byref(d.enc), C.byref(enc._desc), C.sizeof(_lib.EncoderDesc))
+        copy_encoder_desc(d.enc, enc, "RRTMIL")
         d.enc.compute = enc._compute_mode()
         # per-call scheduling hint, never inherited from whatever the encoder's last call left in its descriptor
         # (rrt_encoder_desc.solo also picks between CR-MSA fronts that differ in summation order, ~1e-7: a classifier's logits
@@ -367,7 +367,8 @@ class RRTMIL(HeadState, nn.Module):
             return self._forward_infer(x, return_attn, no_norm)
 
     def _forward_infer(self, x, return_attn=False, no_norm=False):
-        if x.dim() == 3 and x.size(0) == 1 and x.is_cuda:
+        # (an encoder of NystromAttention layers has no one-call head entry: the layer path around its own one call)
+        if x.dim() == 3 and x.size(0) == 1 and x.is_cuda and not self.online_encoder._nys_mode:
             # (1, N, input_dim): the form of every reference trainer -> one library call
             out = self.forward_bag(x[0], return_attn=return_attn, no_norm=no_norm)
             if return_attn:

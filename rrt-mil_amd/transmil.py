@@ -176,7 +176,10 @@ class _TransmilStepFn(torch.autograd.Function):
 
 
 class NystromAttention(HeadState, nn.Module):
-    """modules/nystrom_attention.py:32-149.  ``forward(x)`` with x (1, n, dim) -> (1, n, dim); ``mask=`` and
+    """modules/nystrom_attention.py:32-149.  ``forward(x)`` with x (1, n, dim) -> (1, n, dim); ``forward_batch(x)`` with x
+    (b, n, dim), 1 <= b <= 4096 -> (b, n, dim): one launch per stage for all b sequences and ONE pseudo-inverse scale over the
+    whole batch, as the reference's forward on a batch (rrt_nystrom_attention_batched_f32; inference -- ``forward``, the training
+    path and ``attention_row`` keep b = 1); ``mask=`` and
     ``return_attn=True`` are not implemented (the reference's mask branch names undefined variables, and TransMIL passes
     neither); ``attention_row(x, row)`` gives one row of the approximated attention matrix.  The HIP path supports dim_head = 64, num_landmarks = 256, heads <= 16, pinv_iterations <= 16, an odd
     residual_conv_kernel <= 63 and dim a multiple of 32 up to 1024; anything else raises NotImplementedError at the call."""
@@ -240,7 +243,8 @@ class NystromAttention(HeadState, nn.Module):
                                           "call eval() under torch.no_grad(), or opt in with enable_training()")
             _no_graph(self, x, "NystromAttention")
         if x.dim() != 3 or x.shape[0] != 1:
-            raise ValueError(f"NystromAttention expects (1, n, dim) -- batch > 1 is not supported -- got {tuple(x.shape)}")
+            raise ValueError(f"NystromAttention expects (1, n, dim) -- batch > 1 is not supported by forward(): "
+                             f"forward_batch() takes (b, n, dim) for inference -- got {tuple(x.shape)}")
         if x.shape[2] != self.dim:
             raise ValueError(f"expected feature dim {self.dim}, got {x.shape[2]}")
         if layer_path:
@@ -248,20 +252,39 @@ class NystromAttention(HeadState, nn.Module):
                 y = _NystromFn.apply(self._desc(), x[0].float(), self.to_qkv.weight, self.to_out[0].weight, self.to_out[0].bias,
                                      self.res_conv.weight if self.residual else None)
                 return self.to_out[1](y.unsqueeze(0))
+        return self._forward_batched(x)
+
+    def forward_batch(self, x):
+        """x (b, n, dim), 1 <= b <= 4096 -> (b, n, dim): what the reference's forward computes on a batch -- every sequence
+        padded in front on its own, ONE pseudo-inverse scale over all b * heads matrices -- in one launch per stage
+        (rrt_nystrom_attention_batched_f32).  With b = 1 the bits of ``forward``.  Inference only: ``eval()`` under
+        ``torch.no_grad()``; the training path keeps b = 1."""
+        _no_cpu(x, "NystromAttention")
+        if x.dim() != 3 or x.shape[0] < 1:
+            raise ValueError(f"NystromAttention.forward_batch expects (b, n, dim), got {tuple(x.shape)}")
+        if x.shape[2] != self.dim:
+            raise ValueError(f"expected feature dim {self.dim}, got {x.shape[2]}")
+        if (self.training and self._dropout > 0.) or _needs_graph(self, x):
+            raise NotImplementedError("rrt_mil_amd.NystromAttention.forward_batch is an inference entry (the training path keeps "
+                                      "b = 1: the backward kernels take one sequence): call it in eval() under torch.no_grad()")
+        return self._forward_batched(x)
+
+    def _forward_batched(self, x):
         lib = _lib.load()
-        x2d = x[0].float().contiguous()
-        n, dev = x2d.shape[0], x2d.device
+        x3d = x.float().contiguous()
+        (b, n, _), dev = x3d.shape, x3d.device
         d, keep = self._desc(), []
         w = self._weights(keep)
         need = C.c_size_t()
-        _lib.check(lib.rrt_nystrom_workspace_size(C.byref(d), n, C.byref(need)), "rrt_nystrom_workspace_size")
+        _lib.check(lib.rrt_nystrom_batched_workspace_size(C.byref(d), b, n, C.byref(need)), "rrt_nystrom_batched_workspace_size")
         ws = self._workspace(need.value, dev)
-        y = torch.empty((n, self.dim), dtype=torch.float32, device=dev)
+        y = torch.empty((b, n, self.dim), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.rrt_nystrom_attention_f32(C.byref(d), C.byref(w), x2d.data_ptr(), y.data_ptr(), n,
-                                                     ws.data_ptr(), ws.numel(), st), "rrt_nystrom_attention_f32")
-        return y.unsqueeze(0)
+            # (b = 1: the bits of rrt_nystrom_attention_f32)
+            _lib.check(lib.rrt_nystrom_attention_batched_f32(C.byref(d), C.byref(w), x3d.data_ptr(), y.data_ptr(), b, n,
+                                                             ws.data_ptr(), ws.numel(), st), "rrt_nystrom_attention_batched_f32")
+        return y
 
     def attention_row(self, x, row=0):
         """x (1, n, dim), ``row`` in [0, n) -> (y (1, n, dim), attn (1, heads, n)): ``forward(x)``, bit for bit, and row
@@ -273,7 +296,8 @@ class NystromAttention(HeadState, nn.Module):
         _no_cpu(x, "NystromAttention")
         _no_map_with_graph(self, x, self.training and self._dropout > 0., "NystromAttention.attention_row")
         if x.dim() != 3 or x.shape[0] != 1:
-            raise ValueError(f"NystromAttention expects (1, n, dim) -- batch > 1 is not supported -- got {tuple(x.shape)}")
+            raise ValueError(f"NystromAttention.attention_row expects (1, n, dim) -- it keeps b = 1, batch > 1 is "
+                             f"forward_batch() only -- got {tuple(x.shape)}")
         if x.shape[2] != self.dim:
             raise ValueError(f"expected feature dim {self.dim}, got {x.shape[2]}")
         lib = _lib.load()

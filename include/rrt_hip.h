@@ -1210,6 +1210,43 @@ int rrt_nystrom_output_row_backward_f32(const float *qkv, const float *kl, const
                                         const float *d_o_row, float *d_qkv, float *d_kl, float *d_wz, float *d_conv_w,
                                         int64_t row, int64_t n_padded, int32_t heads, int32_t conv_k, void *stream);
 
+/* ---- MHIM-MIL: hard-instance mask selection on the device (Survival/models/MHIM/network.py:480-575, the topk / .tolist() /
+ * set arithmetic of select_mask_fn and get_mask as ONE call) and the row movement of the masked student.
+ *
+ * rrt_mask_select_f32: a [n] the teacher's attention scores, stages [n_stages] (a HOST array; pick is device memory).
+ *  Order      for stage s, the n tokens ordered by a: descending if largest, ascending otherwise.  Equal values: the LOWER
+ *             index first (-0.0 == +0.0: they tie).  NaN counts as greater than every number, as in torch.topk; NaNs tie
+ *             among themselves, by index.
+ *  Candidates the first k tokens of that order, 1 <= k <= n.
+ *  Pick       the candidate at position j is selected iff pick == NULL or pick[j] != 0; pick is device memory [k].
+ *  Result     the selected set is the union over the stages, 1 <= n_stages <= 3.  invert == 0: kept = the complement of the
+ *             selected set; invert != 0: kept = the selected set (select_inv).
+ *  Outputs    ids [n] (int64): ids[0:count) the kept indices ascending, ids[count:n) the others ascending -- a permutation of
+ *             0..n-1, the reference's mask_ids up to the order inside each part.  count [1] (int64, DEVICE memory) the kept
+ *             count.  mask [n] (optional, may be NULL) = 1 where dropped, 0 where kept.
+ *  The same inputs give the same bits; nothing visits the host; stream-ordered, re-entrant.  workspace:
+ *  rrt_mask_select_workspace_size(n, n_stages) bytes (never less for a larger n), else RRT_E_WORKSPACE.  n <= 262144, otherwise
+ *  RRT_E_UNSUPPORTED; RRT_E_INVALID on NULL a / stages / ids / count / workspace, n < 1, n_stages outside 1..3, a k outside
+ *  1..n.  Every argument is checked before the first launch.
+ *
+ * rrt_gather_rows_f32:  dst [n_rows, dim] : dst[r, :] = src[ids[r], :], src [n_src, dim].  An id outside [0, n_src) is never
+ *  dereferenced; its row is filled with NaN.
+ * rrt_scatter_rows_f32: the adjoint.  dst [n_dst, dim] is zero-filled, then dst[ids[r], :] = src[r, :], src [n_rows, dim]; the
+ *  ids are distinct, ids outside [0, n_dst) are skipped.
+ *  Both: dim % 4 == 0 (else RRT_E_UNSUPPORTED), src and dst 16-byte aligned and not overlapping, sizes >= 1 (RRT_E_INVALID). */
+typedef struct rrt_mask_stage {
+  int32_t largest;      /* != 0: the k largest scores are the candidates; 0: the k smallest */
+  int64_t k;
+  const uint8_t *pick;  /* device [k], or NULL = every candidate */
+} rrt_mask_stage;
+int rrt_mask_select_workspace_size(int64_t n, int32_t n_stages, size_t *bytes);
+int rrt_mask_select_f32(const float *a, int64_t n, const rrt_mask_stage *stages, int32_t n_stages, int32_t invert,
+                        int64_t *ids, int64_t *count, uint8_t *mask, void *workspace, size_t workspace_bytes, void *stream);
+int rrt_gather_rows_f32(const float *src, const int64_t *ids, float *dst, int64_t n_rows, int64_t n_src, int32_t dim,
+                        void *stream);
+int rrt_scatter_rows_f32(const float *src, const int64_t *ids, float *dst, int64_t n_rows, int64_t n_dst, int32_t dim,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

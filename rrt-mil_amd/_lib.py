@@ -144,6 +144,12 @@ class TransmilGrads(C.Structure):
                 ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p)]
 
 
+class MaskStage(C.Structure):
+    """rrt_mask_stage: the `k` first tokens by score (descending if `largest`), of which `pick` (device [k] uint8, or None =
+    all of them) says which are selected"""
+    _fields_ = [("largest", C.c_int32), ("k", C.c_int64), ("pick", C.c_void_p)]
+
+
 class Bag(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("n_tokens", C.c_int64)]
 
@@ -383,11 +389,18 @@ SIGNATURES = {
     "rrt_encoder_nystrom_forward_f32": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderNystromDesc),
                                                   C.POINTER(EncoderWeights), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                   C.c_size_t, C.c_void_p]),
+    # MHIM-MIL: mask selection on the device, rows by index
+    "rrt_mask_select_workspace_size": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_mask_select_f32": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(MaskStage), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_gather_rows_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
+    "rrt_scatter_rows_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
 }
 
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32X3 = 0, 1, 2, 3
 POS_NONE, POS_PEG, POS_PPEG = 0, 1, 2
 EPEG_ATTN, EPEG_VALUE_BF, EPEG_VALUE_AF = 0, 1, 2
+MASK_SELECT_MAX_N = 262144               # rrt_mask_select_f32's largest bag
 BAGPOOL_MEAN, BAGPOOL_MAX, BAGPOOL_ATTN, BAGPOOL_ATTN_GATED, BAGPOOL_ATTN_DECONF = range(5)     # rrt_bagmil_desc.pool
 
 PLAN_FUSED, PLAN_FUSED_PROJ, PLAN_FUSED16, PLAN_FUSED_X3, PLAN_CRMSA_PARTS, PLAN_ATTN_HD = 1, 2, 4, 8, 16, 32     # rrt_encoder_plan flags

@@ -477,3 +477,25 @@ hipError_t launch_nystrom_output_row(const float* qkv, const float* kl, const fl
 hipError_t launch_nystrom_output_row_backward(const float* qkv, const float* kl, const float* wz, const float* conv_w,
                                               const float* d_o_row, float* d_qkv, float* d_kl, float* d_wz, float* d_conv_w,
                                               long row, long np, int heads, int ks, hipStream_t st);
+
+// MHIM-MIL's mask selection and the row movement around it (mask_select.hip)
+constexpr int MASK_SELECT_MAX_N = 262144;
+constexpr int MASK_SPLIT_MAX = 16;     // chunks the rank kernel cuts the j range into (rows of part_asc / part_desc)
+struct MaskStages {                    // rrt_mask_stage x n by value; any_asc / any_desc: which of the two ranks a stage reads
+  int n, any_asc, any_desc;
+  int largest[3];
+  int k[3];
+  const unsigned char* pick[3];
+};
+struct MaskSplit {
+  int blocks, split, chunk_len;        // 256-token blocks, chunks of the j range, keys per chunk (a multiple of 256)
+};
+MaskSplit mask_select_split(int n);    // split * n <= min(MASK_SPLIT_MAX * n, MASK_SELECT_MAX_N)
+// part_asc / part_desc [split, n], kept [n], block_cnt / block_off [blocks]
+hipError_t launch_mask_select(const float* a, int n, const MaskStages& st, int invert, long long* ids, long long* count,
+                              unsigned char* mask, unsigned* part_asc, unsigned* part_desc, unsigned char* kept, int* block_cnt,
+                              int* block_off, hipStream_t stream);
+hipError_t launch_gather_rows(const float* src, const long long* ids, float* dst, long long n_rows, long long n_src, int dim,
+                              hipStream_t stream);
+hipError_t launch_scatter_rows(const float* src, const long long* ids, float* dst, long long n_rows, long long n_dst, int dim,
+                               hipStream_t stream);

@@ -509,7 +509,10 @@ typedef struct rrt_mil_weights {
  * Outputs pooled [dim], attn [N] (normalised), a_raw [N] (the scores).  ... and its adjoint: given d_pooled [dim] (and
  * optionally d_attn [N] with c_ext = sum_n attn_n d_attn_n as a device scalar, d_raw [N]) ->
  * dy [N, dim] = attn_n d_pooled, dhid_a / dhid_b [N, hidden], dwcb [hidden + 4] = d c_w | d c_b (at [hidden]).
- * workspace: rrt_attn_pool_workspace_size bytes (either call). */
+ * workspace: rrt_attn_pool_workspace_size bytes (either call).
+ * Limits (RRT_E_UNSUPPORTED from the size query and from both calls alike, before anything is launched): dim % 32, hidden % 4,
+ * n_tokens <= 1e6; the merge block's LDS 4 * (n_tokens / 32 + dim) + 16 KB <= 150 KB; the backward block's LDS
+ * 4 * (dim + 4 * (hidden + 4)) <= 64 KB. */
 int rrt_attn_pool_workspace_size(int64_t n_tokens, int32_t dim, int32_t hidden, size_t *bytes);
 int rrt_attn_pool_f32(const float *y, const float *hid_a, const float *hid_b, const float *c_w, const float *c_b,
                       float *pooled, float *attn, float *a_raw, int64_t n_tokens, int32_t dim, int32_t hidden,
@@ -531,7 +534,9 @@ int rrt_mil_forward_f32(const rrt_mil_desc *desc, const rrt_mil_weights *w, cons
                         void *workspace, size_t workspace_bytes, void *stream);
 
 /* DAttention + predictor alone on encoder features y [n_tokens, dim] (datten.py:28-38,69-83; rrt.py:241).
- * pooled (optional, [dim]) receives the bag embedding.  workspace: rrt_pool_workspace_size bytes. */
+ * pooled (optional, [dim]) receives the bag embedding.  workspace: rrt_pool_workspace_size bytes.
+ * Limits as rrt_attn_pool_f32's forward (the merge block's LDS <= 150 KB); rrt_mil_* and rrt_bagmil_* with an attention pool
+ * refuse the same shapes from their size queries and their forwards. */
 int rrt_pool_workspace_size(int64_t n_tokens, int32_t dim, int32_t hidden, int32_t gated, size_t *bytes);
 int rrt_pool_predict_f32(const float *y, const float *a_w, const float *a_b, const float *b_w,
                          const float *b_b, const float *c_w, const float *c_b, const float *pred_w,

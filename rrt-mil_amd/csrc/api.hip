@@ -1544,6 +1544,16 @@ int check_pool(int64_t N, int dim, int hidden, int act, int n_classes) {
   if (hidden % 4) return unsupported("pool: hidden width must be a multiple of 4");
   if (act < RRT_ACT_NONE || act > RRT_ACT_TANH) return unsupported("pool: act must be none/relu/gelu/tanh");
   if (N > (int64_t)1000000) return unsupported("pool: bag larger than 1e6 tokens");
+  if (!pool_merge_fits(N, dim)) return unsupported("pool: the merge block's LDS (4 * (n_tokens / 32 + dim) + 16 KB) is above 150 KB");
+  return RRT_OK;
+}
+// the pooling alone (rrt_attn_pool_*): one workspace query serves the forward and the backward, so all three refuse what
+// either launch cannot hold
+int check_attn_pool(int64_t N, int dim, int hidden) {
+  int rc = check_pool(N, dim, hidden, RRT_ACT_NONE, 1);
+  if (rc) return rc;
+  if (!pool_backward_fits(dim, hidden))
+    return unsupported("attn pool: the backward block's LDS (4 * (dim + 4 * (hidden + 4))) is above 64 KB");
   return RRT_OK;
 }
 
@@ -1863,7 +1873,7 @@ int rrt_pool_predict_f32(const float* y, const float* a_w, const float* a_b, con
 // ---- the pooling alone, forward and backward (training: the first Linear + activation stay autograd-visible layers)
 int rrt_attn_pool_workspace_size(int64_t n_tokens, int32_t dim, int32_t hidden, size_t* bytes) {
   if (!bytes) return RRT_E_INVALID;
-  int rc = check_pool(n_tokens, dim, hidden, RRT_ACT_NONE, 1);
+  int rc = check_attn_pool(n_tokens, dim, hidden);
   if (rc) return rc;
   const size_t nb = (size_t)(n_tokens + POOL_CHUNK - 1) / POOL_CHUNK;
   const size_t fwd = align_up(nb * ((size_t)dim + 4) * sizeof(float), 256);
@@ -1876,7 +1886,7 @@ int rrt_attn_pool_f32(const float* y, const float* hid_a, const float* hid_b, co
                       float* pooled, float* attn, float* a_raw, int64_t n_tokens, int32_t dim, int32_t hidden,
                       void* workspace, size_t workspace_bytes, void* stream) {
   if (!y || !hid_a || !c_w || !pooled || !attn || !a_raw) return RRT_E_INVALID;
-  int rc = check_pool(n_tokens, dim, hidden, RRT_ACT_NONE, 1);
+  int rc = check_attn_pool(n_tokens, dim, hidden);
   if (rc) return rc;
   size_t need = 0;
   (void)rrt_attn_pool_workspace_size(n_tokens, dim, hidden, &need);
@@ -1891,7 +1901,7 @@ int rrt_attn_pool_backward_f32(const float* y, const float* hid_a, const float* 
                                const float* c_ext, float* dy, float* dhid_a, float* dhid_b, float* dwcb, int64_t n_tokens,
                                int32_t dim, int32_t hidden, void* workspace, size_t workspace_bytes, void* stream) {
   if (!y || !hid_a || !c_w || !attn || !pooled || !d_pooled || !dy || !dhid_a || !dwcb || (hid_b && !dhid_b)) return RRT_E_INVALID;
-  int rc = check_pool(n_tokens, dim, hidden, RRT_ACT_NONE, 1);
+  int rc = check_attn_pool(n_tokens, dim, hidden);
   if (rc) return rc;
   if (d_attn && !c_ext) return RRT_E_INVALID;     // c_ext = sum_n attn_n d_attn_n (device scalar) goes with d_attn
   size_t need = 0;

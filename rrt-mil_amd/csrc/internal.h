@@ -266,6 +266,10 @@ hipError_t launch_pool_merge(const float* part, const float* a_raw, const float*
                              float* pooled, float* logits, float* attn, int no_norm, int N, int dim,
                              int n_classes, hipStream_t st);
 
+// whether the merge block's / the backward block's dynamic LDS fits what launch_pool_merge / launch_pool_backward may ask for
+bool pool_merge_fits(int64_t N, int dim);
+bool pool_backward_fits(int dim, int hid);
+
 // backward of the pooling (mil_pool.hip): dy [N, dim], dhid_a / dhid_b [N, hid], dwcb [hid + 4] = d wc | d bc
 size_t pool_backward_part_floats(int N, int hid);
 hipError_t launch_pool_backward(const float* y, const float* hid_a, const float* hid_b, const float* wc, const float* attn,

@@ -278,19 +278,32 @@ __global__ __launch_bounds__(256) void pool_backward_kernel(const float* __restr
 
 }  // namespace
 
+// dynamic LDS of the two launches below that grow with the shape.  The backward block stays inside the default limit (no head
+// builds a hidden width near it: 128 everywhere in the reference); the merge block may raise its limit up to POOL_MERGE_LDS_MAX.
+constexpr size_t POOL_LDS_DEFAULT = 64 * 1024, POOL_MERGE_LDS_MAX = 150 * 1024;
+size_t pool_backward_lds_bytes(int dim, int hid) { return ((size_t)dim + 4 * ((size_t)hid + 4)) * sizeof(float); }
+size_t pool_merge_lds_bytes(int64_t N, int dim) {
+  const size_t nb = (size_t)((N + POOL_CHUNK - 1) / POOL_CHUNK);
+  return (((nb + 3) & ~(size_t)3) + dim) * sizeof(float) + (size_t)8 * 128 * sizeof(float4);
+}
+bool pool_merge_fits(int64_t N, int dim) { return pool_merge_lds_bytes(N, dim) <= POOL_MERGE_LDS_MAX; }
+bool pool_backward_fits(int dim, int hid) { return pool_backward_lds_bytes(dim, hid) <= POOL_LDS_DEFAULT; }
+
 // d wc [hid] and d bc [1] come out as dwcb [hid + 4] (d bc at [hid]); part: ceil(N / 32) * (hid + 4) floats
 hipError_t launch_pool_backward(const float* y, const float* hid_a, const float* hid_b, const float* wc, const float* attn,
                                 const float* pooled, const float* d_pooled, const float* d_attn, const float* d_raw,
                                 const float* c_ext, float* dy, float* dhid_a, float* dhid_b, float* dwcb, float* part, int N,
                                 int dim, int hid, hipStream_t st) {
   const int nb = (N + POOL_BWD_ROWS - 1) / POOL_BWD_ROWS;
-  const size_t lds = ((size_t)dim + 4 * (hid + 4)) * sizeof(float);
+  const size_t lds = pool_backward_lds_bytes(dim, hid);
+  if (lds > POOL_LDS_DEFAULT) return hipErrorInvalidValue;      // (the C ABI refuses these shapes before it gets here)
   pool_backward_kernel<<<dim3(nb), dim3(256), lds, st>>>(y, hid_a, hid_b, wc, attn, pooled, d_pooled, d_attn, d_raw, c_ext, dy,
                                                          dhid_a, dhid_b, part, N, dim, hid);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   return launch_reduce_partials(part, dwcb, nb, (size_t)hid + 4, st);
 }
+
 size_t pool_backward_part_floats(int N, int hid) { return (size_t)((N + POOL_BWD_ROWS - 1) / POOL_BWD_ROWS) * (hid + 4); }
 
 hipError_t launch_pool_partial(const float* y, const float* hid_a, const float* hid_b, const float* wc,
@@ -306,10 +319,10 @@ hipError_t launch_pool_merge(const float* part, const float* a_raw, const float*
                              float* pooled, float* logits, float* attn, int no_norm, int N, int dim,
                              int n_classes, hipStream_t st) {
   const int nb = (N + POOL_CHUNK - 1) / POOL_CHUNK;
-  const size_t lds = ((size_t)((nb + 3) & ~3) + dim) * sizeof(float) + (size_t)8 * 128 * sizeof(float4);
-  if (lds > 150 * 1024) return hipErrorInvalidValue;
+  const size_t lds = pool_merge_lds_bytes(N, dim);
+  if (lds > POOL_MERGE_LDS_MAX) return hipErrorInvalidValue;    // (the C ABI refuses these shapes before it gets here)
   auto kern = pool_merge_kernel;
-  if (lds > 64 * 1024)
+  if (lds > POOL_LDS_DEFAULT)
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   kern<<<dim3(1), dim3(1024), lds, st>>>(part, a_raw, pred_w, pred_b, pooled, logits, attn, no_norm, N, dim,
                                          n_classes, nb);

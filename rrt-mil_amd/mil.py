@@ -154,11 +154,14 @@ class _AttnPool(torch.autograd.Function):
 
 def lib_attn_pool(x, hid_a, hid_b, lin_c):
     """(1, N, D) bag x and its hidden rows (1, N, H) through the HIP pooling when it applies (one bag, a plain final
-    nn.Linear(H, 1), H % 4 == 0, D % 32 == 0, fp32); None otherwise (the caller keeps the torch ops)."""
+    nn.Linear(H, 1), H % 4 == 0, D % 32 == 0, fp32, a shape inside the kernels' LDS limits); None otherwise (the caller keeps the torch ops)."""
     ok = (type(lin_c) is nn.Linear and lin_c.out_features == 1 and not lin_c._forward_hooks and not lin_c._forward_pre_hooks
           and x.is_cuda and x.dim() == 3 and x.size(0) == 1 and x.dtype == torch.float32 and x.size(1) > 0
           and lin_c.weight.device == x.device and lin_c.weight.dtype == torch.float32
-          and hid_a.shape[-1] % 4 == 0 and x.shape[-1] % 32 == 0 and x.size(1) <= 1000000)
+          and hid_a.shape[-1] % 4 == 0 and x.shape[-1] % 32 == 0 and x.size(1) <= 1000000
+          # (the LDS of the backward block and of the merge block, as rrt_attn_pool_workspace_size checks them)
+          and 4 * (x.shape[-1] + 4 * (hid_a.shape[-1] + 4)) <= 64 * 1024
+          and 4 * ((((x.size(1) + 31) // 32 + 3) & ~3) + x.shape[-1]) + 16 * 1024 <= 150 * 1024)
     if not ok:
         return None
     pooled, attn, a_raw = _AttnPool.apply(x[0], hid_a[0], hid_b[0] if hid_b is not None else None, lin_c.weight, lin_c.bias)

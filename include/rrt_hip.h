@@ -1247,6 +1247,25 @@ typedef struct rrt_mask_stage {
 int rrt_mask_select_workspace_size(int64_t n, int32_t n_stages, size_t *bytes);
 int rrt_mask_select_f32(const float *a, int64_t n, const rrt_mask_stage *stages, int32_t n_stages, int32_t invert,
                         int64_t *ids, int64_t *count, uint8_t *mask, void *workspace, size_t workspace_bytes, void *stream);
+/* rrt_mask_select_vote_f32: the same selection from the per-head attention rows of a multi-head teacher, a [heads, n] row-major
+ * (network.py:497-508, msa_fusion='vote': a topk per head, the votes, a topk of the votes with the same k -- as ONE call).
+ *  Head order  each head orders the n tokens by its own row under rrt_mask_select_f32's rule (descending if largest, equal
+ *              values: the lower index first, -0.0 == +0.0, NaN greatest); a head's candidates are the first k of that order.
+ *  Vote        vote[i] = the number of heads that hold token i among their candidates, 0..heads.
+ *  Fused order the tokens by vote descending; EQUAL VOTES: THE LOWER INDEX FIRST (torch.topk on the integer votes leaves their
+ *              order unspecified, and with two heads nearly every decisive vote is a tie).  The stage's candidates are the first
+ *              k of the fused order, 1 <= k <= n; the candidate at position j is selected iff pick == NULL or pick[j] != 0.
+ *  Result      union over the stages, invert, ids, count (DEVICE memory) and mask exactly as in rrt_mask_select_f32.  With
+ *              heads == 1 and pick == NULL the outputs are those of rrt_mask_select_f32, bit for bit.
+ *  The same inputs give the same bits; nothing visits the host; plain launches, integer arithmetic to fixed places, no
+ *  atomics; stream-ordered, re-entrant.  workspace: rrt_mask_select_vote_workspace_size(n, heads, n_stages) bytes (never less
+ *  for a larger n or for more heads), else RRT_E_WORKSPACE.  1 <= heads <= 16 and n <= 262144, above either RRT_E_UNSUPPORTED;
+ *  RRT_E_INVALID on NULL a / stages / ids / count / workspace, n < 1, heads < 1, n_stages outside 1..3, a k outside 1..n.
+ *  Every argument is checked before the first launch. */
+int rrt_mask_select_vote_workspace_size(int64_t n, int32_t heads, int32_t n_stages, size_t *bytes);
+int rrt_mask_select_vote_f32(const float *a, int64_t n, int32_t heads, const rrt_mask_stage *stages, int32_t n_stages,
+                             int32_t invert, int64_t *ids, int64_t *count, uint8_t *mask, void *workspace,
+                             size_t workspace_bytes, void *stream);
 int rrt_gather_rows_f32(const float *src, const int64_t *ids, float *dst, int64_t n_rows, int64_t n_src, int32_t dim,
                         void *stream);
 int rrt_scatter_rows_f32(const float *src, const int64_t *ids, float *dst, int64_t n_rows, int64_t n_dst, int32_t dim,

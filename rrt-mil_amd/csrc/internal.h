@@ -499,6 +499,14 @@ MaskSplit mask_select_split(int n);    // split * n <= min(MASK_SPLIT_MAX * n, M
 hipError_t launch_mask_select(const float* a, int n, const MaskStages& st, int invert, long long* ids, long long* count,
                               unsigned char* mask, unsigned* part_asc, unsigned* part_desc, unsigned char* kept, int* block_cnt,
                               int* block_off, hipStream_t stream);
+// vote fusion over heads: a [heads, n]; parts [heads, split, n], vote [n_stages, n], hist / off [n_stages, MASK_VOTE_VALUES,
+// blocks], tot [n_stages, MASK_VOTE_VALUES]; the rest as above
+constexpr int MASK_VOTE_MAX_HEADS = 16;
+constexpr int MASK_VOTE_VALUES = MASK_VOTE_MAX_HEADS + 1;      // a vote lies in 0..heads
+hipError_t launch_mask_select_vote(const float* a, int n, int heads, const MaskStages& st, int invert, long long* ids,
+                                   long long* count, unsigned char* mask, unsigned* part_asc, unsigned* part_desc,
+                                   unsigned char* vote, int* hist, int* off, int* tot, unsigned char* kept, int* block_cnt,
+                                   int* block_off, hipStream_t stream);
 hipError_t launch_gather_rows(const float* src, const long long* ids, float* dst, long long n_rows, long long n_src, int dim,
                               hipStream_t stream);
 hipError_t launch_scatter_rows(const float* src, const long long* ids, float* dst, long long n_rows, long long n_dst, int dim,

@@ -19,6 +19,16 @@
 //   4. mask_place_kernel  ids[0:count) = kept ascending, ids[count:n) = the others ascending (a kept token's place is its
 //                         block's offset + its prefix inside the block; a dropped token i sits at count + i - kept-before-i).
 // Same inputs, same bits: integer arithmetic and fixed places only, no atomics.
+//
+// Vote fusion over heads (rrt_mask_select_vote_f32, a [heads, n]) = six plain launches under the same rules:
+//   1. mask_rank_heads_kernel  the counting rank above with the head on blockIdx.z: parts [heads, split, n].
+//   2. mask_vote_kernel        vote[s, i] = the number of heads that hold token i among their first k_s (a byte, 0..heads), and
+//                              per block and stage the histogram of the heads + 1 vote values (wave ballots, summed in LDS).
+//   3. mask_vote_scan_kernel   one block per (stage, vote value): exclusive scan of that value's <= 1024 block counts and its total.
+//   4. mask_vote_flag_kernel   the fused order is "vote descending, lower index first": its keys are small integers, so a token's
+//                              place is (tokens of a greater vote) + (its vote in earlier blocks) + (its ballot prefix among the
+//                              equal votes of its block) -- no second O(n^2) pass.  Then mask_flag_kernel's test and outputs.
+//   5. / 6. mask_scan_kernel, mask_place_kernel as above.
 #include "internal.h"
 
 namespace {
@@ -62,10 +72,10 @@ __device__ __forceinline__ void count_tile(const unsigned* t, int cnt, unsigned 
   for (int j = c4; j < cnt; ++j) one(t[j], j);
 }
 
+// one block's 256 tokens against one chunk of the j range (the body of both rank kernels)
 template <bool ASC, bool DESC>
-__global__ __launch_bounds__(MS_BLOCK) void mask_rank_kernel(const float* __restrict__ a, int n, int chunk_len,
-                                                             unsigned* __restrict__ part_asc, unsigned* __restrict__ part_desc) {
-  __shared__ __attribute__((aligned(16))) unsigned tile[MS_TILE];
+__device__ __forceinline__ void rank_block(const float* __restrict__ a, int n, int chunk_len, unsigned* __restrict__ part_asc,
+                                           unsigned* __restrict__ part_desc, unsigned* tile /* LDS [MS_TILE], 16-byte aligned */) {
   const int i0 = blockIdx.x * MS_BLOCK, i = i0 + threadIdx.x;
   const unsigned ki = i < n ? order_key(a[i]) : 0u;
   const int j_begin = blockIdx.y * chunk_len, j_end = min(n, j_begin + chunk_len);
@@ -88,6 +98,13 @@ __global__ __launch_bounds__(MS_BLOCK) void mask_rank_kernel(const float* __rest
     if constexpr (ASC) part_asc[(size_t)blockIdx.y * n + i] = asc;
     if constexpr (DESC) part_desc[(size_t)blockIdx.y * n + i] = desc;
   }
+}
+
+template <bool ASC, bool DESC>
+__global__ __launch_bounds__(MS_BLOCK) void mask_rank_kernel(const float* __restrict__ a, int n, int chunk_len,
+                                                             unsigned* __restrict__ part_asc, unsigned* __restrict__ part_desc) {
+  __shared__ __attribute__((aligned(16))) unsigned tile[MS_TILE];
+  rank_block<ASC, DESC>(a, n, chunk_len, part_asc, part_desc, tile);
 }
 
 // the block's exclusive prefix of `flag` over its 256 threads (4 waves) and the block total, through ballots
@@ -167,6 +184,123 @@ __global__ __launch_bounds__(MS_BLOCK) void mask_place_kernel(const unsigned cha
   }
 }
 
+// ---- multi-head vote fusion (rrt_mask_select_vote_f32): the rank per head, then the fused order from small integer keys
+// the counting rank with the head on blockIdx.z: head h reads a[h, :], writes rows [h * split, (h + 1) * split) of the parts
+template <bool ASC, bool DESC>
+__global__ __launch_bounds__(MS_BLOCK) void mask_rank_heads_kernel(const float* __restrict__ a, int n, int chunk_len,
+                                                                   unsigned* __restrict__ part_asc, unsigned* __restrict__ part_desc) {
+  __shared__ __attribute__((aligned(16))) unsigned tile[MS_TILE];
+  const size_t h = blockIdx.z, rows = (size_t)h * gridDim.y * n;
+  rank_block<ASC, DESC>(a + h * n, n, chunk_len, part_asc + rows, part_desc + rows, tile);
+}
+
+// per wave, the number of lanes whose vote is v, for every v in 0..heads: cnt [waves][MASK_VOTE_VALUES] in LDS; returns the
+// lane's prefix among the equal votes of its own wave.  (vote < 0: the lane takes no part.)
+__device__ __forceinline__ int vote_wave_counts(int vote, int heads, int* cnt /* LDS [MS_BLOCK / 64][MASK_VOTE_VALUES] */) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int mine = 0;
+  for (int v = 0; v <= heads; ++v) {                            // block-uniform trip count
+    const unsigned long long b = __ballot(vote == v);
+    if (vote == v) mine = __popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) cnt[w * MASK_VOTE_VALUES + v] = __popcll(b);
+  }
+  return mine;
+}
+
+// vote[s, i] = #{heads h : rank_h(i) < k_s} in stage s's order, and the block's histogram of the heads + 1 vote values per stage:
+// hist [(s * MASK_VOTE_VALUES + v) * blocks + block]
+__global__ __launch_bounds__(MS_BLOCK) void mask_vote_kernel(const unsigned* __restrict__ part_asc, const unsigned* __restrict__ part_desc,
+                                                             int n, int split, int heads, MaskStages st,
+                                                             unsigned char* __restrict__ vote, int* __restrict__ hist) {
+  __shared__ int cnt[3][MS_BLOCK / 64][MASK_VOTE_VALUES];
+  const int i = blockIdx.x * MS_BLOCK + threadIdx.x;
+  int votes[3] = {-1, -1, -1};
+  if (i < n) {
+    for (int s = 0; s < st.n; ++s) votes[s] = 0;
+    for (int h = 0; h < heads; ++h) {
+      unsigned asc = 0, desc = 0;
+      for (int c = 0; c < split; ++c) {
+        const size_t at = ((size_t)h * split + c) * n + i;
+        if (st.any_asc) asc += part_asc[at];
+        if (st.any_desc) desc += part_desc[at];
+      }
+      for (int s = 0; s < st.n; ++s) votes[s] += (st.largest[s] ? desc : asc) < (unsigned)st.k[s];
+    }
+    for (int s = 0; s < st.n; ++s) vote[(size_t)s * n + i] = (unsigned char)votes[s];
+  }
+  for (int s = 0; s < st.n; ++s) vote_wave_counts(votes[s], heads, &cnt[s][0][0]);
+  __syncthreads();
+  for (int e = threadIdx.x; e < st.n * MASK_VOTE_VALUES; e += MS_BLOCK) {
+    const int s = e / MASK_VOTE_VALUES, v = e - s * MASK_VOTE_VALUES;
+    if (v <= heads) {
+      int t = 0;
+      for (int w = 0; w < MS_BLOCK / 64; ++w) t += cnt[s][w][v];
+      hist[(size_t)e * gridDim.x + blockIdx.x] = t;
+    }
+  }
+}
+
+// block (s, v) of n_stages * (heads + 1): exclusive scan over the nb <= 1024 blocks' counts of vote value v in stage s ->
+// off [(s * MASK_VOTE_VALUES + v) * nb + block], tot [s * MASK_VOTE_VALUES + v]
+__global__ __launch_bounds__(1024) void mask_vote_scan_kernel(const int* __restrict__ hist, int nb, int heads, int* __restrict__ off,
+                                                              int* __restrict__ tot) {
+  __shared__ int s[1024];
+  const int t = threadIdx.x;
+  const int e = (blockIdx.x / (heads + 1)) * MASK_VOTE_VALUES + blockIdx.x % (heads + 1);
+  const int own = t < nb ? hist[(size_t)e * nb + t] : 0;
+  s[t] = own;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {
+    const int v = t >= d ? s[t - d] : 0;
+    __syncthreads();
+    s[t] += v;
+    __syncthreads();
+  }
+  if (t < nb) off[(size_t)e * nb + t] = s[t] - own;
+  if (t == 1023) tot[e] = s[1023];
+}
+
+// a token's place in stage s's fused order (vote descending, equal votes: lower index first) =
+//   #{tokens of a greater vote} + #{tokens of its vote in earlier blocks} + its prefix among the equal votes of its block;
+// then mask_flag_kernel's test and outputs
+__global__ __launch_bounds__(MS_BLOCK) void mask_vote_flag_kernel(const unsigned char* __restrict__ vote, const int* __restrict__ off,
+                                                                  const int* __restrict__ tot, int n, int heads, MaskStages st,
+                                                                  int invert, unsigned char* __restrict__ kept,
+                                                                  unsigned char* __restrict__ mask, int* __restrict__ block_cnt) {
+  __shared__ int cnt[3][MS_BLOCK / 64][MASK_VOTE_VALUES];
+  __shared__ int base[3][MASK_VOTE_VALUES];
+  __shared__ int wave_tot[MS_BLOCK / 64];
+  const int i = blockIdx.x * MS_BLOCK + threadIdx.x, w = threadIdx.x >> 6;
+  for (int e = threadIdx.x; e < st.n * MASK_VOTE_VALUES; e += MS_BLOCK) {
+    const int s = e / MASK_VOTE_VALUES, v = e - s * MASK_VOTE_VALUES;
+    int above = 0;
+    for (int u = v + 1; u <= heads; ++u) above += tot[s * MASK_VOTE_VALUES + u];
+    base[s][v] = above;
+  }
+  int votes[3] = {-1, -1, -1}, in_wave[3] = {0, 0, 0};
+  for (int s = 0; s < st.n; ++s) {
+    if (i < n) votes[s] = min((int)vote[(size_t)s * n + i], heads);
+    in_wave[s] = vote_wave_counts(votes[s], heads, &cnt[s][0][0]);
+  }
+  __syncthreads();
+  bool keep = false;
+  if (i < n) {
+    bool sel = false;
+    for (int s = 0; s < st.n; ++s) {
+      const int v = votes[s];
+      int pos = base[s][v] + off[((size_t)s * MASK_VOTE_VALUES + v) * gridDim.x + blockIdx.x] + in_wave[s];
+      for (int u = 0; u < w; ++u) pos += cnt[s][u][v];
+      if (pos >= 0 && pos < st.k[s]) sel |= st.pick[s] == nullptr || st.pick[s][pos] != 0;
+    }
+    keep = invert ? sel : !sel;
+    kept[i] = keep;
+    if (mask) mask[i] = !keep;
+  }
+  int total;
+  block_prefix(keep, wave_tot, total);
+  if (threadIdx.x == 0) block_cnt[blockIdx.x] = total;
+}
+
 // ---- rows by index
 constexpr int ROWS_BLOCK = 256;
 
@@ -226,6 +360,36 @@ hipError_t launch_mask_select(const float* a, int n, const MaskStages& st, int i
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   mask_flag_kernel<<<m.blocks, MS_BLOCK, 0, stream>>>(part_asc, part_desc, n, m.split, st, invert, kept, mask, block_cnt);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  mask_scan_kernel<<<1, 1024, 0, stream>>>(block_cnt, m.blocks, block_off, count);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  mask_place_kernel<<<m.blocks, MS_BLOCK, 0, stream>>>(kept, n, block_off, count, ids);
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_select_vote(const float* a, int n, int heads, const MaskStages& st, int invert, long long* ids,
+                                   long long* count, unsigned char* mask, unsigned* part_asc, unsigned* part_desc,
+                                   unsigned char* vote, int* hist, int* off, int* tot, unsigned char* kept, int* block_cnt,
+                                   int* block_off, hipStream_t stream) {
+  const MaskSplit m = mask_select_split(n);
+  const dim3 grid(m.blocks, m.split, heads);
+  if (st.any_asc && st.any_desc)
+    mask_rank_heads_kernel<true, true><<<grid, MS_BLOCK, 0, stream>>>(a, n, m.chunk_len, part_asc, part_desc);
+  else if (st.any_asc)
+    mask_rank_heads_kernel<true, false><<<grid, MS_BLOCK, 0, stream>>>(a, n, m.chunk_len, part_asc, part_desc);
+  else
+    mask_rank_heads_kernel<false, true><<<grid, MS_BLOCK, 0, stream>>>(a, n, m.chunk_len, part_asc, part_desc);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  mask_vote_kernel<<<m.blocks, MS_BLOCK, 0, stream>>>(part_asc, part_desc, n, m.split, heads, st, vote, hist);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  mask_vote_scan_kernel<<<st.n * (heads + 1), 1024, 0, stream>>>(hist, m.blocks, heads, off, tot);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  mask_vote_flag_kernel<<<m.blocks, MS_BLOCK, 0, stream>>>(vote, off, tot, n, heads, st, invert, kept, mask, block_cnt);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   mask_scan_kernel<<<1, 1024, 0, stream>>>(block_cnt, m.blocks, block_off, count);

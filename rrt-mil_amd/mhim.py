@@ -18,7 +18,8 @@ What differs from the reference, on purpose:
   * equal scores go to the lower index; ``torch.topk`` leaves the order of ties unspecified.
   * dropout is drawn on the kept rows only (the reference draws it on all N rows, then gathers): the same distribution, other
     random numbers.
-Out of scope (NotImplementedError at construction): ``baseline='selfattn'`` and ``mlp_dim != 512``.
+Out of scope here (NotImplementedError at construction): ``mlp_dim != 512``, and ``baseline='selfattn'``, which is the
+sibling module ``rrt_mil_amd.mhim_sattn``.
 """
 import ctypes as C
 import warnings
@@ -34,9 +35,9 @@ from ._head import BagHead
 from .attmil import attn_tail, initialize_weights
 from .mil import lib_attn_pool, lib_linear
 
-_NO_SELFATTN = ("rrt_mil_amd.MHIM covers baseline='attn' (the gated-ABMIL baseline of Survival/main.py); baseline='selfattn' is "
-                "not implemented: its per-head attention rows (a 3-D attn) are fused by ranking integer vote counts -- all ties "
-                "-- and need the attention of a teacher that runs with dropout on")
+_NO_SELFATTN = ("rrt_mil_amd.mhim.MHIM covers baseline='attn' (the gated-ABMIL baseline of Survival/main.py); baseline='selfattn' "
+                "-- the TransMIL-style baseline, whose per-head attention rows (a 3-D attn) are fused by vote -- is not "
+                "implemented in this module: it is rrt_mil_amd.mhim_sattn (the same class names)")
 
 
 def cosine_scheduler(base_value, final_value, epochs, niter_per_ep, warmup_epochs=0, start_warmup_value=0):
@@ -411,9 +412,11 @@ class MHIM(BagHead, nn.Module):
 class PURE_MHIM(nn.Module):
     """network.py:662-668: the unmasked baseline whose checkpoint initialises a teacher"""
 
+    _MHIM = None     # the MHIM class to build (mhim_sattn's subclass names its own)
+
     def __init__(self, input_dim=1024, mlp_dim=512, n_classes=2, baseline='attn'):
         super().__init__()
-        self.model = MHIM(select_mask=False, input_dim=input_dim, mlp_dim=mlp_dim, n_classes=n_classes, baseline=baseline)
+        self.model = (self._MHIM or MHIM)(select_mask=False, input_dim=input_dim, mlp_dim=mlp_dim, n_classes=n_classes, baseline=baseline)
 
     def forward(self, x):
         return self.model.pure(x)
@@ -423,13 +426,15 @@ class MHIM_MIL(nn.Module):
     """network.py:671-722: student + momentum teacher.  ``model(x, i=step)`` in train() -> (logits (1, C), cls_loss);
     ``model(x)`` in eval() -> logits; ``update_teacher(step)`` after the optimiser step."""
 
+    _MHIM = None     # as PURE_MHIM._MHIM
+
     def __init__(self, num_epoch, niter_per_ep, teacher_init=None, mm=0.9999, mm_sche=True, **kwargs):
         super().__init__()
         self.mm = mm
         kwargs['mrh_sche'] = cosine_scheduler(kwargs['mask_ratio_h'], 0., epochs=num_epoch, niter_per_ep=niter_per_ep)
         self.mm_sche = cosine_scheduler(self.mm, 1., epochs=num_epoch, niter_per_ep=niter_per_ep,
                                         start_warmup_value=1.) if mm_sche else None
-        self.student = MHIM(**kwargs)
+        self.student = (self._MHIM or MHIM)(**kwargs)
         self.teacher = deepcopy(self.student)
         if teacher_init is not None:
             # a baseline checkpoint: the whole teacher, and the student's embedding (what loads, loads: strict=False, and a

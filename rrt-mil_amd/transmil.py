@@ -286,15 +286,19 @@ class NystromAttention(HeadState, nn.Module):
                                                              ws.data_ptr(), ws.numel(), st), "rrt_nystrom_attention_batched_f32")
         return y
 
-    def attention_row(self, x, row=0):
+    def attention_row(self, x, row=0, in_train=False):
         """x (1, n, dim), ``row`` in [0, n) -> (y (1, n, dim), attn (1, heads, n)): ``forward(x)``, bit for bit, and row
         ``row`` of the Nystrom-approximated attention matrix over the n tokens (the reference's ``return_attn=True`` is row 0
         without column 0 when n % 256 == 0; at other n it reads a zero pad row, here the row is always the token's own).
         One rrt_nystrom_attention_row_f32 call; softmax(ql k^T) is never materialised.  Inference only: ``eval()`` under
         ``torch.no_grad()``.  Not a probability vector: the front pad keys keep their share, so the row does not sum to 1,
-        and entries can be negative (the pseudo-inverse is an approximation)."""
+        and entries can be negative (the pseudo-inverse is an approximation).
+
+        ``in_train=True`` lifts the ``eval()`` condition (not the ``torch.no_grad()`` one): the row does not depend on the
+        output dropout, so a momentum teacher that runs in ``train()`` may read it.  ``y`` is then the result BEFORE
+        ``to_out``'s Dropout, which the caller applies (mhim_sattn.SAttention does)."""
         _no_cpu(x, "NystromAttention")
-        _no_map_with_graph(self, x, self.training and self._dropout > 0., "NystromAttention.attention_row")
+        _no_map_with_graph(self, x, self.training and self._dropout > 0. and not in_train, "NystromAttention.attention_row")
         if x.dim() != 3 or x.shape[0] != 1:
             raise ValueError(f"NystromAttention.attention_row expects (1, n, dim) -- it keeps b = 1, batch > 1 is "
                              f"forward_batch() only -- got {tuple(x.shape)}")

@@ -1271,6 +1271,82 @@ int rrt_gather_rows_f32(const float *src, const int64_t *ids, float *dst, int64_
 int rrt_scatter_rows_f32(const float *src, const int64_t *ids, float *dst, int64_t n_rows, int64_t n_dst, int32_t dim,
                          void *stream);
 
+/* ---- DTFD-MIL (Survival/models/DTFD/network.py): the double-tier head.  Tier 1 splits the bag into pseudo-bags, pools each
+ * with its own softmax attention and picks, per pseudo-bag, the rows with the highest and the lowest class-activation
+ * probability; tier 2 is a gated attention pool + classifier over the distilled rows.
+ *
+ * rrt_gate_scores_f32: a [n_tokens]: a_n = c_w . (hid_a[n] * hid_b[n]) + c_b, hid_* [n_tokens, hidden]; hid_b and c_b may be
+ *  NULL.  The arithmetic of rrt_attn_pool_f32's a_raw, bit for bit.  hidden % 4 == 0, n_tokens <= 1e6.
+ *
+ * rrt_segment_pool_f32: mid [n_tokens, dim], a [n_tokens] scores, perm [n_tokens] int64 (NULL = the identity) the order in
+ *  which the rows are dealt to the n_groups groups, cls_w [n_classes, dim] the classifier's weight (no bias: get_cam_1d).
+ *  Groups     as np.array_split: q = n_tokens / n_groups, r = n_tokens % n_groups; the first r groups hold q + 1 consecutive
+ *             positions of perm, the others q.
+ *  Per group  w_i = softmax over the group of a_i;  pooled_g = sum_i w_i mid_i;  p_i = softmax_c(w_i * (mid_i . cls_w_c))[C - 1].
+ *  Selection  sel [n_groups, 2] int64 = the ORIGINAL row indices of the group's highest and lowest p, in that order.  Among
+ *             equal p the LOWER POSITION IN GROUP ORDER wins, at both ends; -0 == +0; a NaN p is never selected; a group
+ *             whose every p is NaN selects its first member at both ends; a group of one selects that member twice.
+ *  Outputs    pooled [n_groups, dim], sel; optional (NULL: not wanted) attn [n_tokens] = w and p [n_tokens], both written at
+ *             the original row index.  A perm entry outside [0, n_tokens) is never dereferenced: its row counts as NaN.
+ *  fp32 with accurate expf whatever mode the caller's GEMMs run in; every sum has a fixed order (same inputs, same bits); no
+ *  atomics; nothing visits the host; stream-ordered, re-entrant.
+ * rrt_segment_pool_backward_f32: the pooling's adjoint.  With c_g = pooled_g . d_pooled_g:  d_mid_i = w_i d_pooled_g and
+ *  d_a_i = w_i (mid_i . d_pooled_g - c_g), written at the original row indices (every row belongs to one group).  The
+ *  selection is an integer output without an adjoint: what reaches mid through the selected rows is the caller's
+ *  (rrt_scatter_rows_f32, or torch's index_select).  `workspace` is the one the forward call with the same mid / a / perm /
+ *  sizes left behind: the groups' (m_g, l_g) = (max score, softmax denominator) are its first 2 * n_groups floats.
+ * Limits (RRT_E_UNSUPPORTED from the size query and from the calls alike, before anything is launched): dim % 32 == 0,
+ *  dim <= 2048, 1 <= n_classes <= 8, 1 <= n_groups <= 64, n_groups <= n_tokens <= 1e6 (the reference tolerates
+ *  n_tokens < group -- empty chunks add no rows --, this library refuses it and says so).  RRT_E_INVALID on NULL / non-positive
+ *  arguments or pointers that are not 16-byte aligned, RRT_E_WORKSPACE below rrt_segment_pool_workspace_size bytes. */
+int rrt_segment_pool_workspace_size(int64_t n_tokens, int32_t dim, int32_t n_classes, int32_t n_groups, size_t *bytes);
+int rrt_gate_scores_f32(const float *hid_a, const float *hid_b, const float *c_w, const float *c_b, float *a,
+                        int64_t n_tokens, int32_t hidden, void *stream);
+int rrt_segment_pool_f32(const float *mid, const float *a, const int64_t *perm, const float *cls_w, float *pooled,
+                         int64_t *sel, float *attn, float *p, int64_t n_tokens, int32_t dim, int32_t n_classes,
+                         int32_t n_groups, void *workspace, size_t workspace_bytes, void *stream);
+int rrt_segment_pool_backward_f32(const float *mid, const float *a, const int64_t *perm, const float *pooled,
+                                  const float *d_pooled, float *d_mid, float *d_a, int64_t n_tokens, int32_t dim,
+                                  int32_t n_groups, void *workspace, size_t workspace_bytes, void *stream);
+
+/* DTFD.test_forward as one call (eval, one bag, one stream): x [n_tokens, input_dim] -> fc1 (no bias) + act -> RRTEncoder
+ * over the whole bag (has_rrt) -> the two gate Linears tanh / sigmoid (enc.compute's arithmetic, as the
+ * RRT_BAGPOOL_ATTN_GATED tail) -> rrt_gate_scores_f32 -> rrt_segment_pool_f32 over perm -> the distilled rows
+ * (rrt_gather_rows_f32 by the ids the selection wrote) -> tier 2 (the path behind rrt_pool_predict_f32: gated, tanh) ->
+ * logits [n_classes].  sigmoid / cumprod of the logits stay with the caller.  Nothing visits the host.
+ *   RRT_DTFD_MAXMINS  tier 2 sees [mid[imax_g], mid[imin_g]] for g = 0 .. group - 1   (2 * group rows)
+ *   RRT_DTFD_MAXS     mid[imax_g]                                                      (group rows)
+ *   RRT_DTFD_AFS      pooled_g                                                         (group rows)
+ * Optional outputs (NULL: not wanted): sel [group, 2] int64, p [n_tokens] the CAM probability of every row (the heat map).
+ * Limits: those of the heads' front (rrt_bagmil_forward_f32), of rrt_segment_pool_f32 and of rrt_pool_predict_f32. */
+enum { RRT_DTFD_MAXMINS = 0, RRT_DTFD_MAXS = 1, RRT_DTFD_AFS = 2 };
+typedef struct rrt_dtfd_desc {
+  rrt_encoder_desc enc;    /* has_rrt = 0: only dim (= 512 in the reference) and compute are read */
+  int32_t input_dim;       /* patch feature width (multiple of 32) */
+  int32_t emb_act;         /* RRT_ACT_RELU / RRT_ACT_GELU (RRT_ACT_NONE is accepted) */
+  int32_t has_rrt;
+  int32_t n_classes;       /* 1..8 */
+  int32_t hidden;          /* D of both Attention blocks: 128 in the reference (multiple of 4) */
+  int32_t group;           /* pseudo-bags, 1..64 */
+  int32_t distill;         /* RRT_DTFD_* */
+} rrt_dtfd_desc;
+typedef struct rrt_dtfd_weights {
+  rrt_encoder_weights enc;
+  const float *emb_w;                  /* dimReduction.fc1.weight              [dim, input_dim] (no bias) */
+  const float *att_v_w, *att_v_b;      /* attention.attention_V.0              [hidden, dim], [hidden] */
+  const float *att_u_w, *att_u_b;      /* attention.attention_U.0              [hidden, dim], [hidden] */
+  const float *att_w_w, *att_w_b;      /* attention.attention_weights          [1, hidden], [1] */
+  const float *cls_w;                  /* classifier.fc.weight                 [n_classes, dim] (its bias plays no part in eval) */
+  const float *u_v_w, *u_v_b;          /* UClassifier.attention.attention_V.0  [hidden, dim], [hidden] */
+  const float *u_u_w, *u_u_b;          /* UClassifier.attention.attention_U.0 */
+  const float *u_w_w, *u_w_b;          /* UClassifier.attention.attention_weights [1, hidden], [1] */
+  const float *u_fc_w, *u_fc_b;        /* UClassifier.classifier.fc            [n_classes, dim], [n_classes] */
+} rrt_dtfd_weights;
+int rrt_dtfd_workspace_size(const rrt_dtfd_desc *desc, int64_t n_tokens, size_t *bytes);
+int rrt_dtfd_forward_f32(const rrt_dtfd_desc *desc, const rrt_dtfd_weights *w, const float *x, const int64_t *perm,
+                         float *logits, int64_t *sel, float *p, int64_t n_tokens, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,8 +39,10 @@ from .mean_max import MaxMIL, MeanMIL  # noqa: F401,E402
 from . import mhim  # noqa: F401,E402  (mhim.DAttention / AttentionGated: the MHIM file's variants keep their module's namespace)
 from .mhim import MHIM, MHIM_MIL, PURE_MHIM  # noqa: F401,E402
 from . import mhim_sattn  # noqa: F401,E402  (baseline='selfattn': the same class names, inside the module)
+from . import dtfd  # noqa: F401,E402  (dtfd.Attention / DimReduction / ...: the DTFD file's blocks keep their module's namespace)
+from .dtfd import DTFD  # noqa: F401,E402
 from .encoder import (CrossRegionAttntion, InnerAttention, RegionAttntion, RRTEncoder,  # noqa: F401
                       TransLayer, initialize_weights)
 
-__all__ = ["RRTEncoder", "RRTMIL", "CLAM_SB", "CLAM_MB", "MILNet", "DSMIL", "TransMIL", "NystromAttention", "ABMIL", "GatedABMIL", "IBMIL", "MeanMIL", "MaxMIL", "MHIM", "MHIM_MIL", "PURE_MHIM", "mhim", "mhim_sattn", "DAttention", "TransLayer", "RegionAttntion", "CrossRegionAttntion", "InnerAttention",
+__all__ = ["RRTEncoder", "RRTMIL", "CLAM_SB", "CLAM_MB", "MILNet", "DSMIL", "TransMIL", "NystromAttention", "ABMIL", "GatedABMIL", "IBMIL", "MeanMIL", "MaxMIL", "MHIM", "MHIM_MIL", "PURE_MHIM", "mhim", "mhim_sattn", "DTFD", "dtfd", "DAttention", "TransLayer", "RegionAttntion", "CrossRegionAttntion", "InnerAttention",
            "initialize_weights", "geometry", "sharding", "synth", "device_error"]

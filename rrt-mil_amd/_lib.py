@@ -144,6 +144,17 @@ class TransmilGrads(C.Structure):
                 ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p)]
 
 
+class DtfdDesc(C.Structure):
+    _fields_ = [("enc", EncoderDesc)] + [(n, C.c_int32) for n in (
+        "input_dim", "emb_act", "has_rrt", "n_classes", "hidden", "group", "distill")]
+
+
+class DtfdWeights(C.Structure):
+    _fields_ = [("enc", EncoderWeights)] + [(n, C.c_void_p) for n in (
+        "emb_w", "att_v_w", "att_v_b", "att_u_w", "att_u_b", "att_w_w", "att_w_b", "cls_w", "u_v_w", "u_v_b", "u_u_w", "u_u_b",
+        "u_w_w", "u_w_b", "u_fc_w", "u_fc_b")]
+
+
 class MaskStage(C.Structure):
     """rrt_mask_stage: the `k` first tokens by score (descending if `largest`), of which `pick` (device [k] uint8, or None =
     all of them) says which are selected"""
@@ -398,6 +409,16 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rrt_gather_rows_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
     "rrt_scatter_rows_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
+    # DTFD-MIL: scores, the segmented pool + CAM selection and its adjoint, test_forward as one call
+    "rrt_segment_pool_workspace_size": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_gate_scores_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_void_p]),
+    "rrt_segment_pool_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                                          C.c_void_p]),
+    "rrt_segment_pool_backward_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                                                   C.c_void_p]),
+    "rrt_dtfd_workspace_size": (C.c_int, [C.POINTER(DtfdDesc), C.c_int64, C.POINTER(C.c_size_t)]),
+    "rrt_dtfd_forward_f32": (C.c_int, [C.POINTER(DtfdDesc), C.POINTER(DtfdWeights)] + [C.c_void_p] * 5 +
+                             [C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32X3 = 0, 1, 2, 3
@@ -406,6 +427,8 @@ EPEG_ATTN, EPEG_VALUE_BF, EPEG_VALUE_AF = 0, 1, 2
 MASK_SELECT_MAX_N = 262144               # rrt_mask_select_f32's largest bag
 MASK_VOTE_MAX_HEADS = 16                 # rrt_mask_select_vote_f32's most heads
 BAGPOOL_MEAN, BAGPOOL_MAX, BAGPOOL_ATTN, BAGPOOL_ATTN_GATED, BAGPOOL_ATTN_DECONF = range(5)     # rrt_bagmil_desc.pool
+DTFD_MAXMINS, DTFD_MAXS, DTFD_AFS = range(3)      # rrt_dtfd_desc.distill
+SEGMENT_POOL_MAX_GROUPS = 64                      # rrt_segment_pool_f32's most groups
 
 PLAN_FUSED, PLAN_FUSED_PROJ, PLAN_FUSED16, PLAN_FUSED_X3, PLAN_CRMSA_PARTS, PLAN_ATTN_HD = 1, 2, 4, 8, 16, 32     # rrt_encoder_plan flags
 # rrt_linear_plan / rrt_debug_linear_f32 (enums in include/rrt_hip.h)

@@ -1404,14 +1404,15 @@ namespace {
 
 // ---- the front every head around the encoder shares: patch_to_emb (Linear + activation in the GEMM epilogue) -> the
 // encoder, where the head has one.  rrt_mil_desc / rrt_clam_desc / rrt_dsmil_desc each hold these fields.
-struct HeadFront {
-  const rrt_encoder_desc* enc;   // (enc->dim is the embedding width whether or not there is an encoder)
-  int input_dim, emb_act, has_rrt;
-  int input16;                   // RRTMIL: the caller's features ARE the 16-bit operand (RRT_COMPUTE_BF16 / F16), else 0
-};
+// (struct HeadFront: api_internal.h)
 HeadFront head_front(const rrt_mil_desc* d) { return HeadFront{&d->enc, d->input_dim, d->emb_act, 1, d->input16}; }
 HeadFront head_front(const rrt_clam_desc* d) { return HeadFront{&d->enc, d->input_dim, d->emb_act, d->has_rrt, 0}; }
 HeadFront head_front(const rrt_dsmil_desc* d) { return HeadFront{&d->enc, d->input_dim, d->emb_act, d->has_rrt, 0}; }
+
+}  // namespace
+
+// what api_dtfd.hip builds its one-call forward from as well (declared in api_internal.h): the shared front and the ABMIL tail
+namespace rrt_api {
 
 // F32X3 concerns the R-MSA layers' big products only (encoder_forward): the GEMMs around the encoder are exact fp32
 int gemm_precision(int compute) { return compute == RRT_COMPUTE_F32X3 ? RRT_COMPUTE_F32 : compute; }
@@ -1434,13 +1435,7 @@ int check_head_front(const HeadFront& f, int64_t N) {
 // patch_to_emb's weight and, with pool16_hidden > 0, the encoder's output rows and two [pool16_hidden, dim] weights of the
 // head's first Linears (0: the head keeps fp32 operands, DSMIL).  The images are part of the size in every mode, so that a
 // workspace sized once serves a module that switches modes.
-struct HeadWs {
-  float *emb, *y;      // (y == emb without an encoder)
-  char *enc_ws, *head;
-  size_t enc_bytes;
-  uint16_t *x16, *w16, *y16, *pa16, *pb16;
-  size_t bytes;
-};
+// (struct HeadWs: api_internal.h)
 int carve_head(const HeadFront& f, int64_t N, size_t head_bytes, int pool16_hidden, char* base, HeadWs* out) {
   HeadWs w{};
   if (f.has_rrt) {
@@ -1522,10 +1517,7 @@ int head_front_forward(const HeadFront& f, const HeadWs& ws, const float* x, con
   return RRT_OK;
 }
 
-struct PoolWs {
-  float *hid_a, *hid_b, *a_raw, *part;
-  size_t bytes;
-};
+// (struct PoolWs: api_internal.h)
 PoolWs carve_pool(int64_t N, int dim, int hidden, int gated, char* base) {
   PoolWs w{};
   Arena a{base};
@@ -1560,8 +1552,8 @@ int check_attn_pool(int64_t N, int dim, int hidden) {
 int pool_predict(const float* y, const float* a_w, const float* a_b, const float* b_w, const float* b_b,
                  const float* c_w, const float* c_b, const float* pred_w, const float* pred_b, float* pooled,
                  float* logits, float* attn, int no_norm, int64_t N, int dim, int hidden, int act,
-                 int n_classes, int compute, const PoolWs& ws, hipStream_t st, const uint16_t* y16 = nullptr,
-                 const uint16_t* a_w16 = nullptr, const uint16_t* b_w16 = nullptr) {
+                 int n_classes, int compute, const PoolWs& ws, hipStream_t st, const uint16_t* y16, const uint16_t* a_w16,
+                 const uint16_t* b_w16) {
   LinearEpilogue ep{};
   ep.prec = compute;
   ep.bias = a_b;
@@ -1584,6 +1576,10 @@ int pool_predict(const float* y, const float* a_w, const float* a_b, const float
   RRT_TRY(launch_pool_partial(y, ws.hid_a, b_w ? ws.hid_b : nullptr, c_w, c_b, ws.a_raw, ws.part, (int)N, dim, hidden, st));
   return (int)launch_pool_merge(ws.part, ws.a_raw, pred_w, pred_b, pooled, logits, attn, no_norm, (int)N, dim, n_classes, st);
 }
+
+}  // namespace rrt_api
+
+namespace {
 
 int check_mil(const rrt_mil_desc* d, int64_t N) {
   if (!d) return RRT_E_INVALID;

@@ -48,4 +48,35 @@ int make_drop(float p, DropCfg* d);
 int encoder_tail_workspace_size(const rrt_encoder_desc* desc, int64_t n_tokens, size_t* bytes);
 int encoder_tail(const rrt_encoder_desc* desc, const rrt_encoder_weights* w, const float* x1, const float* x0, float* y,
                  int64_t n_tokens, void* workspace, size_t workspace_bytes, void* stream);
+
+// ---- the front every head around the encoder shares, and the ABMIL tail (defined in api.hip, where their comments are)
+struct HeadFront {
+  const rrt_encoder_desc* enc;   // (enc->dim is the embedding width whether or not there is an encoder)
+  int input_dim, emb_act, has_rrt;
+  int input16;                   // RRTMIL: the caller's features ARE the 16-bit operand (RRT_COMPUTE_BF16 / F16), else 0
+};
+struct HeadWs {
+  float *emb, *y;      // (y == emb without an encoder)
+  char *enc_ws, *head;
+  size_t enc_bytes;
+  uint16_t *x16, *w16, *y16, *pa16, *pb16;
+  size_t bytes;
+};
+struct PoolWs {
+  float *hid_a, *hid_b, *a_raw, *part;
+  size_t bytes;
+};
+int gemm_precision(int compute);
+int check_head_front(const HeadFront& f, int64_t N);
+int carve_head(const HeadFront& f, int64_t N, size_t head_bytes, int pool16_hidden, char* base, HeadWs* out);
+int head_front_forward(const HeadFront& f, const HeadWs& ws, const float* x, const float* emb_w, const float* emb_b,
+                       const rrt_encoder_weights* enc_w, const float* pool_a_w, const float* pool_b_w, int pool_hidden,
+                       float* y_out, bool tuning, int64_t N, void* stream, bool* p16);
+PoolWs carve_pool(int64_t N, int dim, int hidden, int gated, char* base);
+int check_pool(int64_t N, int dim, int hidden, int act, int n_classes);
+int pool_predict(const float* y, const float* a_w, const float* a_b, const float* b_w, const float* b_b, const float* c_w,
+                 const float* c_b, const float* pred_w, const float* pred_b, float* pooled, float* logits, float* attn,
+                 int no_norm, int64_t N, int dim, int hidden, int act, int n_classes, int compute, const PoolWs& ws,
+                 hipStream_t st, const uint16_t* y16 = nullptr, const uint16_t* a_w16 = nullptr,
+                 const uint16_t* b_w16 = nullptr);
 }  // namespace rrt_api

@@ -511,3 +511,17 @@ hipError_t launch_gather_rows(const float* src, const long long* ids, float* dst
                               hipStream_t stream);
 hipError_t launch_scatter_rows(const float* src, const long long* ids, float* dst, long long n_rows, long long n_dst, int dim,
                                hipStream_t stream);
+
+// ---- segment_pool.hip: DTFD-MIL's first tier -- pseudo-bag (np.array_split) softmax pooling through a permutation, the CAM
+// probability of every row and its argmax / argmin per group.  N >= G >= 1, dim % 32 == 0, dim <= 2048, 1 <= C <= 8.
+hipError_t launch_gate_scores(const float* hid_a, const float* hid_b, const float* wc, const float* bc, float* a, int N, int hid,
+                              hipStream_t stream);
+size_t segment_pool_parts(int N, int G);       // (group, chunk of POOL_CHUNK positions) partials: no chunk straddles two groups
+// ml [2 G] receives (m_g, l_g); part [parts, dim + 4]; z [N, C] in group-position order; ids (optional): the selected rows in
+// tier 2's gather layout, ids_stride 2 = [max_g, min_g] per group, 1 = [max_g]
+hipError_t launch_segment_pool(const float* mid, const float* a, const long long* perm, const float* cls_w, float* pooled,
+                               long long* sel, float* attn, float* p, float* ml, float* part, float* z, long long* ids,
+                               int ids_stride, int N, int dim, int C, int G, hipStream_t stream);
+hipError_t launch_segment_pool_backward(const float* mid, const float* a, const long long* perm, const float* pooled,
+                                        const float* d_pooled, const float* ml, float* d_mid, float* d_a, int N, int dim, int G,
+                                        hipStream_t stream);

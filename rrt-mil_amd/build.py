@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "librrt_hip.so")
 STAMP = os.path.join(HERE, "csrc", ".build_stamp")
 SOURCES = ["ln_partition.hip", "cast16.hip", "linear_f32.hip", "region_attn.hip", "region_attn_hd.hip", "rmsa_fused.hip", "rmsa_fused16.hip", "rmsa_pair16.hip", "rmsa_fused_x3.hip", "crmsa.hip", "epeg_variants.hip", "mil_pool.hip", "clam_pool.hip", "dsmil_pool.hip", "bag_pool.hip", "linear_bwd.hip", "ln_bwd.hip", "attn_bwd.hip", "crmsa_bwd.hip", "peg.hip", "nystrom.hip", "nystrom_bwd.hip", "nystrom_row.hip", "transmil_bwd.hip",
            "mask_select.hip", "segment_pool.hip", "api.hip", "api_nystrom.hip", "api_mask.hip", "api_dtfd.hip"]
-HEADERS = ["common.h", "internal.h", "api_internal.h", "fused16.h", "nystrom_tiles.h", os.path.join("..", "..", "include", "rrt_hip.h")]
+HEADERS = ["common.h", "internal.h", "api_internal.h", "fused16.h", "nystrom_tiles.h", "pool_core.h", os.path.join("..", "..", "include", "rrt_hip.h")]
 # -amdgpu-mfma-vgpr-form: gfx950 has one unified VGPR/AGPR file; keep MFMA accumulators in VGPRs so the
 # softmax / rescale VALU code does not shuttle them through v_accvgpr_read/write (hazard stalls).
 # -amdgpu-kernarg-preload-count: the leading kernel arguments (pointers, sizes: up to 16 dwords) arrive in SGPRs with the

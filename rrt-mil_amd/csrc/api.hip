@@ -1958,7 +1958,7 @@ int rrt_branch_pool_f32(const float* y, const float* hid_a, const float* hid_b, 
   if (!y || !hid_a || !c_w || !pooled || !a_raw) return RRT_E_INVALID;
   int rc = check_branch_pool(n_tokens, dim, hidden, n_branches);
   if (rc) return rc;
-  if (branch_pool_merge_lds((int)n_tokens, dim) > 150 * 1024) return unsupported("branch pool: bag too large for the merge block");
+  if (!pool_merge_fits(n_tokens, dim)) return unsupported("branch pool: bag too large for the merge block");
   if (!workspace || workspace_bytes < branch_pool_workspace(n_tokens, dim, hidden, n_branches)) return RRT_E_WORKSPACE;
   return (int)launch_branch_pool(y, hid_a, hid_b, c_w, c_b, nullptr, nullptr, pooled, nullptr, attn, a_raw, (float*)workspace, 0,
                                  0, (int)n_tokens, dim, hidden, n_branches, (hipStream_t)stream);
@@ -1971,7 +1971,7 @@ int rrt_branch_pool_backward_f32(const float* y, const float* hid_a, const float
   if (!y || !hid_a || !c_w || !attn || !pooled || !d_pooled || !dy || !dhid_a || !dwcb || (hid_b && !dhid_b)) return RRT_E_INVALID;
   int rc = check_branch_pool(n_tokens, dim, hidden, n_branches);
   if (rc) return rc;
-  if (branch_pool_backward_lds(dim, hidden, n_branches) > 150 * 1024)
+  if (branch_pool_backward_lds(dim, hidden, n_branches) > POOL_MERGE_LDS_MAX)
     return unsupported("branch pool backward: n_branches * (dim + 4 * hidden) floats exceed the block's LDS budget");
   if (!workspace || workspace_bytes < branch_pool_workspace(n_tokens, dim, hidden, n_branches)) return RRT_E_WORKSPACE;
   return (int)launch_branch_pool_backward(y, hid_a, hid_b, c_w, attn, pooled, d_pooled, d_raw, dy, dhid_a, dhid_b, dwcb,
@@ -2010,7 +2010,7 @@ int rrt_clam_forward_f32(const rrt_clam_desc* desc, const rrt_clam_weights* w, c
     if (desc->k_sample > 32) return unsupported("topk: k <= 32");
     if (n_tokens < desc->k_sample) return RRT_E_INVALID;
   }
-  if (branch_pool_merge_lds((int)n_tokens, desc->enc.dim) > 150 * 1024) return unsupported("branch pool: bag too large for the merge block");
+  if (!pool_merge_fits(n_tokens, desc->enc.dim)) return unsupported("branch pool: bag too large for the merge block");
   HeadWs hw;
   ClamWs cws;
   rc = carve_clam_head(desc, n_tokens, (char*)workspace, &hw, &cws);

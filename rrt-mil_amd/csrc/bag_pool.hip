@@ -16,7 +16,7 @@
 // Deconfounder (rrt_deconf_head_f32), one block, O(J (dim + V) + K V) work, FOLDED like the DSMIL bag stream:
 //     q = W_q pooled + b_q [J] ;  k_i . q = conf_i . (W_k^T q) + b_k . q   so k [K, J] is never formed;
 //     a = softmax_i(k_i . q / sqrt(J)) over the K confounders ;  cf = sum_i a_i conf_i ;  logits = head [pooled | cf] + b.
-#include "internal.h"
+#include "pool_core.h"
 
 namespace {
 
@@ -99,13 +99,7 @@ __global__ __launch_bounds__(1024) void mean_final_kernel(const float* __restric
     __syncthreads();
   }
   for (int j = wave; j < C; j += 16) {
-    float acc = 0.f;
-    for (int c = lane * 4; c < dim; c += 256) {
-      const float4 x = *(const float4*)(w + (size_t)j * dim + c);
-      const float4 p = *(const float4*)(s_mean + c);
-      acc += (x.x * p.x + x.y * p.y) + (x.z * p.z + x.w * p.w);
-    }
-    acc = wave_sum(acc);
+    const float acc = wave_row_dot(w + (size_t)j * dim, s_mean, dim, lane);
     if (lane == 0) logits[j] = acc + (b ? b[j] : 0.f);
   }
 }
@@ -165,13 +159,7 @@ __global__ __launch_bounds__(256) void deconf_head_kernel(const float* __restric
   for (int c = tid; c < dim; c += 256) s_p[c] = pooled[c];
   __syncthreads();
   for (int j = wave; j < J; j += 4) {
-    float acc = 0.f;
-    for (int c = lane * 4; c < dim; c += 256) {
-      const float4 x = *(const float4*)(q_w + (size_t)j * dim + c);
-      const float4 p = *(const float4*)(s_p + c);
-      acc += (x.x * p.x + x.y * p.y) + (x.z * p.z + x.w * p.w);
-    }
-    acc = wave_sum(acc) + (q_b ? q_b[j] : 0.f);
+    const float acc = wave_row_dot(q_w + (size_t)j * dim, s_p, dim, lane) + (q_b ? q_b[j] : 0.f);
     if (lane == 0) s_q[j] = acc;
   }
   __syncthreads();
@@ -189,13 +177,7 @@ __global__ __launch_bounds__(256) void deconf_head_kernel(const float* __restric
   }
   __syncthreads();
   for (int i = wave; i < K; i += 4) {
-    float acc = 0.f;
-    for (int v = lane * 4; v < V; v += 256) {
-      const float4 x = *(const float4*)(conf + (size_t)i * V + v);
-      const float4 u = *(const float4*)(s_u + v);
-      acc += (x.x * u.x + x.y * u.y) + (x.z * u.z + x.w * u.w);
-    }
-    acc = wave_sum(acc);
+    const float acc = wave_row_dot(conf + (size_t)i * V, s_u, V, lane);
     if (lane == 0) s_s[i] = (acc + s_beta) * scale;
   }
   __syncthreads();
@@ -220,18 +202,8 @@ __global__ __launch_bounds__(256) void deconf_head_kernel(const float* __restric
   __syncthreads();
   const size_t hs = (size_t)dim + V;
   for (int o = wave; o < C; o += 4) {
-    float acc = 0.f;
-    for (int c = lane * 4; c < dim; c += 256) {
-      const float4 x = *(const float4*)(head_w + o * hs + c);
-      const float4 p = *(const float4*)(s_p + c);
-      acc += (x.x * p.x + x.y * p.y) + (x.z * p.z + x.w * p.w);
-    }
-    for (int v = lane * 4; v < V; v += 256) {
-      const float4 x = *(const float4*)(head_w + o * hs + dim + v);
-      const float4 p = *(const float4*)(s_cf + v);
-      acc += (x.x * p.x + x.y * p.y) + (x.z * p.z + x.w * p.w);
-    }
-    acc = wave_sum(acc);
+    float acc = lane_row_dot(head_w + o * hs, s_p, dim, lane, 0.f);          // [pooled | cf]: one sum over both segments
+    acc = wave_sum(lane_row_dot(head_w + o * hs + dim, s_cf, V, lane, acc));
     if (lane == 0) logits[o] = acc + (head_b ? head_b[o] : 0.f);
   }
 }

@@ -6,12 +6,12 @@
 //     A[c, :] = softmax_n(s[c, :])           over the N tokens of the bag, per branch
 //     M[c, :] = sum_n A[c, n] y_n            [K, dim]
 //
-// Same online-softmax shape as mil_pool.hip: every POOL_CHUNK-token block emits (m, l, sum e^{s-m} y) -- here for every
+// The online softmax of pool_core.h: every POOL_CHUNK-token block emits (m, l, sum e^{s-m} y) -- here for every
 // branch -- and one merge block per branch rescales and adds them.  The point of the kernel is that a y row is read ONCE for
 // all K branches: the K float4 accumulators of a column lane live in registers (K = 8: 32 VGPRs), so CLAM_MB's n_classes
 // branches read y once, not n_classes times.  Nothing of size N x dim is written.  Every sum has a fixed order (no atomics): the
 // same inputs give the same bits, whatever else is in flight.
-#include "internal.h"
+#include "pool_core.h"
 
 namespace {
 
@@ -33,28 +33,15 @@ __global__ __launch_bounds__(256) void branch_partial_kernel(const float* __rest
 
   // ---- scores: one wave per token, the hidden row read once for the K score rows
   for (int t = wave; t < cnt; t += 4) {
-    const size_t row = (size_t)(n0 + t) * hid;
-    float acc[K];
+    float s[K];
+    gate_scores_row<K>(hid_a, hid_b, wc, (size_t)(n0 + t) * hid, hid, lane, s);
 #pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = 0.f;
-    for (int c = lane * 4; c < hid; c += 256) {
-      float4 h = *(const float4*)(hid_a + row + c);
-      if (hid_b) {
-        const float4 g = *(const float4*)(hid_b + row + c);
-        h.x *= g.x; h.y *= g.y; h.z *= g.z; h.w *= g.w;
-      }
+    for (int k = 0; k < K; ++k) s[k] += bc ? bc[k] : 0.f;
+    if (lane == 0) {
 #pragma unroll
       for (int k = 0; k < K; ++k) {
-        const float4 w = *(const float4*)(wc + (size_t)k * hid + c);
-        acc[k] += (h.x * w.x + h.y * w.y) + (h.z * w.z + h.w * w.w);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const float s = wave_sum(acc[k]) + (bc ? bc[k] : 0.f);
-      if (lane == 0) {
-        s_a[k][t] = s;
-        a_raw[(size_t)k * N + n0 + t] = s;
+        s_a[k][t] = s[k];
+        a_raw[(size_t)k * N + n0 + t] = s[k];
       }
     }
   }
@@ -76,52 +63,11 @@ __global__ __launch_bounds__(256) void branch_partial_kernel(const float* __rest
     out[(size_t)K * dim + K + tid] = l;
   }
 
-  // ---- weighted sums of the chunk's rows: thread = (row group rg of 2, float4 column lane of 128); every row's float4 is
-  //      loaded once and feeds the K branch accumulators
-  const int cl = tid & 127, rg = tid >> 7;
-  for (int cb = 0; cb < dim; cb += 512) {
-    const int c = cb + cl * 4;
-    float4 acc[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c < dim) {
-      for (int t0 = rg; t0 < cnt; t0 += 8) {          // 4 independent rows in flight
-        float4 v[4];
-        int tt[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int t = t0 + 2 * u;
-          const bool ok = t < cnt;
-          tt[u] = ok ? t : POOL_CHUNK - 1;              // (a row past the chunk: zero data; its weight is a finite number)
-          v[u] = ok ? *(const float4*)(y + (size_t)(n0 + t) * dim + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-#pragma unroll
-          for (int k = 0; k < K; ++k) {
-            const float e = s_e[k][tt[u]];
-            acc[k].x += e * v[u].x; acc[k].y += e * v[u].y; acc[k].z += e * v[u].z; acc[k].w += e * v[u].w;
-          }
-        }
-      }
-    }
-    if (rg == 1 && c < dim) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) red[k][cl] = acc[k];
-    }
-    __syncthreads();
-    if (rg == 0 && c < dim) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const float4 o = red[k][cl];
-        *(float4*)(out + (size_t)k * dim + c) = make_float4(acc[k].x + o.x, acc[k].y + o.y, acc[k].z + o.z, acc[k].w + o.w);
-      }
-    }
-    __syncthreads();
-  }
+  // ---- weighted sums of the chunk's rows (a row past the chunk meets s_e[k][31], which is 0 whenever cnt < 32)
+  chunk_weighted_rowsum<K>(y, s_e, red, out, n0, cnt, dim);
 }
 
-// One block per branch: global max / normaliser over the chunk partials, the pooled row, the normalised attention row and
+// One block per branch: the merge core over the chunk partials, then the normalised attention row and
 // the bag logits -- per_branch (CLAM_MB): logits[c] = cls_w[c] . M[c] + cls_b[c] by block c; otherwise (CLAM_SB, one branch)
 // logits[j] = cls_w[j] . M[0] + cls_b[j] for the n_classes rows of the classifier.
 __global__ __launch_bounds__(1024) void branch_merge_kernel(const float* __restrict__ part, const float* __restrict__ a_raw,
@@ -130,101 +76,22 @@ __global__ __launch_bounds__(1024) void branch_merge_kernel(const float* __restr
                                                             float* __restrict__ attn, int per_branch, int n_classes, int N,
                                                             int dim, int K, int nb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* s_scale = (float*)smem;                    // [nb] exp(m_b - M)
-  float* s_pool = s_scale + ((nb + 3) & ~3);        // [dim]
-  float4* s_red = (float4*)(s_pool + dim);          // [8 groups][128 column lanes]
-  __shared__ float s_w[16];
-  __shared__ float s_M, s_invL;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int br = blockIdx.x;
-  const size_t ps = bpart_stride(K, dim);
-  const float* pm = part + (size_t)K * dim + br;           // m of chunk b: pm[b * ps]; l: pm[b * ps + K]
-  const float* pv = part + (size_t)br * dim;
-
-  float m = -3.0e38f;
-  for (int b = tid; b < nb; b += 1024) m = fmaxf(m, pm[b * ps]);
-  m = wave_max(m);
-  if (lane == 0) s_w[wave] = m;
-  __syncthreads();
-  if (tid == 0) {
-    float M = s_w[0];
-    for (int w = 1; w < 16; ++w) M = fmaxf(M, s_w[w]);
-    s_M = M;
-  }
-  __syncthreads();
-  const float M = s_M;
-  float l = 0.f;
-  for (int b = tid; b < nb; b += 1024) {
-    const float sc = __expf(pm[b * ps] - M);
-    s_scale[b] = sc;
-    l += pm[b * ps + K] * sc;
-  }
-  l = wave_sum(l);
-  __syncthreads();                                  // s_w reuse
-  if (lane == 0) s_w[wave] = l;
-  __syncthreads();
-  if (tid == 0) {
-    float L = 0.f;
-    for (int w = 0; w < 16; ++w) L += s_w[w];
-    s_invL = 1.0f / L;
-  }
-  __syncthreads();
-  const float invL = s_invL;
-
-  // pooled[c] = invL * sum_b scale_b part[b][br][c] : thread = (chunk group of 8, float4 column lane of 128)
-  const int cl = tid & 127, grp = tid >> 7;
-  for (int cb = 0; cb < dim; cb += 512) {
-    const int c = cb + cl * 4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c < dim) {
-      for (int b0 = grp; b0 < nb; b0 += 32) {
-        float4 v[4];
-        float sc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int b = b0 + 8 * u;
-          const bool ok = b < nb;
-          sc[u] = ok ? s_scale[b] : 0.f;
-          v[u] = ok ? *(const float4*)(pv + b * ps + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          acc.x += sc[u] * v[u].x; acc.y += sc[u] * v[u].y; acc.z += sc[u] * v[u].z; acc.w += sc[u] * v[u].w;
-        }
-      }
-    }
-    s_red[grp * 128 + cl] = acc;
-    __syncthreads();
-    if (grp == 0 && c < dim) {
-      float4 a = s_red[cl];
-#pragma unroll
-      for (int q = 1; q < 8; ++q) {
-        const float4 o = s_red[q * 128 + cl];
-        a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
-      }
-      a.x *= invL; a.y *= invL; a.z *= invL; a.w *= invL;
-      *(float4*)(s_pool + c) = a;
-      if (pooled) *(float4*)(pooled + (size_t)br * dim + c) = a;
-    }
-    __syncthreads();
-  }
+  // m of chunk b: (part + K * dim + br)[b * ps], l: K floats further; its row for this branch: (part + br * dim) + b * ps
+  const PoolMerged p = pool_merge_core(part + (size_t)K * dim + br, K, part + (size_t)br * dim, bpart_stride(K, dim), nb, dim,
+                                       smem, pooled ? pooled + (size_t)br * dim : nullptr);
 
   // bag logits: one wave per classifier row
   if (logits) {
     const int j0 = per_branch ? br : 0, j1 = per_branch ? br + 1 : (br == 0 ? n_classes : 0);
     for (int j = j0 + wave; j < j1; j += 16) {
-      float acc = 0.f;
-      for (int c = lane * 4; c < dim; c += 256) {
-        const float4 w = *(const float4*)(cls_w + (size_t)j * dim + c);
-        const float4 p = *(const float4*)(s_pool + c);
-        acc += (w.x * p.x + w.y * p.y) + (w.z * p.z + w.w * p.w);
-      }
-      acc = wave_sum(acc);
+      const float acc = wave_row_dot(cls_w + (size_t)j * dim, p.s_pool, dim, lane);
       if (lane == 0) logits[j] = acc + (cls_b ? cls_b[j] : 0.f);
     }
   }
   if (attn) {
-    for (int n = tid; n < N; n += 1024) attn[(size_t)br * N + n] = __expf(a_raw[(size_t)br * N + n] - M) * invL;
+    for (int n = tid; n < N; n += 1024) attn[(size_t)br * N + n] = __expf(a_raw[(size_t)br * N + n] - p.M) * p.invL;
   }
 }
 
@@ -250,27 +117,15 @@ __global__ __launch_bounds__(256) void branch_backward_kernel(const float* __res
   __shared__ float s_c[K][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int accw = (int)bbwd_stride(K, hid);
-  float cpart[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    cpart[k] = 0.f;
-    for (int c = tid; c < dim; c += 256) {
-      const float v = d_pooled[(size_t)k * dim + c];
-      s_dp[k * dim + c] = v;
-      cpart[k] += v * pooled[(size_t)k * dim + c];
-    }
-  }
   for (int c = tid; c < 4 * accw; c += 256) s_acc[c] = 0.f;
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const float t = wave_sum(cpart[k]);
-    if (lane == 0) s_c[k][wave] = t;
-  }
+  for (int k = 0; k < K; ++k)
+    pool_backward_stage(d_pooled + (size_t)k * dim, pooled + (size_t)k * dim, s_dp + k * dim, s_c[k], dim);
   __syncthreads();
   float cc[K], dbc[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    cc[k] = (s_c[k][0] + s_c[k][1]) + (s_c[k][2] + s_c[k][3]);
+    cc[k] = pool_backward_c(s_c[k]);
     dbc[k] = 0.f;
   }
   float* myacc = s_acc + wave * accw;
@@ -422,7 +277,7 @@ hipError_t backward_k(const float* y, const float* hid_a, const float* hid_b, co
                       const float* pooled, const float* d_pooled, const float* d_raw, float* dy, float* dhid_a, float* dhid_b,
                       float* part, int N, int dim, int hid, int nb, size_t lds, hipStream_t st) {
   auto kern = branch_backward_kernel<K>;
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  pool_raise_lds_limit((const void*)kern, lds);
   kern<<<dim3(nb), dim3(256), lds, st>>>(y, hid_a, hid_b, wc, attn, pooled, d_pooled, d_raw, dy, dhid_a, dhid_b, part, N, dim, hid);
   return hipGetLastError();
 }
@@ -432,10 +287,6 @@ hipError_t backward_k(const float* y, const float* hid_a, const float* hid_b, co
 size_t branch_pool_part_floats(int N, int dim, int K) { return (size_t)((N + POOL_CHUNK - 1) / POOL_CHUNK) * bpart_stride(K, dim); }
 size_t branch_pool_backward_part_floats(int N, int hid, int K) {
   return (size_t)((N + BR_BWD_ROWS - 1) / BR_BWD_ROWS) * bbwd_stride(K, hid);
-}
-size_t branch_pool_merge_lds(int N, int dim) {
-  const int nb = (N + POOL_CHUNK - 1) / POOL_CHUNK;
-  return ((size_t)((nb + 3) & ~3) + dim) * sizeof(float) + (size_t)8 * 128 * sizeof(float4);
 }
 size_t branch_pool_backward_lds(int dim, int hid, int K) { return ((size_t)K * dim + 4 * bbwd_stride(K, hid)) * sizeof(float); }
 
@@ -452,10 +303,10 @@ hipError_t launch_branch_pool(const float* y, const float* hid_a, const float* h
     default: return hipErrorInvalidValue;
   }
   if (e != hipSuccess) return e;
-  const size_t lds = branch_pool_merge_lds(N, dim);
-  if (lds > 150 * 1024) return hipErrorInvalidValue;
+  const size_t lds = pool_merge_lds_bytes(nb, dim);
+  if (lds > POOL_MERGE_LDS_MAX) return hipErrorInvalidValue;
   auto kern = branch_merge_kernel;
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  pool_raise_lds_limit((const void*)kern, lds);
   kern<<<dim3(K), dim3(1024), lds, st>>>(part, a_raw, cls_w, cls_b, pooled, logits, attn, per_branch, n_classes, N, dim, K, nb);
   return hipGetLastError();
 }
@@ -466,7 +317,7 @@ hipError_t launch_branch_pool_backward(const float* y, const float* hid_a, const
                                        float* dhid_b, float* dwcb, float* part, int N, int dim, int hid, int K, hipStream_t st) {
   const int nb = (N + BR_BWD_ROWS - 1) / BR_BWD_ROWS;
   const size_t lds = branch_pool_backward_lds(dim, hid, K);
-  if (lds > 150 * 1024) return hipErrorInvalidValue;
+  if (lds > POOL_MERGE_LDS_MAX) return hipErrorInvalidValue;
   hipError_t e;
   switch (K) {
 #define RRT_BR_CASE(k) \

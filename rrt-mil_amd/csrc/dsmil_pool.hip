@@ -12,10 +12,10 @@
 // so Q [N, 128] is never formed: C dot products per row instead of 128.  dsmil_prep_kernel builds v, beta from the
 // device-resident indices (one block per class); dsmil_partial_kernel streams feats ONCE -- a wave owns a DS_CHUNK-token
 // chunk, holds each row in registers for the scores and for the pooling, and keeps an online softmax (m, l, sum e^{s-m} f)
-// per class; dsmil_merge_kernel (one block per class) rescales and adds the chunk partials in a fixed order, writes
+// per class; dsmil_merge_kernel (one block per class) merges the chunk records (pool_core.h: pool_merge_core), writes
 // B[c], A[:, c] and the class's share of the Conv1d(C, C, kernel_size = dim) logits; dsmil_logits_kernel adds the C shares.
 // No atomics anywhere: the same inputs give the same bits.
-#include "internal.h"
+#include "pool_core.h"
 
 namespace {
 
@@ -258,105 +258,26 @@ __global__ __launch_bounds__(64) void dsmil_partial_kernel(const float* __restri
   }
 }
 
-// One block per class c: global max / normaliser over the chunk records, B[c] (kept in LDS), A[:, c] in the reference's
+// One block per class c: the merge core over the chunk records leaves B[c] in LDS; then A[:, c] in the reference's
 // [N, C] layout, and this class's share of the logits: lpart[c][o] = fcc_w[o, c, :] . B[c].
 __global__ __launch_bounds__(1024) void dsmil_merge_kernel(const float* __restrict__ part, const float* __restrict__ raw,
                                                            const float* __restrict__ fcc_w, float* __restrict__ B,
                                                            float* __restrict__ A, float* __restrict__ lpart, int N, int dim,
                                                            int K, int nb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* s_scale = (float*)smem;                    // [nb] exp(m_b - M)
-  float* s_pool = s_scale + ((nb + 3) & ~3);        // [dim]
-  float4* s_red = (float4*)(s_pool + dim);          // [8 groups][128 column lanes]
-  __shared__ float s_w[16];
-  __shared__ float s_M, s_invL;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int br = blockIdx.x;
-  const size_t ps = dpart_stride(K, dim);
-  const float* pm = part + (size_t)K * dim + br;           // m of chunk b: pm[b * ps]; l: pm[b * ps + K]
-  const float* pv = part + (size_t)br * dim;
-
-  float m = -3.0e38f;
-  for (int b = tid; b < nb; b += 1024) m = fmaxf(m, pm[b * ps]);
-  m = wave_max(m);
-  if (lane == 0) s_w[wave] = m;
-  __syncthreads();
-  if (tid == 0) {
-    float M = s_w[0];
-    for (int w = 1; w < 16; ++w) M = fmaxf(M, s_w[w]);
-    s_M = M;
-  }
-  __syncthreads();
-  const float M = s_M;
-  float l = 0.f;
-  for (int b = tid; b < nb; b += 1024) {
-    const float sc = __expf(pm[b * ps] - M);
-    s_scale[b] = sc;
-    l += pm[b * ps + K] * sc;
-  }
-  l = wave_sum(l);
-  __syncthreads();                                  // s_w reuse
-  if (lane == 0) s_w[wave] = l;
-  __syncthreads();
-  if (tid == 0) {
-    float L = 0.f;
-    for (int w = 0; w < 16; ++w) L += s_w[w];
-    s_invL = 1.0f / L;
-  }
-  __syncthreads();
-  const float invL = s_invL;
-
-  // B[c] = invL * sum_b scale_b part[b][br][:] : thread = (chunk group of 8, float4 column lane of 128)
-  const int cl = tid & 127, grp = tid >> 7;
-  for (int cb = 0; cb < dim; cb += 512) {
-    const int c = cb + cl * 4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c < dim) {
-      for (int b0 = grp; b0 < nb; b0 += 32) {
-        float4 x[4];
-        float sc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int b = b0 + 8 * u;
-          const bool ok = b < nb;
-          sc[u] = ok ? s_scale[b] : 0.f;
-          x[u] = ok ? *(const float4*)(pv + b * ps + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          acc.x += sc[u] * x[u].x; acc.y += sc[u] * x[u].y; acc.z += sc[u] * x[u].z; acc.w += sc[u] * x[u].w;
-        }
-      }
-    }
-    s_red[grp * 128 + cl] = acc;
-    __syncthreads();
-    if (grp == 0 && c < dim) {
-      float4 a = s_red[cl];
-#pragma unroll
-      for (int q = 1; q < 8; ++q) {
-        const float4 o = s_red[q * 128 + cl];
-        a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
-      }
-      a.x *= invL; a.y *= invL; a.z *= invL; a.w *= invL;
-      *(float4*)(s_pool + c) = a;
-      if (B) *(float4*)(B + (size_t)br * dim + c) = a;
-    }
-    __syncthreads();
-  }
+  // m of chunk b: (part + K * dim + br)[b * ps], l: K floats further; its row for this class: (part + br * dim) + b * ps
+  const PoolMerged p = pool_merge_core(part + (size_t)K * dim + br, K, part + (size_t)br * dim, dpart_stride(K, dim), nb, dim,
+                                       smem, B ? B + (size_t)br * dim : nullptr);
 
   // fcc (Conv1d(C, C, kernel_size = dim) on [1, C, dim]): output o takes fcc_w[o, c, :] . B[c] from this class -- one wave per o
   for (int o = wave; o < K; o += 16) {
-    float acc = 0.f;
-    for (int c = lane * 4; c < dim; c += 256) {
-      const float4 w = *(const float4*)(fcc_w + ((size_t)o * K + br) * dim + c);
-      const float4 p = *(const float4*)(s_pool + c);
-      acc += (w.x * p.x + w.y * p.y) + (w.z * p.z + w.w * p.w);
-    }
-    acc = wave_sum(acc);
+    const float acc = wave_row_dot(fcc_w + ((size_t)o * K + br) * dim, p.s_pool, dim, lane);
     if (lane == 0) lpart[br * 8 + o] = acc;
   }
   if (A) {
-    for (int n = tid; n < N; n += 1024) A[(size_t)n * K + br] = __expf(raw[(size_t)n * K + br] - M) * invL;
+    for (int n = tid; n < N; n += 1024) A[(size_t)n * K + br] = __expf(raw[(size_t)n * K + br] - p.M) * p.invL;
   }
 }
 
@@ -391,10 +312,6 @@ hipError_t dpartial_k(const float* feats, const float* v, const float* vb, float
 
 size_t instance_max_part_records(int N) { return (size_t)((N + IMAX_CHUNK - 1) / IMAX_CHUNK); }
 size_t dsmil_pool_part_floats(int N, int dim, int K) { return (size_t)((N + DS_CHUNK - 1) / DS_CHUNK) * dpart_stride(K, dim); }
-size_t dsmil_pool_merge_lds(int N, int dim) {
-  const int nb = (N + DS_CHUNK - 1) / DS_CHUNK;
-  return ((size_t)((nb + 3) & ~3) + dim) * sizeof(float) + (size_t)8 * 128 * sizeof(float4);
-}
 
 hipError_t launch_instance_max(const float* y, const float* w, const float* b, float* classes, float* cmax, long long* argmax,
                                float* pv, int* pi, int N, int dim, int K, hipStream_t st) {
@@ -417,8 +334,8 @@ hipError_t launch_dsmil_pool(const float* feats, const long long* argmax, const 
                              const float* fcc_b, float* logits, float* A, float* B, float* raw, float* v, float* vb, float* lpart,
                              float* part, int N, int dim, int Q, int K, hipStream_t st) {
   const int nb = (N + DS_CHUNK - 1) / DS_CHUNK;
-  const size_t lds = dsmil_pool_merge_lds(N, dim);
-  if (K < 1 || K > 8 || lds > 150 * 1024 || (size_t)Q * sizeof(float) > 48 * 1024) return hipErrorInvalidValue;
+  const size_t lds = pool_merge_lds_bytes(nb, dim);
+  if (K < 1 || K > 8 || lds > POOL_MERGE_LDS_MAX || (size_t)Q * sizeof(float) > 48 * 1024) return hipErrorInvalidValue;
   dsmil_prep_kernel<<<dim3(K), dim3(256), (size_t)Q * sizeof(float), st>>>(feats, argmax, q_w, q_b, v, vb, N, dim, Q,
                                                                          1.0f / sqrtf((float)Q));
   hipError_t e = hipGetLastError();
@@ -432,7 +349,7 @@ hipError_t launch_dsmil_pool(const float* feats, const long long* argmax, const 
   }
   if (e != hipSuccess) return e;
   auto kern = dsmil_merge_kernel;
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  pool_raise_lds_limit((const void*)kern, lds);
   kern<<<dim3(K), dim3(1024), lds, st>>>(part, raw, fcc_w, B, A, lpart, N, dim, K, nb);
   e = hipGetLastError();
   if (e != hipSuccess) return e;

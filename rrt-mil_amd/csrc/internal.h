@@ -266,7 +266,19 @@ hipError_t launch_pool_merge(const float* part, const float* a_raw, const float*
                              float* pooled, float* logits, float* attn, int no_norm, int N, int dim,
                              int n_classes, hipStream_t st);
 
+// Dynamic LDS of the pooling launches that grow with the shape.  A block gets POOL_LDS_DEFAULT without asking; the merge block
+// of every head (pool_core.h: one scale per chunk, the pooled row, 8 x 128 float4 partials) and the CLAM adjoint may raise
+// their limit up to POOL_MERGE_LDS_MAX.
+constexpr size_t POOL_LDS_DEFAULT = 64 * 1024, POOL_MERGE_LDS_MAX = 150 * 1024;
+inline size_t pool_merge_lds_bytes(size_t nb, int dim) {       // nb: chunk records to merge
+  return (((nb + 3) & ~(size_t)3) + dim) * sizeof(float) + (size_t)8 * 128 * sizeof(float4);
+}
+inline void pool_raise_lds_limit(const void* kern, size_t lds) {
+  if (lds > POOL_LDS_DEFAULT)
+    (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
 // whether the merge block's / the backward block's dynamic LDS fits what launch_pool_merge / launch_pool_backward may ask for
+// (POOL_CHUNK = DS_CHUNK tokens per chunk record: the same answer for the ABMIL, CLAM and DSMIL merge blocks)
 bool pool_merge_fits(int64_t N, int dim);
 bool pool_backward_fits(int dim, int hid);
 
@@ -280,7 +292,6 @@ hipError_t launch_pool_backward(const float* y, const float* hid_a, const float*
 // CLAM heads (clam_pool.hip): K attention branches from one pass over y, their adjoint, top-k of rows
 size_t branch_pool_part_floats(int N, int dim, int K);
 size_t branch_pool_backward_part_floats(int N, int hid, int K);
-size_t branch_pool_merge_lds(int N, int dim);
 size_t branch_pool_backward_lds(int dim, int hid, int K);
 hipError_t launch_branch_pool(const float* y, const float* hid_a, const float* hid_b, const float* wc, const float* bc,
                               const float* cls_w, const float* cls_b, float* pooled, float* logits, float* attn, float* a_raw,
@@ -295,7 +306,6 @@ constexpr int IMAX_CHUNK = 128;  // tokens per (max, index) record of the instan
 constexpr int DS_CHUNK = 32;     // tokens per online-softmax record of the bag stream (one wave)
 size_t instance_max_part_records(int N);
 size_t dsmil_pool_part_floats(int N, int dim, int K);
-size_t dsmil_pool_merge_lds(int N, int dim);
 hipError_t launch_instance_max(const float* y, const float* w, const float* b, float* classes, float* cmax, long long* argmax,
                                float* pv, int* pi, int N, int dim, int K, hipStream_t st);
 hipError_t launch_dsmil_pool(const float* feats, const long long* argmax, const float* q_w, const float* q_b, const float* fcc_w,

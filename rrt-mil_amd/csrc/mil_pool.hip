@@ -7,10 +7,11 @@
 //     pooled = sum_n A_n y_n              [dim]
 //     logits = pred_w pooled + pred_b     [n_classes]
 // The softmax over N is an online softmax over POOL_CHUNK-token chunks: every block emits
-// (m_b, l_b, v_b = sum exp(a_n - m_b) y_n), one merge block rescales and adds them.  HBM-bound:
+// (m_b, l_b, v_b = sum exp(a_n - m_b) y_n), one merge block rescales and adds them (pool_core.h: the pieces every head's
+// pooling kernels are built from; the kernels here are those pieces at one branch plus the predictor).  HBM-bound:
 // reads y (N*dim) and the hidden rows (N*hid) once; the 18 MB of y never has to be re-read by a
 // separate softmax / matmul pair, and nothing of size N x dim is written.
-#include "internal.h"
+#include "pool_core.h"
 
 namespace {
 
@@ -25,9 +26,8 @@ __global__ __launch_bounds__(256) void pool_partial_kernel(const float* __restri
                                                            float* __restrict__ a_raw,
                                                            float* __restrict__ part, int N, int dim, int hid) {
   __shared__ float s_a[POOL_CHUNK];
-  __shared__ float s_e[POOL_CHUNK];
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float4* red = (float4*)smem;                       // [dim/4] second row group's partial
+  __shared__ float s_e[1][POOL_CHUNK];
+  extern __shared__ __attribute__((aligned(16))) char smem[];     // [dim/4 <= 128] float4: second row group's partial
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n0 = blockIdx.x * POOL_CHUNK;
   const int cnt = min(POOL_CHUNK, N - n0);
@@ -35,18 +35,9 @@ __global__ __launch_bounds__(256) void pool_partial_kernel(const float* __restri
   // ---- scores: one wave per token, POOL_CHUNK / 4 tokens per wave
   const float b = bc ? bc[0] : 0.f;
   for (int t = wave; t < cnt; t += 4) {
-    const size_t row = (size_t)(n0 + t) * hid;
-    float acc = 0.f;
-    for (int c = lane * 4; c < hid; c += 256) {
-      float4 h = *(const float4*)(hid_a + row + c);
-      if (hid_b) {
-        const float4 g = *(const float4*)(hid_b + row + c);
-        h.x *= g.x; h.y *= g.y; h.z *= g.z; h.w *= g.w;
-      }
-      const float4 w = *(const float4*)(wc + c);
-      acc += (h.x * w.x + h.y * w.y) + (h.z * w.z + h.w * w.w);
-    }
-    acc = wave_sum(acc) + b;
+    float s[1];
+    gate_scores_row<1>(hid_a, hid_b, wc, (size_t)(n0 + t) * hid, hid, lane, s);
+    const float acc = s[0] + b;
     if (lane == 0) {
       s_a[t] = acc;
       a_raw[n0 + t] = acc;
@@ -56,50 +47,22 @@ __global__ __launch_bounds__(256) void pool_partial_kernel(const float* __restri
   // ---- chunk max / exp / sum (every thread redundantly: cnt <= 32 LDS reads)
   float m = -3.0e38f;
   for (int t = 0; t < cnt; ++t) m = fmaxf(m, s_a[t]);
-  if (tid < cnt) s_e[tid] = __expf(s_a[tid] - m);
+  if (tid < POOL_CHUNK) s_e[0][tid] = tid < cnt ? __expf(s_a[tid] - m) : 0.f;
   __syncthreads();
   float l = 0.f;
-  for (int t = 0; t < cnt; ++t) l += s_e[t];
+  for (int t = 0; t < cnt; ++t) l += s_e[0][t];
 
-  // ---- weighted sum of the chunk's rows: thread = (row group rg of 2, float4 column lane of 128)
-  const int cl = tid & 127, rg = tid >> 7;
+  // ---- weighted sum of the chunk's rows
   float* out = part + (size_t)blockIdx.x * part_stride(dim);
-  for (int cb = 0; cb < dim; cb += 512) {
-    const int c = cb + cl * 4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c < dim) {
-      for (int t0 = rg; t0 < cnt; t0 += 8) {          // 4 independent rows in flight
-        float4 v[4];
-        float e[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int t = t0 + 2 * u;
-          const bool ok = t < cnt;
-          e[u] = ok ? s_e[t] : 0.f;
-          v[u] = ok ? *(const float4*)(y + (size_t)(n0 + t) * dim + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          acc.x += e[u] * v[u].x; acc.y += e[u] * v[u].y; acc.z += e[u] * v[u].z; acc.w += e[u] * v[u].w;
-        }
-      }
-    }
-    if (rg == 1 && c < dim) red[cl] = acc;
-    __syncthreads();
-    if (rg == 0 && c < dim) {
-      const float4 o = red[cl];
-      *(float4*)(out + c) = make_float4(acc.x + o.x, acc.y + o.y, acc.z + o.z, acc.w + o.w);
-    }
-    __syncthreads();
-  }
+  chunk_weighted_rowsum<1>(y, s_e, (float4(*)[128])smem, out, n0, cnt, dim);
   if (tid == 0) {
     out[dim] = m;
     out[dim + 1] = l;
   }
 }
 
-// One block: global max / normaliser over the chunk partials, pooled vector, predictor, and the
-// attention row the reference returns (normalised, or raw scores for no_norm=True).
+// One block: the merge core over the chunk partials, then the predictor and the attention row the reference returns
+// (normalised, or raw scores for no_norm=True).
 __global__ __launch_bounds__(1024) void pool_merge_kernel(const float* __restrict__ part,
                                                           const float* __restrict__ a_raw,
                                                           const float* __restrict__ pred_w,
@@ -108,97 +71,18 @@ __global__ __launch_bounds__(1024) void pool_merge_kernel(const float* __restric
                                                           float* __restrict__ logits, float* __restrict__ attn,
                                                           int no_norm, int N, int dim, int n_classes, int nb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* s_scale = (float*)smem;                    // [nb] exp(m_b - M)
-  float* s_pool = s_scale + ((nb + 3) & ~3);        // [dim]
-  float4* s_red = (float4*)(s_pool + dim);          // [8 groups][128 column lanes]
-  __shared__ float s_w[16];
-  __shared__ float s_M, s_invL;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const size_t ps = part_stride(dim);
-
-  float m = -3.0e38f;
-  for (int b = tid; b < nb; b += 1024) m = fmaxf(m, part[b * ps + dim]);
-  m = wave_max(m);
-  if (lane == 0) s_w[wave] = m;
-  __syncthreads();
-  if (tid == 0) {
-    float M = s_w[0];
-    for (int w = 1; w < 16; ++w) M = fmaxf(M, s_w[w]);
-    s_M = M;
-  }
-  __syncthreads();
-  const float M = s_M;
-  float l = 0.f;
-  for (int b = tid; b < nb; b += 1024) {
-    const float sc = __expf(part[b * ps + dim] - M);
-    s_scale[b] = sc;
-    l += part[b * ps + dim + 1] * sc;
-  }
-  l = wave_sum(l);
-  __syncthreads();                                  // s_w reuse
-  if (lane == 0) s_w[wave] = l;
-  __syncthreads();
-  if (tid == 0) {
-    float L = 0.f;
-    for (int w = 0; w < 16; ++w) L += s_w[w];
-    s_invL = 1.0f / L;
-  }
-  __syncthreads();
-  const float invL = s_invL;
-
-  // pooled[c] = invL * sum_b scale_b part[b][c] : thread = (chunk group of 8, float4 column lane of 128)
-  const int cl = tid & 127, grp = tid >> 7;
-  for (int cb = 0; cb < dim; cb += 512) {
-    const int c = cb + cl * 4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c < dim) {
-      for (int b0 = grp; b0 < nb; b0 += 32) {
-        float4 v[4];
-        float sc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int b = b0 + 8 * u;
-          const bool ok = b < nb;
-          sc[u] = ok ? s_scale[b] : 0.f;
-          v[u] = ok ? *(const float4*)(part + b * ps + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          acc.x += sc[u] * v[u].x; acc.y += sc[u] * v[u].y; acc.z += sc[u] * v[u].z; acc.w += sc[u] * v[u].w;
-        }
-      }
-    }
-    s_red[grp * 128 + cl] = acc;
-    __syncthreads();
-    if (grp == 0 && c < dim) {
-      float4 a = s_red[cl];
-#pragma unroll
-      for (int q = 1; q < 8; ++q) {
-        const float4 o = s_red[q * 128 + cl];
-        a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
-      }
-      a.x *= invL; a.y *= invL; a.z *= invL; a.w *= invL;
-      *(float4*)(s_pool + c) = a;
-      if (pooled) *(float4*)(pooled + c) = a;
-    }
-    __syncthreads();
-  }
+  const PoolMerged p = pool_merge_core(part + dim, 1, part, part_stride(dim), nb, dim, smem, pooled);
 
   // predictor: one wave per class
   for (int j = wave; j < n_classes; j += 16) {
-    float acc = 0.f;
-    for (int c = lane * 4; c < dim; c += 256) {
-      const float4 w = *(const float4*)(pred_w + (size_t)j * dim + c);
-      const float4 p = *(const float4*)(s_pool + c);
-      acc += (w.x * p.x + w.y * p.y) + (w.z * p.z + w.w * p.w);
-    }
-    acc = wave_sum(acc);
+    const float acc = wave_row_dot(pred_w + (size_t)j * dim, p.s_pool, dim, lane);
     if (lane == 0) logits[j] = acc + (pred_b ? pred_b[j] : 0.f);
   }
   if (attn) {
     for (int n = tid; n < N; n += 1024) {
       const float a = a_raw[n];
-      attn[n] = no_norm ? a : __expf(a - M) * invL;
+      attn[n] = no_norm ? a : __expf(a - p.M) * p.invL;
     }
   }
 }
@@ -222,18 +106,11 @@ __global__ __launch_bounds__(256) void pool_backward_kernel(const float* __restr
   float* s_dp = (float*)smem;                        // d pooled [dim]
   float* s_acc = s_dp + dim;                         // [4 waves][hid + 4]: this block's d wc | d bc partial
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  float cpart = 0.f;
-  for (int c = tid; c < dim; c += 256) {
-    const float v = d_pooled[c];
-    s_dp[c] = v;
-    cpart += v * pooled[c];
-  }
-  for (int c = tid; c < 4 * (hid + 4); c += 256) s_acc[c] = 0.f;
   __shared__ float s_c[4];
-  cpart = wave_sum(cpart);
-  if (lane == 0) s_c[wave] = cpart;
+  for (int c = tid; c < 4 * (hid + 4); c += 256) s_acc[c] = 0.f;
+  pool_backward_stage(d_pooled, pooled, s_dp, s_c, dim);
   __syncthreads();
-  const float cc = (s_c[0] + s_c[1]) + (s_c[2] + s_c[3]) + (c_ext ? c_ext[0] : 0.f);
+  const float cc = pool_backward_c(s_c) + (c_ext ? c_ext[0] : 0.f);
   float* myacc = s_acc + wave * (hid + 4);
   const int n0 = blockIdx.x * POOL_BWD_ROWS;
   float dbc = 0.f;
@@ -278,15 +155,11 @@ __global__ __launch_bounds__(256) void pool_backward_kernel(const float* __restr
 
 }  // namespace
 
-// dynamic LDS of the two launches below that grow with the shape.  The backward block stays inside the default limit (no head
-// builds a hidden width near it: 128 everywhere in the reference); the merge block may raise its limit up to POOL_MERGE_LDS_MAX.
-constexpr size_t POOL_LDS_DEFAULT = 64 * 1024, POOL_MERGE_LDS_MAX = 150 * 1024;
+// The backward block stays inside the default LDS limit (no head builds a hidden width near it: 128 everywhere in the reference).
 size_t pool_backward_lds_bytes(int dim, int hid) { return ((size_t)dim + 4 * ((size_t)hid + 4)) * sizeof(float); }
-size_t pool_merge_lds_bytes(int64_t N, int dim) {
-  const size_t nb = (size_t)((N + POOL_CHUNK - 1) / POOL_CHUNK);
-  return (((nb + 3) & ~(size_t)3) + dim) * sizeof(float) + (size_t)8 * 128 * sizeof(float4);
+bool pool_merge_fits(int64_t N, int dim) {
+  return pool_merge_lds_bytes((size_t)((N + POOL_CHUNK - 1) / POOL_CHUNK), dim) <= POOL_MERGE_LDS_MAX;
 }
-bool pool_merge_fits(int64_t N, int dim) { return pool_merge_lds_bytes(N, dim) <= POOL_MERGE_LDS_MAX; }
 bool pool_backward_fits(int dim, int hid) { return pool_backward_lds_bytes(dim, hid) <= POOL_LDS_DEFAULT; }
 
 // d wc [hid] and d bc [1] come out as dwcb [hid + 4] (d bc at [hid]); part: ceil(N / 32) * (hid + 4) floats
@@ -319,11 +192,10 @@ hipError_t launch_pool_merge(const float* part, const float* a_raw, const float*
                              float* pooled, float* logits, float* attn, int no_norm, int N, int dim,
                              int n_classes, hipStream_t st) {
   const int nb = (N + POOL_CHUNK - 1) / POOL_CHUNK;
-  const size_t lds = pool_merge_lds_bytes(N, dim);
+  const size_t lds = pool_merge_lds_bytes(nb, dim);
   if (lds > POOL_MERGE_LDS_MAX) return hipErrorInvalidValue;    // (the C ABI refuses these shapes before it gets here)
   auto kern = pool_merge_kernel;
-  if (lds > POOL_LDS_DEFAULT)
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  pool_raise_lds_limit((const void*)kern, lds);
   kern<<<dim3(1), dim3(1024), lds, st>>>(part, a_raw, pred_w, pred_b, pooled, logits, attn, no_norm, N, dim,
                                          n_classes, nb);
   return hipGetLastError();

@@ -6,12 +6,12 @@
 //     p_i    = softmax_c(w_i * (mid_i . Wcls_c))[C - 1]                          (get_cam_1d: the classifier's weight, no bias)
 //     imax_g = argmax_i p_i ,  imin_g = argmin_i p_i                             (sel [G, 2], original row indices)
 // in three launches over one read of mid: a partial per (group, chunk of POOL_CHUNK positions) -- the online-softmax triple
-// (m, l, v[dim]) of mil_pool.hip and, from the same registers, the C dot products z_ic = mid_i . Wcls_c --, then one block per
+// (m, l, v[dim]) of pool_core.h and, from the same registers, the C dot products z_ic = mid_i . Wcls_c --, then one block per
 // group that merges its partials and walks its positions for p and the two selections.  Ties: among equal p the lower
 // position in group order wins at both ends, -0 = +0, a NaN p is never selected, a group whose every p is NaN selects its
 // first member twice.  Everything is fp32 with accurate expf, and every sum has a fixed order: the same inputs give the same
 // bits.  No atomics: every row belongs to exactly one group.
-#include "internal.h"
+#include "pool_core.h"
 
 namespace {
 
@@ -54,7 +54,7 @@ __device__ __forceinline__ int seg_row(const long long* __restrict__ perm, int j
   return (i < 0 || i >= N) ? -1 : (int)i;
 }
 
-// a_n = wc . h_n (+ bc): the prologue of pool_partial_kernel (mil_pool.hip) on its own -- the same arithmetic in the same order
+// a_n = wc . h_n (+ bc): the gate score of pool_core.h as a stage of its own, one wave per row in the ABMIL pool's chunks
 __global__ __launch_bounds__(256) void gate_scores_kernel(const float* __restrict__ hid_a, const float* __restrict__ hid_b,
                                                           const float* __restrict__ wc, const float* __restrict__ bc,
                                                           float* __restrict__ a_raw, int N, int hid) {
@@ -63,19 +63,9 @@ __global__ __launch_bounds__(256) void gate_scores_kernel(const float* __restric
   const int cnt = min(POOL_CHUNK, N - n0);
   const float b = bc ? bc[0] : 0.f;
   for (int t = wave; t < cnt; t += 4) {
-    const size_t row = (size_t)(n0 + t) * hid;
-    float acc = 0.f;
-    for (int c = lane * 4; c < hid; c += 256) {
-      float4 h = *(const float4*)(hid_a + row + c);
-      if (hid_b) {
-        const float4 g = *(const float4*)(hid_b + row + c);
-        h.x *= g.x; h.y *= g.y; h.z *= g.z; h.w *= g.w;
-      }
-      const float4 w = *(const float4*)(wc + c);
-      acc += (h.x * w.x + h.y * w.y) + (h.z * w.z + h.w * w.w);
-    }
-    acc = wave_sum(acc) + b;
-    if (lane == 0) a_raw[n0 + t] = acc;
+    float s[1];
+    gate_scores_row<1>(hid_a, hid_b, wc, (size_t)(n0 + t) * hid, hid, lane, s);
+    if (lane == 0) a_raw[n0 + t] = s[0] + b;
   }
 }
 
@@ -327,16 +317,9 @@ __global__ __launch_bounds__(256) void seg_backward_kernel(const float* __restri
   seg_block(sp, blockIdx.x, g, ch);
   const int j0 = seg_start(sp, g) + ch * POOL_CHUNK;
   const int cnt = min(POOL_CHUNK, seg_size(sp, g) - ch * POOL_CHUNK);
-  float cpart = 0.f;
-  for (int c = tid; c < dim; c += 256) {
-    const float v = d_pooled[(size_t)g * dim + c];
-    s_dp[c] = v;
-    cpart += v * pooled[(size_t)g * dim + c];
-  }
-  cpart = wave_sum(cpart);
-  if (lane == 0) s_c[wave] = cpart;
+  pool_backward_stage(d_pooled + (size_t)g * dim, pooled + (size_t)g * dim, s_dp, s_c, dim);
   __syncthreads();
-  const float cc = (s_c[0] + s_c[1]) + (s_c[2] + s_c[3]);
+  const float cc = pool_backward_c(s_c);
   const float M = ml[2 * g], invL = 1.0f / ml[2 * g + 1];
   for (int t = wave; t < cnt; t += 4) {
     const int row = seg_row(perm, j0 + t, N);
@@ -371,7 +354,7 @@ hipError_t launch_segment_pool(const float* mid, const float* a, const long long
                                int ids_stride, int N, int dim, int C, int G, hipStream_t st) {
   const int nb = (int)segment_pool_parts(N, G);
   const size_t lds = (size_t)(C > 3 ? C : 3) * dim * sizeof(float);      // <= 8 * 2048 * 4 = 64 KiB, beside 384 static bytes
-  if (lds + 1024 > 64 * 1024)
+  if (lds + 1024 > POOL_LDS_DEFAULT)
     (void)hipFuncSetAttribute((const void*)seg_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   seg_partial_kernel<<<dim3(nb), dim3(256), lds, st>>>(mid, a, perm, cls_w, part, z, N, dim, C, G);
   hipError_t e = hipGetLastError();

@@ -1,4 +1,4 @@
-"""Case lists and closed-form inputs of the attention-pooling tests (csrc/mil_pool.hip): tests/test_mil_pool_cases_cpu.py checks
+"""Case lists and closed-form inputs of the attention-pooling tests (csrc/mil_pool.hip on csrc/pool_core.h): tests/test_mil_pool_cases_cpu.py checks
 on the CPU that the lists cover what they claim and that every premise holds; tests/test_mil_pool_matrix.py runs them on the
 GPU.  Importing this module needs no device.
 

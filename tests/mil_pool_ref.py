@@ -1,4 +1,5 @@
-"""Restatements of csrc/mil_pool.hip for tests/test_mil_pool_matrix.py and tests/test_mil_pool_cases_cpu.py (no device).
+"""Restatements of csrc/mil_pool.hip and of the pooling core its kernels are built on (csrc/pool_core.h: gate score, chunk sum,
+merge block) for tests/test_mil_pool_matrix.py and tests/test_mil_pool_cases_cpu.py (no device).
 
 ``ref64`` is the operation of the file's header comment in float64 torch on the CPU:
     s_n = c_w . h_n (+ c_b)   h = hid_a, or hid_a * hid_b (gated)      attn = softmax_n(s)
@@ -15,7 +16,7 @@ import torch
 
 CHUNK = 32                      # POOL_CHUNK (csrc/internal.h); tests/test_mil_pool_cases_cpu.py reads the compiled value
 BWD_ROWS = 32                   # POOL_BWD_ROWS
-MERGE_THREADS = 1024            # pool_merge_kernel's block: the stride of its loops over the partials
+MERGE_THREADS = 1024            # the merge block (pool_merge_core): the stride of its loops over the partials
 HID_STRIDE = 256                # floats of a hidden row one wave covers per trip
 DIM_PASS = 512                  # columns per pass of the weighted sums
 CLASS_STRIDE = 16               # classes per trip of the predictor (one wave each)

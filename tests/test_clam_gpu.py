@@ -126,6 +126,18 @@ def test_branch_pool_forward_plain(dim, hid, K, gated):
 
 
 @pytest.mark.parametrize("gated", [False, True])
+@pytest.mark.parametrize("N", [1057, 32801])
+def test_branch_pool_forward_plain_past_one_merge_trip(N, gated):
+    """nb = 34: the merge block's first chunk-group trip past 32; nb = 1026: a second trip of its 1024-stride loops, the last
+    chunk ragged (one token).  K = 3: branches 1 and 2 reach m, l and their rows through the branch offsets of the part layout."""
+    dim, hid, K = 64, 12, 3
+    y, ha, hb, cw, cb = _inputs(N, dim, hid, K, gated, f"{N}/{dim}/{hid}/{K}")
+    got = _branch_pool(y, ha, hb, cw, cb)
+    _check_fwd(got, _ref64(y, ha, hb, cw, cb), f"plain N={N}")
+    assert abs(float(got[1].double().sum(1).sub(1).abs().max())) < 1e-5
+
+
+@pytest.mark.parametrize("gated", [False, True])
 @pytest.mark.parametrize("K", [1, 2, 3, 8])
 @pytest.mark.parametrize("dim,hid", [(64, 12), (64, 256), (512, 12), (512, 256)])
 def test_branch_pool_forward_peaked(dim, hid, K, gated):

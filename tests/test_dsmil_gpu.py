@@ -215,6 +215,15 @@ def test_dsmil_pool_plain(dim, Q, K):
                 "no biases")
 
 
+@pytest.mark.parametrize("N", [1057, 32801])
+def test_dsmil_pool_plain_past_one_merge_trip(N):
+    """nb = 34: the merge block's first chunk-group trip past 32; nb = 1026: a second trip of its 1024-stride loops, the last
+    chunk ragged (one token).  K = 3: classes 1 and 2 reach m, l and their rows through the class offsets of the part layout."""
+    dim, Q, K = 64, 32, 3
+    args = _pool_inputs(N, dim, Q, K, f"{N}/{dim}/{Q}/{K}")
+    _check_pool(_pool(*args), _pool_ref64(*args), f"plain N={N}")
+
+
 @pytest.mark.parametrize("K", [1, 2, 3, 8])
 @pytest.mark.parametrize("dim,Q", [(64, 32), (64, 128), (512, 32), (512, 128)])
 def test_dsmil_pool_peaked(dim, Q, K):

@@ -1,5 +1,6 @@
 """CPU: the case lists of tests/test_mil_pool_matrix.py (tests/mil_pool_cases.py) cover what they claim, and the Python
-restatement of csrc/mil_pool.hip's constants (tests/mil_pool_ref.py) is the compiled one.
+restatement of the constants of csrc/mil_pool.hip and of the pooling core it is built on, csrc/pool_core.h
+(tests/mil_pool_ref.py), is the compiled one.
 
   * the chunk size, the backward's rows per block, every loop stride and the merge launch's LDS formula with its two thresholds
     are read out of the sources; the two workspace-size queries are compared with the restated formulas over a sweep;
@@ -39,28 +40,36 @@ def _src(name):
 
 # ------------------------------------------------------------------ the restated constants are the compiled ones
 def test_restated_constants_are_the_compiled_ones(lib):
-    hdr, src = _src("internal.h"), _src("mil_pool.hip")
+    hdr, src, core = _src("internal.h"), _src("mil_pool.hip"), _src("pool_core.h")
     assert int(re.search(r"constexpr int POOL_CHUNK = (\d+);", hdr).group(1)) == R.CHUNK == 32
     assert int(re.search(r"constexpr int POOL_BWD_ROWS = (\d+);", src).group(1)) == R.BWD_ROWS == 32
-    # the merge block: 1024 threads striding over the partials (maximum, then scale / normaliser) and over attn
+    # the merge block: 1024 threads striding over the partials (maximum, then scale / normaliser) and over attn; every head's
+    # merge kernel is that block
     assert "__launch_bounds__(1024) void pool_merge_kernel" in src and "kern<<<dim3(1), dim3(1024), lds, st>>>" in src
-    assert len(re.findall(r"for \(int b = tid; b < nb; b \+= 1024\)", src)) == 2 and R.MERGE_THREADS == 1024
+    for unit, kern in (("clam_pool.hip", "branch_merge_kernel"), ("dsmil_pool.hip", "dsmil_merge_kernel")):
+        text = _src(unit)
+        assert f"__launch_bounds__(1024) void {kern}" in text and f"auto kern = {kern};" in text
+        assert "kern<<<dim3(K), dim3(1024), lds, st>>>" in text
+    assert "auto kern = pool_merge_kernel;" in src
+    assert len(re.findall(r"for \(int b = tid; b < nb; b \+= 1024\)", core)) == 2 and R.MERGE_THREADS == 1024
     assert "for (int n = tid; n < N; n += 1024)" in src
-    assert "for (int b0 = grp; b0 < nb; b0 += 32)" in src and "const int b = b0 + 8 * u;" in src          # 8 groups, 4 in flight
+    assert "for (int b0 = grp; b0 < nb; b0 += 32)" in core and "const int b = b0 + 8 * u;" in core        # 8 groups, 4 in flight
     assert "for (int j = wave; j < n_classes; j += 16)" in src and R.CLASS_STRIDE == 16
-    assert len(re.findall(r"for \(int cb = 0; cb < dim; cb \+= 512\)", src)) == 2 and R.DIM_PASS == 512
-    assert len(re.findall(r"for \(int c = lane \* 4; c < hid; c \+= 256\)", src)) == 2 and R.HID_STRIDE == 256
-    assert len(re.findall(r"for \(int c = lane \* 4; c < dim; c \+= 256\)", src)) == 2
-    assert "for (int t0 = rg; t0 < cnt; t0 += 8)" in src and "const int t = t0 + 2 * u;" in src
+    assert len(re.findall(r"for \(int cb = 0; cb < dim; cb \+= 512\)", core)) == 2 and R.DIM_PASS == 512   # chunk sum, merge
+    hid_loop = r"for \(int c = lane \* 4; c < hid; c \+= 256\)"                                            # gate score | backward
+    assert len(re.findall(hid_loop, core)) == 1 and len(re.findall(hid_loop, src)) == 1 and R.HID_STRIDE == 256
+    dim_loop = r"for \(int c = lane \* 4; c < dim; c \+= 256\)"                                            # row dot | backward
+    assert len(re.findall(dim_loop, core)) == 1 and len(re.findall(dim_loop, src)) == 1
+    assert "for (int t0 = rg; t0 < cnt; t0 += 8)" in core and "const int t = t0 + 2 * u;" in core
     assert "for (int t = wave; t < POOL_BWD_ROWS; t += 4)" in src and "if (n >= N) break;" in src
-    assert "float m = -3.0e38f;" in src and R.SENTINEL == np.float32(-3.0e38)
+    assert "float m = -3.0e38f;" in src and "float m = -3.0e38f;" in core and R.SENTINEL == np.float32(-3.0e38)
     # the LDS formulas and thresholds
-    m = re.search(r"constexpr size_t POOL_LDS_DEFAULT = (\d+) \* 1024, POOL_MERGE_LDS_MAX = (\d+) \* 1024;", src)
+    m = re.search(r"constexpr size_t POOL_LDS_DEFAULT = (\d+) \* 1024, POOL_MERGE_LDS_MAX = (\d+) \* 1024;", hdr)
     assert (int(m.group(1)) * 1024, int(m.group(2)) * 1024) == (K.LDS_DEFAULT, K.LDS_MERGE_MAX)
-    assert "return (((nb + 3) & ~(size_t)3) + dim) * sizeof(float) + (size_t)8 * 128 * sizeof(float4);" in src
+    assert "return (((nb + 3) & ~(size_t)3) + dim) * sizeof(float) + (size_t)8 * 128 * sizeof(float4);" in hdr
     assert "return ((size_t)dim + 4 * ((size_t)hid + 4)) * sizeof(float);" in src
-    assert "if (lds > POOL_MERGE_LDS_MAX) return hipErrorInvalidValue;" in src and "if (lds > POOL_LDS_DEFAULT)\n" in src
-    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in src
+    assert "if (lds > POOL_MERGE_LDS_MAX) return hipErrorInvalidValue;" in src and "if (lds > POOL_LDS_DEFAULT)\n" in hdr
+    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in hdr and "pool_raise_lds_limit((const void*)kern, lds);" in src
     assert K.LDS_EDGE == 392192 and K.merge_lds(K.LDS_EDGE, 32) == 65536 and K.merge_lds(K.LDS_EDGE + 1, 32) == 65552
     assert K.merge_lds(K.MAX_TOKENS, K.LDS_DIM) <= K.LDS_MERGE_MAX
     need = C.c_size_t()

@@ -921,6 +921,21 @@ int rrt_encoder_backward_f32(const rrt_encoder_desc *desc, const rrt_encoder_wei
                              size_t workspace_bytes, float drop_p, uint64_t drop_seed,
                              const float *branch_scale, void *stream);
 
+/* The same pair for the part of an encoder BEHIND its attention layers (CR-MSA, all_shortcut, the final LayerNorm), for callers
+ * that run the attention layers themselves (the Nystrom ablations' training path; exports added under ABI 29, the pair above
+ * and its bits unchanged).  desc must have n_rmsa_layers = 0 and pos none (else RRT_E_UNSUPPORTED); sizes are
+ * rrt_encoder_train_sizes' for that desc.  x1 [n_tokens, dim] is the attention layers' output, x0 what all_shortcut adds (the
+ * encoder's ORIGINAL input; read, and d_x0 written, only when desc->all_shortcut, and then neither may be NULL).  backward
+ * writes d_x1 (or skips it when NULL) without the shortcut's share, which goes to d_x0.  CR-MSA's stochastic-depth multiplier
+ * is branch_scale[0] (its layer index is n_rmsa_layers = 0). */
+int rrt_encoder_tail_forward_train_f32(const rrt_encoder_desc *desc, const rrt_encoder_weights *w, const float *x1,
+                                       const float *x0, float *y, int64_t n_tokens, void *stash, size_t stash_bytes,
+                                       float drop_p, uint64_t drop_seed, const float *branch_scale, void *stream);
+int rrt_encoder_tail_backward_f32(const rrt_encoder_desc *desc, const rrt_encoder_weights *w, const float *x1, const float *dy,
+                                  const void *stash, size_t stash_bytes, const rrt_encoder_grads *grads, float *d_x1,
+                                  float *d_x0, int64_t n_tokens, void *workspace, size_t workspace_bytes, float drop_p,
+                                  uint64_t drop_seed, const float *branch_scale, void *stream);
+
 /* ---- Nystrom attention and the TransMIL baseline (modules/nystrom_attention.py:67-149, modules/transmil.py:26-125; exports
  * added under ABI 29, no existing struct touched).  Inference, exact fp32 on the fp32 matrix cores, no atomics: the same inputs
  * give the same bits.  There is no mask argument (the reference's mask branch names undefined variables).
@@ -1066,6 +1081,50 @@ int rrt_nystrom_pinv_sim_backward_f32(const float *ql, const float *kl, const fl
                                       void *stream);
 int rrt_nystrom_landmarks_backward_f32(const float *d_ql, const float *d_kl, float *d_qkv, int64_t n_padded, int32_t heads,
                                        void *stream);
+
+/* ---- Batched Nystrom attention, training (exports added under ABI 29; nothing above changes).  The reference's autograd on a
+ * (b, n, dim) batch, b sequences per launch: exact fp32 on the fp32 matrix cores, no atomics, every sum in a fixed order (the
+ * parameter gradients are summed over the items in item order), two calls give the same bits.  Layouts are those of the
+ * batched forward stages above (a leading b; each item's np - n zero rows in FRONT of that item).  What a batch changes:
+ *  - the pseudo-inverse's den is ONE scalar over all b * heads matrices, so d den is the sum of <d_z, the tangent of z along
+ *    the scale of z0> over every item and head, and it goes to the columns that attain the largest column sum ANYWHERE in
+ *    the batch, shared evenly among columns whose sums are equal bit for bit, across items too;
+ *  - the stencil's adjoint and d_conv_w run along each item's own padded sequence; d_conv_w is summed over the items;
+ *  - d_o's pad rows are zero and d_qkv's pad rows are dropped in front of the qkv linear's backward.
+ * Envelope: the single-sequence one plus 1 <= b <= 2048 (b * heads stays a valid grid dimension) and b * n <= 4e6; beyond
+ * it the size functions and every entry return RRT_E_UNSUPPORTED naming b.  A short stash or workspace is RRT_E_WORKSPACE.
+ * With b = 1 every entry takes the single-sequence code path and gives the bits of its single-sequence counterpart.
+ * batched_train_sizes: the stash is the batched forward's workspace kept whole plus the row log-sum-exp [b, heads, 256]; the
+ *   backward's workspace holds (pinv_iterations + 10) matrices per (item, head) -- 2 GiB at b = 64, 8 heads, 6 iterations.
+ * forward_train: x [b, n, dim] -> y [b, n, dim], bit-identical to rrt_nystrom_attention_batched_f32.
+ * backward: dy [b, n, dim] -> grads (WRITTEN, not accumulated) and, unless NULL, dx [b, n, dim].
+ * The stage entries are the single-sequence ones above with b in front of the sizes. */
+int rrt_nystrom_batched_train_sizes(const rrt_nystrom_desc *desc, int64_t b, int64_t n, size_t *stash_bytes,
+                                    size_t *backward_workspace_bytes);
+int rrt_nystrom_attention_batched_forward_train_f32(const rrt_nystrom_desc *desc, const rrt_nystrom_weights *w, const float *x,
+                                                    float *y, int64_t b, int64_t n, void *stash, size_t stash_bytes,
+                                                    void *stream);
+int rrt_nystrom_attention_batched_backward_f32(const rrt_nystrom_desc *desc, const rrt_nystrom_weights *w, const float *x,
+                                               const float *dy, const void *stash, size_t stash_bytes,
+                                               const rrt_nystrom_grads *grads, float *dx, int64_t b, int64_t n, void *workspace,
+                                               size_t workspace_bytes, void *stream);
+int rrt_nystrom_output_batched_backward_workspace_size(int64_t b, int64_t n_padded, int32_t heads, size_t *bytes);
+int rrt_nystrom_output_batched_backward_f32(const float *qkv, const float *kl, const float *wz, const float *conv_w,
+                                            const float *d_o, float *d_qkv, float *d_kl, float *d_wz, float *d_conv_w, int64_t b,
+                                            int64_t n_padded, int32_t heads, int32_t conv_k, void *workspace,
+                                            size_t workspace_bytes, void *stream);
+int rrt_nystrom_zav_batched_backward_f32(const float *z, const float *av, const float *d_wz, float *d_z, float *d_av, int64_t b,
+                                         int32_t heads, void *stream);
+int rrt_nystrom_landmark_attn_batched_backward_workspace_size(int64_t b, int64_t n_padded, int32_t heads, size_t *bytes);
+int rrt_nystrom_landmark_attn_batched_backward_f32(const float *qkv, const float *ql, const float *d_av, float *d_qkv,
+                                                   float *d_ql, int64_t b, int64_t n_padded, int32_t heads, void *workspace,
+                                                   size_t workspace_bytes, void *stream);
+int rrt_nystrom_pinv_sim_batched_backward_workspace_size(int64_t b, int32_t heads, int32_t iterations, size_t *bytes);
+int rrt_nystrom_pinv_sim_batched_backward_f32(const float *ql, const float *kl, const float *d_z, float *d_ql, float *d_kl,
+                                              int64_t b, int32_t heads, int32_t iterations, void *workspace,
+                                              size_t workspace_bytes, void *stream);
+int rrt_nystrom_landmarks_batched_backward_f32(const float *d_ql, const float *d_kl, float *d_qkv, int64_t b, int64_t n_padded,
+                                               int32_t heads, void *stream);
 
 /* TransMIL's PPEG (transmil.py:47-61): x, y [1 + side * side, dim]; row 0 (the cls token) passes through, the other rows as
  * a side x side image become x + conv7(x) + conv5(x) + conv3(x), depth-wise with zero borders.  The side is EXACTLY the

@@ -327,6 +327,13 @@ SIGNATURES = {
                                            C.c_void_p, C.c_size_t, C.POINTER(EncoderGrads), C.c_void_p, C.c_int64,
                                            C.c_void_p, C.c_size_t, C.c_float, C.c_uint64, C.POINTER(C.c_float),
                                            C.c_void_p]),
+    "rrt_encoder_tail_forward_train_f32": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderWeights), C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_float, C.c_uint64,
+                                                     C.POINTER(C.c_float), C.c_void_p]),
+    "rrt_encoder_tail_backward_f32": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderWeights), C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_size_t, C.POINTER(EncoderGrads), C.c_void_p, C.c_void_p,
+                                                C.c_int64, C.c_void_p, C.c_size_t, C.c_float, C.c_uint64,
+                                                C.POINTER(C.c_float), C.c_void_p]),
     "rrt_linear_act_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                         C.c_void_p]),
     "rrt_nystrom_workspace_size": (C.c_int, [C.POINTER(NystromDesc), C.c_int64, C.POINTER(C.c_size_t)]),
@@ -400,6 +407,28 @@ SIGNATURES = {
     "rrt_encoder_nystrom_forward_f32": (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(EncoderNystromDesc),
                                                   C.POINTER(EncoderWeights), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                   C.c_size_t, C.c_void_p]),
+    # ... and their training: the stashing forward, the backward and its stages, b in front of the sizes
+    "rrt_nystrom_batched_train_sizes": (C.c_int, [C.POINTER(NystromDesc), C.c_int64, C.c_int64, C.POINTER(C.c_size_t),
+                                                  C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_attention_batched_forward_train_f32": (C.c_int, [C.POINTER(NystromDesc), C.POINTER(NystromWeights), C.c_void_p,
+                                                                  C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
+                                                                  C.c_void_p]),
+    "rrt_nystrom_attention_batched_backward_f32": (C.c_int, [C.POINTER(NystromDesc), C.POINTER(NystromWeights), C.c_void_p,
+                                                             C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(NystromGrads),
+                                                             C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
+                                                             C.c_void_p]),
+    "rrt_nystrom_output_batched_backward_workspace_size": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_output_batched_backward_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                                                             C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rrt_nystrom_zav_batched_backward_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_void_p]),
+    "rrt_nystrom_landmark_attn_batched_backward_workspace_size": (C.c_int, [C.c_int64, C.c_int64, C.c_int32,
+                                                                            C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_landmark_attn_batched_backward_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                                                                    C.c_size_t, C.c_void_p]),
+    "rrt_nystrom_pinv_sim_batched_backward_workspace_size": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "rrt_nystrom_pinv_sim_batched_backward_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                                                               C.c_size_t, C.c_void_p]),
+    "rrt_nystrom_landmarks_batched_backward_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
     # MHIM-MIL: mask selection on the device, rows by index
     "rrt_mask_select_workspace_size": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
     "rrt_mask_select_f32": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(MaskStage), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,

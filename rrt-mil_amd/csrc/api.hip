@@ -2953,9 +2953,14 @@ int rrt_debug_transpose_batch_f32(const float* const* in, float* const* out, con
   return (int)launch_transpose_batch(tj, (hipStream_t)stream);
 }
 
-int rrt_encoder_forward_train_f32(const rrt_encoder_desc* desc, const rrt_encoder_weights* w, const float* x,
-                                  float* y, int64_t n_tokens, void* stash, size_t stash_bytes, float drop_p,
-                                  uint64_t drop_seed, const float* branch_scale, void* stream) {
+}  // extern "C"
+
+namespace {
+// rrt_encoder_forward_train_f32; shortcut (rrt_encoder_tail_forward_train_f32): what all_shortcut adds, when it is not this
+// call's x
+int encoder_forward_train(const rrt_encoder_desc* desc, const rrt_encoder_weights* w, const float* x, const float* shortcut,
+                          float* y, int64_t n_tokens, void* stash, size_t stash_bytes, float drop_p, uint64_t drop_seed,
+                          const float* branch_scale, void* stream) {
   if (!desc || !w || !x || !y || x == y) return RRT_E_INVALID;
   DropCfg dc{};
   if (make_drop(drop_p, &dc)) return RRT_E_INVALID;
@@ -3046,7 +3051,7 @@ int rrt_encoder_forward_train_f32(const rrt_encoder_desc* desc, const rrt_encode
       xin = s.xf[li];
     }
   }
-  const float* x0 = desc->all_shortcut ? x : nullptr;
+  const float* x0 = desc->all_shortcut ? (shortcut ? shortcut : x) : nullptr;
   if (!w->norm_w || !w->norm_b) return RRT_E_INVALID;
   if (desc->cr_msa) {
     const rrt_attn_weights& cw = w->crmsa;
@@ -3099,10 +3104,12 @@ int rrt_encoder_forward_train_f32(const rrt_encoder_desc* desc, const rrt_encode
   return RRT_OK;
 }
 
-int rrt_encoder_backward_f32(const rrt_encoder_desc* desc, const rrt_encoder_weights* w, const float* x,
-                             const float* dy, const void* stash, size_t stash_bytes, const rrt_encoder_grads* gr,
-                             float* dx, int64_t n_tokens, void* workspace, size_t workspace_bytes, float drop_p,
-                             uint64_t drop_seed, const float* branch_scale, void* stream) {
+// rrt_encoder_backward_f32; d_shortcut (rrt_encoder_tail_backward_f32, all_shortcut = 1): the shortcut's gradient goes there
+// instead of into dx
+int encoder_backward(const rrt_encoder_desc* desc, const rrt_encoder_weights* w, const float* x, const float* dy,
+                     const void* stash, size_t stash_bytes, const rrt_encoder_grads* gr, float* dx, float* d_shortcut,
+                     int64_t n_tokens, void* workspace, size_t workspace_bytes, float drop_p, uint64_t drop_seed,
+                     const float* branch_scale, void* stream) {
   if (!desc || !w || !x || !dy || !gr) return RRT_E_INVALID;
   DropCfg dc{};
   if (make_drop(drop_p, &dc)) return RRT_E_INVALID;
@@ -3303,9 +3310,56 @@ int rrt_encoder_backward_f32(const rrt_encoder_desc* desc, const rrt_encoder_wei
     rc = peg_backward(x);
     if (rc) return rc;
   }
-  if (dx) RRT_TRY(launch_layernorm(cur, desc->all_shortcut ? b.dx2 : nullptr, nullptr, nullptr, dx, N, D, st));
+  if (dx) RRT_TRY(launch_layernorm(cur, desc->all_shortcut && !d_shortcut ? b.dx2 : nullptr, nullptr, nullptr, dx, N, D, st));
+  if (desc->all_shortcut && d_shortcut)
+    RRT_TRY(hipMemcpyAsync(d_shortcut, b.dx2, (size_t)N * D * sizeof(float), hipMemcpyDeviceToDevice, st));
   RRT_TRY(launch_reduce_jobs(rj, st));
   return RRT_OK;
+}
+
+// the tail entries take what encoder_tail takes: no attention layer and no PEG stage in front of CR-MSA
+int check_tail_desc(const rrt_encoder_desc* desc) {
+  if (!desc) return RRT_E_INVALID;
+  if (desc->n_rmsa_layers != 0 || desc->pos != RRT_POS_NONE)
+    return unsupported("encoder_tail: n_rmsa_layers must be 0 and pos none (the part behind the attention layers)");
+  return RRT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rrt_encoder_forward_train_f32(const rrt_encoder_desc* desc, const rrt_encoder_weights* w, const float* x,
+                                  float* y, int64_t n_tokens, void* stash, size_t stash_bytes, float drop_p,
+                                  uint64_t drop_seed, const float* branch_scale, void* stream) {
+  return encoder_forward_train(desc, w, x, nullptr, y, n_tokens, stash, stash_bytes, drop_p, drop_seed, branch_scale, stream);
+}
+
+int rrt_encoder_backward_f32(const rrt_encoder_desc* desc, const rrt_encoder_weights* w, const float* x,
+                             const float* dy, const void* stash, size_t stash_bytes, const rrt_encoder_grads* gr,
+                             float* dx, int64_t n_tokens, void* workspace, size_t workspace_bytes, float drop_p,
+                             uint64_t drop_seed, const float* branch_scale, void* stream) {
+  return encoder_backward(desc, w, x, dy, stash, stash_bytes, gr, dx, nullptr, n_tokens, workspace, workspace_bytes, drop_p,
+                          drop_seed, branch_scale, stream);
+}
+
+int rrt_encoder_tail_forward_train_f32(const rrt_encoder_desc* desc, const rrt_encoder_weights* w, const float* x1,
+                                       const float* x0, float* y, int64_t n_tokens, void* stash, size_t stash_bytes,
+                                       float drop_p, uint64_t drop_seed, const float* branch_scale, void* stream) {
+  int rc = check_tail_desc(desc);
+  if (rc) return rc;
+  if (desc->all_shortcut && !x0) return RRT_E_INVALID;
+  return encoder_forward_train(desc, w, x1, x0, y, n_tokens, stash, stash_bytes, drop_p, drop_seed, branch_scale, stream);
+}
+
+int rrt_encoder_tail_backward_f32(const rrt_encoder_desc* desc, const rrt_encoder_weights* w, const float* x1, const float* dy,
+                                  const void* stash, size_t stash_bytes, const rrt_encoder_grads* gr, float* d_x1, float* d_x0,
+                                  int64_t n_tokens, void* workspace, size_t workspace_bytes, float drop_p, uint64_t drop_seed,
+                                  const float* branch_scale, void* stream) {
+  int rc = check_tail_desc(desc);
+  if (rc) return rc;
+  if (desc->all_shortcut && !d_x0) return RRT_E_INVALID;
+  return encoder_backward(desc, w, x1, dy, stash, stash_bytes, gr, d_x1, d_x0, n_tokens, workspace, workspace_bytes, drop_p,
+                          drop_seed, branch_scale, stream);
 }
 
 }  // extern "C"

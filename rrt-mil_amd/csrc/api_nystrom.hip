@@ -113,7 +113,7 @@ bool nystrom_weights_ok(const rrt_nystrom_desc* d, const rrt_nystrom_weights* w)
 // item's zeroed pad rows and the output's real rows back -- a quarter more traffic than the attention's own, against up to
 // np / n times the flops of both linears on zero rows.
 int nystrom_batched_front(const rrt_nystrom_desc* d, const rrt_nystrom_weights* w, const float* x, int64_t n, const NystromWs& ws,
-                          hipStream_t st, const float** o_compact) {
+                          hipStream_t st, const float** o_compact, float* lse = nullptr) {
   const int hd = d->heads * 64, b = (int)ws.b;
   const int64_t pad = ws.np - n;
   const size_t row3 = (size_t)3 * hd * sizeof(float), row1 = (size_t)hd * sizeof(float);
@@ -128,7 +128,7 @@ int nystrom_batched_front(const rrt_nystrom_desc* d, const rrt_nystrom_weights* 
   }
   RRT_TRY(launch_nystrom_landmarks(ws.qkv, ws.ql, ws.kl, (long)ws.np, d->heads, st, b));
   RRT_TRY(launch_nystrom_sim2(ws.ql, ws.kl, ws.a2, d->heads, st, b));
-  RRT_TRY(launch_nystrom_lattn(ws.qkv, ws.ql, ws.av, ws.lattn, (long)ws.np, d->heads, st, nullptr, b));
+  RRT_TRY(launch_nystrom_lattn(ws.qkv, ws.ql, ws.av, ws.lattn, (long)ws.np, d->heads, st, lse, b));
   RRT_TRY(launch_nystrom_pinv(ws.a2, ws.z, ws.pinv, d->heads, d->pinv_iterations, st, b));
   RRT_TRY(launch_nystrom_zav(ws.z, ws.av, ws.wz, d->heads, st, b));
   RRT_TRY(launch_nystrom_output(ws.qkv, ws.kl, ws.wz, d->residual ? w->conv_w : nullptr, ws.o, (long)ws.np, d->heads,
@@ -172,18 +172,18 @@ int nystrom_row(const rrt_nystrom_desc* d, int64_t row, float* attn, int64_t n, 
 }
 
 // ---- Nystrom attention: training (nystrom_bwd.hip)
-// the forward's workspace kept whole (what the backward reads: qkv, ql, kl, a2, z, av, wz, o) | lse [heads, 256]
+// the forward's workspace kept whole (what the backward reads: qkv, ql, kl, a2, z, av, wz, o) | lse [b, heads, 256]
 struct NystromStash {
   NystromWs f;
   float* lse;
   size_t bytes;
 };
-NystromStash carve_nystrom_stash(const rrt_nystrom_desc* d, int64_t n, char* base, bool with_o = true) {
+NystromStash carve_nystrom_stash(const rrt_nystrom_desc* d, int64_t n, char* base, bool with_o = true, int64_t b = 1) {
   NystromStash s{};
-  s.f = carve_nystrom(d, n, base, with_o);
+  s.f = carve_nystrom(d, n, base, with_o, b);
   Arena a{base};
   a.take<char>(s.f.bytes);
-  s.lse = a.take((size_t)d->heads * 256);
+  s.lse = a.take((size_t)b * d->heads * 256);
   s.bytes = a.bytes();
   return s;
 }
@@ -193,24 +193,30 @@ size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 struct NystromBwdWs {
   float *d_o, *d_qkv, *d_ql, *d_kl, *d_wz, *d_av, *d_z, *part, *pinv;
   char* lin;
+  float *d_o_c, *d_qkv_c;  // b > 1 with front padding: the two linears' compact [b * n] rows, as the forward's qkv_c / o_c
   size_t bytes;
 };
-NystromBwdWs carve_nystrom_bwd(const rrt_nystrom_desc* d, int64_t n, char* base) {
+// b sequences: every piece b times as large, in the same order (b = 1 is the single-sequence layout)
+NystromBwdWs carve_nystrom_bwd(const rrt_nystrom_desc* d, int64_t n, char* base, int64_t b = 1) {
   NystromBwdWs ws{};
   const int64_t np = (n + 255) / 256 * 256;
-  const int hd = d->heads * 64;
-  const size_t lm = (size_t)d->heads * 256 * 64, mm = (size_t)d->heads * 256 * 256;
+  const int hd = d->heads * 64, ib = (int)b;
+  const size_t lm = (size_t)b * d->heads * 256 * 64, mm = (size_t)b * d->heads * 256 * 256;
   Arena a{base};
-  ws.d_o = a.take((size_t)np * hd);
-  ws.d_qkv = a.take((size_t)np * 3 * hd);
+  ws.d_o = a.take((size_t)b * np * hd);
+  ws.d_qkv = a.take((size_t)b * np * 3 * hd);
   ws.d_ql = a.take(lm);
   ws.d_kl = a.take(lm);
   ws.d_wz = a.take(lm);
   ws.d_av = a.take(lm);
   ws.d_z = a.take(mm);
-  ws.part = a.take(max_sz(nystrom_output_bwd_floats((long)np, d->heads), nystrom_lattn_bwd_floats((long)np, d->heads)));
-  ws.pinv = a.take(nystrom_pinv_bwd_floats(d->heads, d->pinv_iterations));
-  ws.lin = a.take<char>(max_sz(linear_bwd_workspace((int)n, d->dim, hd), linear_bwd_workspace((int)n, 3 * hd, d->dim)));
+  ws.part = a.take(max_sz(nystrom_output_bwd_floats((long)np, d->heads, ib), nystrom_lattn_bwd_floats((long)np, d->heads, ib)));
+  ws.pinv = a.take(nystrom_pinv_bwd_floats(d->heads, d->pinv_iterations, ib));
+  ws.lin = a.take<char>(max_sz(linear_bwd_workspace((int)(b * n), d->dim, hd), linear_bwd_workspace((int)(b * n), 3 * hd, d->dim)));
+  if (b > 1 && np != n) {
+    ws.d_o_c = a.take((size_t)b * n * hd);
+    ws.d_qkv_c = a.take((size_t)b * n * 3 * hd);
+  }
   ws.bytes = a.bytes();
   return ws;
 }
@@ -219,13 +225,13 @@ struct LattnBwdWs {
   float *fwd, *av, *lse, *bwd;
   size_t bytes;
 };
-LattnBwdWs carve_lattn_bwd(int64_t np, int heads, char* base) {
+LattnBwdWs carve_lattn_bwd(int64_t np, int heads, char* base, int b = 1) {
   LattnBwdWs ws{};
   Arena a{base};
-  ws.fwd = a.take(nystrom_lattn_floats((long)np, heads));
-  ws.av = a.take((size_t)heads * 256 * 64);
-  ws.lse = a.take((size_t)heads * 256);
-  ws.bwd = a.take(nystrom_lattn_bwd_floats((long)np, heads));
+  ws.fwd = a.take(nystrom_lattn_floats((long)np, heads, b));
+  ws.av = a.take((size_t)b * heads * 256 * 64);
+  ws.lse = a.take((size_t)b * heads * 256);
+  ws.bwd = a.take(nystrom_lattn_bwd_floats((long)np, heads, b));
   ws.bytes = a.bytes();
   return ws;
 }
@@ -234,11 +240,11 @@ struct PinvSimBwdWs {
   float *a2, *bwd;
   size_t bytes;
 };
-PinvSimBwdWs carve_pinv_sim_bwd(int heads, int iters, char* base) {
+PinvSimBwdWs carve_pinv_sim_bwd(int heads, int iters, char* base, int b = 1) {
   PinvSimBwdWs ws{};
   Arena a{base};
-  ws.a2 = a.take((size_t)heads * 256 * 256);
-  ws.bwd = a.take(nystrom_pinv_bwd_floats(heads, iters));
+  ws.a2 = a.take((size_t)b * heads * 256 * 256);
+  ws.bwd = a.take(nystrom_pinv_bwd_floats(heads, iters, b));
   ws.bytes = a.bytes();
   return ws;
 }
@@ -287,6 +293,66 @@ int nystrom_backward(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w,
   RRT_TRY(launch_nystrom_output_backward(s.f.qkv, s.f.kl, s.f.wz, desc->residual ? w->conv_w : nullptr, b.d_o, b.d_qkv, b.d_kl,
                                          b.d_wz, grads->conv_w, b.part, np, heads, desc->residual_conv_kernel, st));
   return nystrom_backward_rest(desc, w, x, s, b, grads, dx, n, st);
+}
+
+// ---- b > 1 sequences, training.  The item rides in blockIdx.z of the tile kernels and in the batch (z) of the backward's
+// matrix products, b * heads of them: 2048 * 16 stays within a grid's 65535.
+int check_nystrom_train_batch(int64_t b) {
+  if (b < 1 || b > 2048) return unsupported("nystrom: training batch b must be in 1..2048");
+  return RRT_OK;
+}
+
+// rrt_nystrom_attention_batched_backward_f32 on carved structs, b > 1; everything checked by the caller.  The adjoint of
+// nystrom_batched_front: both linears run on the b * n real rows, d_o's pad rows (in FRONT of each item) are zero, d_qkv's are
+// dropped; n a multiple of 256 works in place.
+int nystrom_backward_batched(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w, const float* x, const float* dy,
+                             const NystromStash& s, const NystromBwdWs& bw, const rrt_nystrom_grads* grads, float* dx, int64_t n,
+                             hipStream_t st) {
+  const int heads = desc->heads, hd = heads * 64, b = (int)s.f.b;
+  const long np = (long)s.f.np;
+  const int64_t pad = s.f.np - n, rows = (int64_t)b * n;
+  const size_t row3 = (size_t)3 * hd * sizeof(float), row1 = (size_t)hd * sizeof(float);
+  RRT_TRY(launch_linear_backward(dy, pad ? s.f.o_c : s.f.o, w->out_w, pad ? bw.d_o_c : bw.d_o, grads->out_w, grads->out_b,
+                                 (int)rows, desc->dim, hd, RRT_COMPUTE_F32, bw.lin, st));
+  if (pad) {
+    RRT_TRY(hipMemset2DAsync(bw.d_o, (size_t)np * row1, 0, (size_t)pad * row1, (size_t)b, st));
+    RRT_TRY(hipMemcpy2DAsync(bw.d_o + (size_t)pad * hd, (size_t)np * row1, bw.d_o_c, (size_t)n * row1, (size_t)n * row1, (size_t)b,
+                             hipMemcpyDeviceToDevice, st));
+  }
+  RRT_TRY(launch_nystrom_output_backward(s.f.qkv, s.f.kl, s.f.wz, desc->residual ? w->conv_w : nullptr, bw.d_o, bw.d_qkv, bw.d_kl,
+                                         bw.d_wz, grads->conv_w, bw.part, np, heads, desc->residual_conv_kernel, st, b));
+  RRT_TRY(launch_nystrom_zav_backward(s.f.z, s.f.av, bw.d_wz, bw.d_z, bw.d_av, heads, st, b));
+  RRT_TRY(launch_nystrom_lattn_backward(s.f.qkv, s.f.ql, s.f.av, s.lse, bw.d_av, bw.d_qkv, bw.d_ql, bw.part, np, heads, st, b));
+  RRT_TRY(launch_nystrom_pinv_sim_backward(s.f.ql, s.f.kl, s.f.a2, bw.d_z, bw.d_ql, bw.d_kl, 1, bw.pinv, heads,
+                                           desc->pinv_iterations, st, b));
+  RRT_TRY(launch_nystrom_landmarks_backward(bw.d_ql, bw.d_kl, bw.d_qkv, np, heads, st, b));
+  float* d_rows = bw.d_qkv;
+  if (pad) {
+    RRT_TRY(hipMemcpy2DAsync(bw.d_qkv_c, (size_t)n * row3, bw.d_qkv + (size_t)pad * 3 * hd, (size_t)np * row3, (size_t)n * row3,
+                             (size_t)b, hipMemcpyDeviceToDevice, st));
+    d_rows = bw.d_qkv_c;
+  }
+  RRT_TRY(launch_nystrom_scale_q(d_rows, (long)rows, heads, st));
+  RRT_TRY(launch_linear_backward(d_rows, x, w->qkv_w, dx, grads->qkv_w, nullptr, (int)rows, 3 * hd, desc->dim, RRT_COMPUTE_F32,
+                                 bw.lin, st));
+  return RRT_OK;
+}
+
+int check_nystrom_train_batched(const rrt_nystrom_desc* desc, int64_t b, int64_t n) {
+  int rc = check_nystrom(desc, n);
+  if (!rc) rc = check_nystrom_train_batch(b);
+  if (!rc) rc = check_nystrom_rows(b, n);
+  return rc;
+}
+int check_stage_batched(int64_t b, int32_t heads) {
+  int rc = check_nystrom_heads(heads);
+  if (!rc) rc = check_nystrom_train_batch(b);
+  return rc;
+}
+int check_stage_batched(int64_t b, int64_t np, int32_t heads) {
+  int rc = check_np_heads(np, heads);
+  if (!rc) rc = check_nystrom_train_batch(b);
+  return rc;
 }
 
 int check_output_row(int64_t row, int64_t np, int32_t heads, const float* conv_w, int32_t conv_k) {
@@ -1127,6 +1193,139 @@ int rrt_nystrom_landmarks_backward_f32(const float* d_ql, const float* d_kl, flo
   int rc = check_np_heads(n_padded, heads);
   if (rc) return rc;
   return (int)launch_nystrom_landmarks_backward(d_ql, d_kl, d_qkv, (long)n_padded, heads, (hipStream_t)stream);
+}
+
+// ---- ... b sequences per launch, training (the b = 1 calls are the single-sequence ones, launch for launch)
+int rrt_nystrom_batched_train_sizes(const rrt_nystrom_desc* desc, int64_t b, int64_t n, size_t* stash_bytes,
+                                    size_t* backward_workspace_bytes) {
+  if (!stash_bytes || !backward_workspace_bytes) return RRT_E_INVALID;
+  int rc = check_nystrom_train_batched(desc, b, n);
+  if (rc) return rc;
+  *stash_bytes = carve_nystrom_stash(desc, n, nullptr, true, b).bytes;
+  *backward_workspace_bytes = carve_nystrom_bwd(desc, n, nullptr, b).bytes;
+  return RRT_OK;
+}
+
+int rrt_nystrom_attention_batched_forward_train_f32(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w, const float* x,
+                                                    float* y, int64_t b, int64_t n, void* stash, size_t stash_bytes,
+                                                    void* stream) {
+  if (!desc || !w || !x || !y) return RRT_E_INVALID;
+  int rc = check_nystrom_train_batched(desc, b, n);
+  if (rc) return rc;
+  if (!nystrom_weights_ok(desc, w)) return RRT_E_INVALID;
+  if (!stash || stash_bytes < carve_nystrom_stash(desc, n, nullptr, true, b).bytes) return RRT_E_WORKSPACE;
+  const NystromStash s = carve_nystrom_stash(desc, n, (char*)stash, true, b);
+  hipStream_t st = (hipStream_t)stream;
+  if (b == 1) return nystrom_forward(desc, w, x, y, n, s.f, st, s.lse);
+  const float* o = nullptr;
+  rc = nystrom_batched_front(desc, w, x, n, s.f, st, &o, s.lse);
+  if (rc) return rc;
+  LinearEpilogue eo{};
+  eo.bias = w->out_b;
+  RRT_TRY(launch_linear(o, w->out_w, y, (int)(b * n), desc->dim, desc->heads * 64, eo, st));
+  return RRT_OK;
+}
+
+int rrt_nystrom_attention_batched_backward_f32(const rrt_nystrom_desc* desc, const rrt_nystrom_weights* w, const float* x,
+                                               const float* dy, const void* stash, size_t stash_bytes,
+                                               const rrt_nystrom_grads* grads, float* dx, int64_t b, int64_t n, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+  if (!desc || !w || !x || !dy || !grads) return RRT_E_INVALID;
+  int rc = check_nystrom_train_batched(desc, b, n);
+  if (rc) return rc;
+  if (!nystrom_weights_ok(desc, w)) return RRT_E_INVALID;
+  if (!grads->qkv_w || !grads->out_w || !grads->out_b || (desc->residual && !grads->conv_w)) return RRT_E_INVALID;
+  if (!stash || stash_bytes < carve_nystrom_stash(desc, n, nullptr, true, b).bytes) return RRT_E_WORKSPACE;
+  if (!workspace || workspace_bytes < carve_nystrom_bwd(desc, n, nullptr, b).bytes) return RRT_E_WORKSPACE;
+  const NystromStash s = carve_nystrom_stash(desc, n, (char*)stash, true, b);
+  const NystromBwdWs bw = carve_nystrom_bwd(desc, n, (char*)workspace, b);
+  if (b == 1) return nystrom_backward(desc, w, x, dy, s, bw, grads, dx, n, (hipStream_t)stream);
+  return nystrom_backward_batched(desc, w, x, dy, s, bw, grads, dx, n, (hipStream_t)stream);
+}
+
+int rrt_nystrom_output_batched_backward_workspace_size(int64_t b, int64_t n_padded, int32_t heads, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_stage_batched(b, n_padded, heads);
+  if (rc) return rc;
+  Arena a{nullptr};
+  a.take(nystrom_output_bwd_floats((long)n_padded, heads, (int)b));
+  *bytes = a.bytes();
+  return RRT_OK;
+}
+
+int rrt_nystrom_output_batched_backward_f32(const float* qkv, const float* kl, const float* wz, const float* conv_w,
+                                            const float* d_o, float* d_qkv, float* d_kl, float* d_wz, float* d_conv_w, int64_t b,
+                                            int64_t n_padded, int32_t heads, int32_t conv_k, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  if (!qkv || !kl || !wz || !d_o || !d_qkv || !d_kl || !d_wz || (conv_w && !d_conv_w)) return RRT_E_INVALID;
+  int rc = check_stage_batched(b, n_padded, heads);
+  if (rc) return rc;
+  if (conv_w && (conv_k < 1 || conv_k % 2 == 0 || conv_k > 63)) return unsupported("nystrom: residual_conv_kernel must be odd and <= 63");
+  Arena a{(char*)workspace};
+  float* part = a.take(nystrom_output_bwd_floats((long)n_padded, heads, (int)b));
+  if (!workspace || workspace_bytes < a.bytes()) return RRT_E_WORKSPACE;
+  return (int)launch_nystrom_output_backward(qkv, kl, wz, conv_w, d_o, d_qkv, d_kl, d_wz, d_conv_w, part, (long)n_padded, heads,
+                                             conv_k, (hipStream_t)stream, (int)b);
+}
+
+int rrt_nystrom_zav_batched_backward_f32(const float* z, const float* av, const float* d_wz, float* d_z, float* d_av, int64_t b,
+                                         int32_t heads, void* stream) {
+  if (!z || !av || !d_wz || !d_z || !d_av) return RRT_E_INVALID;
+  int rc = check_stage_batched(b, heads);
+  if (rc) return rc;
+  return (int)launch_nystrom_zav_backward(z, av, d_wz, d_z, d_av, heads, (hipStream_t)stream, (int)b);
+}
+
+int rrt_nystrom_landmark_attn_batched_backward_workspace_size(int64_t b, int64_t n_padded, int32_t heads, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_stage_batched(b, n_padded, heads);
+  if (rc) return rc;
+  *bytes = carve_lattn_bwd(n_padded, heads, nullptr, (int)b).bytes;
+  return RRT_OK;
+}
+
+int rrt_nystrom_landmark_attn_batched_backward_f32(const float* qkv, const float* ql, const float* d_av, float* d_qkv, float* d_ql,
+                                                   int64_t b, int64_t n_padded, int32_t heads, void* workspace,
+                                                   size_t workspace_bytes, void* stream) {
+  if (!qkv || !ql || !d_av || !d_qkv || !d_ql) return RRT_E_INVALID;
+  int rc = check_stage_batched(b, n_padded, heads);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < carve_lattn_bwd(n_padded, heads, nullptr, (int)b).bytes) return RRT_E_WORKSPACE;
+  const LattnBwdWs ws = carve_lattn_bwd(n_padded, heads, (char*)workspace, (int)b);
+  hipStream_t st = (hipStream_t)stream;
+  RRT_TRY(launch_nystrom_lattn(qkv, ql, ws.av, ws.fwd, (long)n_padded, heads, st, ws.lse, (int)b));
+  return (int)launch_nystrom_lattn_backward(qkv, ql, ws.av, ws.lse, d_av, d_qkv, d_ql, ws.bwd, (long)n_padded, heads, st, (int)b);
+}
+
+int rrt_nystrom_pinv_sim_batched_backward_workspace_size(int64_t b, int32_t heads, int32_t iterations, size_t* bytes) {
+  if (!bytes) return RRT_E_INVALID;
+  int rc = check_stage_batched(b, heads);
+  if (!rc) rc = check_pinv_iterations(iterations);
+  if (rc) return rc;
+  *bytes = carve_pinv_sim_bwd(heads, iterations, nullptr, (int)b).bytes;
+  return RRT_OK;
+}
+
+int rrt_nystrom_pinv_sim_batched_backward_f32(const float* ql, const float* kl, const float* d_z, float* d_ql, float* d_kl,
+                                              int64_t b, int32_t heads, int32_t iterations, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+  if (!ql || !kl || !d_z || !d_ql || !d_kl) return RRT_E_INVALID;
+  int rc = check_stage_batched(b, heads);
+  if (!rc) rc = check_pinv_iterations(iterations);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < carve_pinv_sim_bwd(heads, iterations, nullptr, (int)b).bytes) return RRT_E_WORKSPACE;
+  const PinvSimBwdWs ws = carve_pinv_sim_bwd(heads, iterations, (char*)workspace, (int)b);
+  hipStream_t st = (hipStream_t)stream;
+  RRT_TRY(launch_nystrom_sim2(ql, kl, ws.a2, heads, st, (int)b));
+  return (int)launch_nystrom_pinv_sim_backward(ql, kl, ws.a2, d_z, d_ql, d_kl, 0, ws.bwd, heads, iterations, st, (int)b);
+}
+
+int rrt_nystrom_landmarks_batched_backward_f32(const float* d_ql, const float* d_kl, float* d_qkv, int64_t b, int64_t n_padded,
+                                               int32_t heads, void* stream) {
+  if (!d_ql || !d_kl || !d_qkv) return RRT_E_INVALID;
+  int rc = check_stage_batched(b, n_padded, heads);
+  if (rc) return rc;
+  return (int)launch_nystrom_landmarks_backward(d_ql, d_kl, d_qkv, (long)n_padded, heads, (hipStream_t)stream, (int)b);
 }
 
 int rrt_nystrom_output_row_f32(const float* qkv, const float* kl, const float* wz, const float* conv_w, float* o_row, int64_t row,

@@ -437,20 +437,23 @@ hipError_t launch_nystrom_attn_row(const float* qkv, const float* ql, const floa
 //                    ws: nystrom_lattn_bwd_floats
 //  pinv_sim_backward d_ql, d_kl (+)= the gradient of pinv(a2 = softmax(ql kl^T)) under d_z; ws: nystrom_pinv_bwd_floats
 //  landmarks_backward ADDS the 1 / l shares of d_ql, d_kl into the q and k thirds
-size_t nystrom_output_bwd_floats(long np, int heads);
-size_t nystrom_lattn_bwd_floats(long np, int heads);
-size_t nystrom_pinv_bwd_floats(int heads, int iters);
+// b items per launch: every layout gains a leading b (launch_nystrom_* above), d_conv_w is summed over the items, and the
+// pseudo-inverse's den (with its ties and its gradient) is ONE scalar over all b * heads matrices; b * heads <= 65535
+size_t nystrom_output_bwd_floats(long np, int heads, int b = 1);
+size_t nystrom_lattn_bwd_floats(long np, int heads, int b = 1);
+size_t nystrom_pinv_bwd_floats(int heads, int iters, int b = 1);
 hipError_t launch_nystrom_output_backward(const float* qkv, const float* kl, const float* wz, const float* conv_w,
                                           const float* d_o, float* d_qkv, float* d_kl, float* d_wz, float* d_conv_w, float* ws,
-                                          long np, int heads, int ks, hipStream_t st);
+                                          long np, int heads, int ks, hipStream_t st, int b = 1);
 hipError_t launch_nystrom_zav_backward(const float* z, const float* av, const float* d_wz, float* d_z, float* d_av, int heads,
-                                       hipStream_t st);
+                                       hipStream_t st, int b = 1);
 hipError_t launch_nystrom_lattn_backward(const float* qkv, const float* ql, const float* av, const float* lse, const float* d_av,
-                                         float* d_qkv, float* d_ql, float* ws, long np, int heads, hipStream_t st);
+                                         float* d_qkv, float* d_ql, float* ws, long np, int heads, hipStream_t st, int b = 1);
 hipError_t launch_nystrom_pinv_sim_backward(const float* ql, const float* kl, const float* a2, const float* d_z, float* d_ql,
-                                            float* d_kl, int accumulate, float* ws, int heads, int iters, hipStream_t st);
+                                            float* d_kl, int accumulate, float* ws, int heads, int iters, hipStream_t st,
+                                            int b = 1);
 hipError_t launch_nystrom_landmarks_backward(const float* d_ql, const float* d_kl, float* d_qkv, long np, int heads,
-                                             hipStream_t st);
+                                             hipStream_t st, int b = 1);
 hipError_t launch_nystrom_scale_q(float* d_qkv, long rows, int heads, hipStream_t st);
 hipError_t launch_transmil_assemble(const float* h, const float* cls, float* seq, int N, int rows, int dim, hipStream_t st);
 hipError_t launch_transmil_head(const float* x, const float* w, const float* b, float* logits, int dim, int n_classes,

@@ -20,6 +20,11 @@
 //              the softmax backward (a row of a softmax sums to one) and is left out; then the softmax backward of A2 and
 //              dql += dS2 kl, dkl += dS2^T ql.
 //   landmarks  row t of landmark j receives dql[j] / l in its q columns and dkl[j] / l in its k columns
+//
+// b sequences per launch (the trailing `b` of every launcher, 1 = the single-sequence launches, bit for bit): the item is
+// blockIdx.z of the tile kernels and rides in the head index (item * heads + head) of everything laid out per head, so each
+// item's stencil, pad rows and chunk records are its own.  den stays ONE scalar over all b * heads matrices; dconv_w is summed
+// over the items in item order.
 #include "nystrom_tiles.h"
 
 namespace {
@@ -135,7 +140,7 @@ __device__ __forceinline__ void store_record(float* __restrict__ rec, const f32x
         rec[(size_t)(64 * ct + 16 * w + 4 * (lane >> 4) + r) * ND + 16 * j + (lane & 15)] = acc[ct][j][r];
 }
 
-// ---- output backward: block (chunk of 64-token tiles, head)
+// ---- output backward: block (chunk of 64-token tiles, head, item)
 __global__ __launch_bounds__(256) void nysb_output_kernel(const float* __restrict__ qkv, const float* __restrict__ kl,
                                                           const float* __restrict__ wz, const float* __restrict__ conv_w,
                                                           const float* __restrict__ d_o, float* __restrict__ d_qkv,
@@ -147,9 +152,12 @@ __global__ __launch_bounds__(256) void nysb_output_kernel(const float* __restric
   float* Pbuf = Bbuf + 64 * LDB;
   const int ch = blockIdx.x, h = blockIdx.y, nch = gridDim.x, hd = heads * ND;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const size_t ld3 = (size_t)3 * hd;
-  const float* kl_h = kl + (size_t)h * NM * ND;
-  const float* wz_h = wz + (size_t)h * NM * ND;
+  const size_t ld3 = (size_t)3 * hd, bh = (size_t)blockIdx.z * heads + h;
+  qkv += (size_t)blockIdx.z * np * ld3;    // this item's own padded sequence: the stencil's taps stay inside [0, np)
+  d_qkv += (size_t)blockIdx.z * np * ld3;
+  d_o += (size_t)blockIdx.z * np * hd;
+  const float* kl_h = kl + bh * NM * ND;
+  const float* wz_h = wz + bh * NM * ND;
   const int s_begin = ch * sub_per_chunk, s_end = min(nsub, s_begin + sub_per_chunk);
   f32x4 accW[4][4], accK[4][4];
 #pragma unroll
@@ -287,7 +295,7 @@ __global__ __launch_bounds__(256) void nysb_output_kernel(const float* __restric
         for (int j = 0; j < 4; ++j) dst[(size_t)r * ld3 + 2 * hd + 16 * j] = 0.f;
     }
   }
-  const size_t rec = (size_t)h * nch + ch;
+  const size_t rec = bh * nch + ch;
   store_record(pW + rec * NM * ND, accW);
   store_record(pK + rec * NM * ND, accK);
   __syncthreads();
@@ -296,14 +304,18 @@ __global__ __launch_bounds__(256) void nysb_output_kernel(const float* __restric
   if (threadIdx.x < 64) pC[rec * 64 + threadIdx.x] = ((lds[threadIdx.x] + lds[64 + threadIdx.x]) + lds[128 + threadIdx.x]) + lds[192 + threadIdx.x];
 }
 
-// out[h, i] (+)= the sum over the chunks, in chunk order, of part[h, c, i]; i < out_elems <= elems
+// out[h, i] (+)= the sum over the items, in item order, and within an item over the chunks, in chunk order, of
+// part[item, h, c, i]; i < out_elems <= elems.  (items = 1 with the grid's y over item * heads + head: a sum per item.)
 __global__ __launch_bounds__(256) void nysb_merge_kernel(const float* __restrict__ part, float* __restrict__ out, int nch,
-                                                         int elems, int out_elems, int acc) {
+                                                         int elems, int out_elems, int acc, int items) {
   const int h = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   if (i >= out_elems) return;
-  const float* p = part + (size_t)h * nch * elems + i;
+  const size_t item_stride = (size_t)gridDim.y * nch * elems;
   float s = 0.f;
-  for (int c = 0; c < nch; ++c) s += p[(size_t)c * elems];
+  for (int it = 0; it < items; ++it) {
+    const float* p = part + it * item_stride + (size_t)h * nch * elems + i;
+    for (int c = 0; c < nch; ++c) s += p[(size_t)c * elems];
+  }
   float* o = out + (size_t)h * out_elems + i;
   *o = acc ? *o + s : s;
 }
@@ -319,7 +331,7 @@ __global__ __launch_bounds__(256) void nysb_rowdot_kernel(const float* __restric
   if (lane == 0) d3[row] = s;
 }
 
-// ---- landmark attention backward: block (chunk of 64-key tiles, head)
+// ---- landmark attention backward: block (chunk of 64-key tiles, head, item)
 __global__ __launch_bounds__(256) void nysb_lattn_kernel(const float* __restrict__ qkv, const float* __restrict__ ql,
                                                          const float* __restrict__ lse, const float* __restrict__ d3,
                                                          const float* __restrict__ d_av, float* __restrict__ d_qkv,
@@ -330,9 +342,11 @@ __global__ __launch_bounds__(256) void nysb_lattn_kernel(const float* __restrict
   float* Pbuf = Bbuf + 64 * LDB;
   const int ch = blockIdx.x, h = blockIdx.y, nch = gridDim.x, hd = heads * ND;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const size_t ld3 = (size_t)3 * hd;
-  const float* ql_h = ql + (size_t)h * NM * ND;
-  const float* dav_h = d_av + (size_t)h * NM * ND;
+  const size_t ld3 = (size_t)3 * hd, bh = (size_t)blockIdx.z * heads + h;
+  qkv += (size_t)blockIdx.z * nsub * 64 * ld3;
+  d_qkv += (size_t)blockIdx.z * nsub * 64 * ld3;
+  const float* ql_h = ql + bh * NM * ND;
+  const float* dav_h = d_av + bh * NM * ND;
   const int s_begin = ch * sub_per_chunk, s_end = min(nsub, s_begin + sub_per_chunk);
   float lreg[4][4], dreg[4][4];           // of landmark 64 lb + 16 j + (lane & 15)
   f32x4 accQ[4][4];
@@ -340,8 +354,8 @@ __global__ __launch_bounds__(256) void nysb_lattn_kernel(const float* __restrict
   for (int lb = 0; lb < 4; ++lb)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      lreg[lb][j] = lse[(size_t)h * NM + 64 * lb + 16 * j + (lane & 15)];
-      dreg[lb][j] = d3[(size_t)h * NM + 64 * lb + 16 * j + (lane & 15)];
+      lreg[lb][j] = lse[bh * NM + 64 * lb + 16 * j + (lane & 15)];
+      dreg[lb][j] = d3[bh * NM + 64 * lb + 16 * j + (lane & 15)];
       accQ[lb][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
   for (int sc = s_begin; sc < s_end; ++sc) {
@@ -421,7 +435,7 @@ __global__ __launch_bounds__(256) void nysb_lattn_kernel(const float* __restrict
         dst[(size_t)r * ld3 + hd + 16 * j] += dv[j][r];
       }
   }
-  store_record(pQ + ((size_t)h * nch + ch) * NM * ND, accQ);
+  store_record(pQ + (bh * nch + ch) * NM * ND, accQ);
 }
 
 // ---- pinv backward pieces
@@ -435,10 +449,10 @@ __global__ __launch_bounds__(256) void nysb_sums_kernel(const float* __restrict_
     rs += fabsf(a[(size_t)t * NM + i]);
     cs += fabsf(a[(size_t)i * NM + t]);
   }
-  rsum[h * NM + t] = rs;
-  csum[h * NM + t] = cs;
+  rsum[(size_t)h * NM + t] = rs;
+  csum[(size_t)h * NM + t] = cs;
 }
-// scal = {mr, mc, mr * mc, the number of columns whose sum equals mc} over all heads: one block
+// scal = {mr, mc, mr * mc, the number of columns whose sum equals mc} over all heads (of all items): one block
 __global__ __launch_bounds__(256) void nysb_scal_kernel(const float* __restrict__ rsum, const float* __restrict__ csum,
                                                         float* __restrict__ scal, int n) {
   __shared__ float red[2][256];
@@ -502,22 +516,38 @@ __global__ __launch_bounds__(256) void nysb_dot_kernel(const float* __restrict__
   }
   if (t == 0) part[h] = red[0];
 }
-// da2[i][j] += dz[j][i] / den + (column (h, j) attains mc ? dden mr / ties : 0), dden = -(sum_h part[h]) / den with
-// part[h] = sum(d_z . zd) of head h, the tangent of the forward sweep
-__global__ __launch_bounds__(256) void nysb_da2_z0_kernel(float* __restrict__ da2, const float* __restrict__ dz,
-                                                          const float* __restrict__ csum, const float* __restrict__ scal,
-                                                          const float* __restrict__ part, int heads) {
-  __shared__ float tile[16][17];
-  const float mr = scal[0], mc = scal[1], den = scal[2], ties = scal[3];
+// scal[4] = the sum of the n per-matrix partials in a fixed order: thread t sums partials 64 t .. 64 t + 63 in index order
+// (and, beyond 256 * 64 of them, every 256th run of 64 after it), thread 0 adds the runs' sums in run order.  Up to 64
+// partials that is the plain sum in index order.
+__global__ __launch_bounds__(256) void nysb_tot_kernel(const float* __restrict__ part, float* __restrict__ scal, int n) {
+  __shared__ float run[256];
+  const int t = threadIdx.x, nrun = (n + 63) / 64;
   float tot = 0.f;
-  for (int i = 0; i < heads; ++i) tot += part[i];
+  for (int r0 = 0; r0 < nrun; r0 += 256) {
+    float s = 0.f;
+    const int beg = (r0 + t) * 64, end = min(n, beg + 64);
+    for (int i = beg; i < end; ++i) s += part[i];
+    __syncthreads();
+    run[t] = s;
+    __syncthreads();
+    if (t == 0)
+      for (int r = 0; r < min(256, nrun - r0); ++r) tot += run[r];
+  }
+  if (t == 0) scal[4] = tot;
+}
+// da2[i][j] += dz[j][i] / den + (column (h, j) attains mc ? dden mr / ties : 0), dden = -(sum_h part[h]) / den with
+// part[h] = sum(d_z . zd) of matrix h, the tangent of the forward sweep; their sum is scal[4] (nysb_tot_kernel)
+__global__ __launch_bounds__(256) void nysb_da2_z0_kernel(float* __restrict__ da2, const float* __restrict__ dz,
+                                                          const float* __restrict__ csum, const float* __restrict__ scal) {
+  __shared__ float tile[16][17];
+  const float mr = scal[0], mc = scal[1], den = scal[2], ties = scal[3], tot = scal[4];
   const float share = (-tot / den) * mr / ties;
   const int h = blockIdx.z, ti = blockIdx.y * 16, tj = blockIdx.x * 16, x = threadIdx.x & 15, y = threadIdx.x >> 4;
   tile[y][x] = dz[((size_t)h * NM + tj + y) * NM + ti + x];            // dz[j][i]
   __syncthreads();
   const int col = tj + x;
   const size_t o = ((size_t)h * NM + ti + y) * NM + col;
-  da2[o] += tile[x][y] / den + (csum[h * NM + col] == mc ? share : 0.f);
+  da2[o] += tile[x][y] / den + (csum[(size_t)h * NM + col] == mc ? share : 0.f);
 }
 // ds = a (da - rowsum(da . a)), in place over da: block (row, head)
 __global__ __launch_bounds__(256) void nysb_softmax_bwd_kernel(const float* __restrict__ a2, float* __restrict__ da2) {
@@ -546,14 +576,15 @@ __global__ __launch_bounds__(256) void nysb_sub_kernel(float* __restrict__ a, co
   ((float4*)a)[i] = x;
 }
 
-// ---- landmarks backward: block (row t, q | k): d_qkv[t, third, c] += d[h, t / l, c % 64] / l
+// ---- landmarks backward: block (row t, q | k, item): d_qkv[t, third, c] += d[h, t / l, c % 64] / l
 __global__ void nysb_landmarks_kernel(const float* __restrict__ d_ql, const float* __restrict__ d_kl, float* __restrict__ d_qkv,
                                       int l, int heads) {
   const int hd = heads * ND, c = threadIdx.x;
   if (c >= hd) return;
-  const size_t t = blockIdx.x;
+  const size_t t = blockIdx.x, item = blockIdx.z;
   const float* src = blockIdx.y ? d_kl : d_ql;
-  d_qkv[t * 3 * hd + (size_t)blockIdx.y * hd + c] += src[((size_t)(c >> 6) * NM + t / l) * ND + (c & 63)] / (float)l;
+  d_qkv[(item * gridDim.x + t) * 3 * hd + (size_t)blockIdx.y * hd + c] +=
+      src[((item * heads + (size_t)(c >> 6)) * NM + t / l) * ND + (c & 63)] / (float)l;
 }
 
 // the q columns of rows [0, rows) times 64^-0.5 (the forward scales q in the qkv linear's epilogue)
@@ -566,66 +597,73 @@ __global__ __launch_bounds__(256) void nysb_scale_q_kernel(float* __restrict__ d
 
 }  // namespace
 
-// chunk partials of the output backward: dW | dkl [heads, nch, 256, 64] each, dconv_w [heads, nch, 64]
-size_t nystrom_output_bwd_floats(long np, int heads) {
+// chunk partials of the output backward: dW | dkl [b, heads, nch, 256, 64] each, dconv_w [b, heads, nch, 64]
+size_t nystrom_output_bwd_floats(long np, int heads, int b) {
   int nsub, spc, nch;
   nystrom_chunks(np, &nsub, &spc, &nch);
-  return (size_t)heads * nch * (2 * NM * ND + 64);
+  return (size_t)b * heads * nch * (2 * NM * ND + 64);
 }
-// of the landmark-attention backward: dql [heads, nch, 256, 64] | d3 [heads, 256]
-size_t nystrom_lattn_bwd_floats(long np, int heads) {
+// of the landmark-attention backward: dql [b, heads, nch, 256, 64] | d3 [b, heads, 256]
+size_t nystrom_lattn_bwd_floats(long np, int heads, int b) {
   int nsub, spc, nch;
   nystrom_chunks(np, &nsub, &spc, &nch);
-  return (size_t)heads * nch * NM * ND + (size_t)heads * NM;
+  return (size_t)b * heads * nch * NM * ND + (size_t)b * heads * NM;
 }
-// z_0 .. z_{iters-1} | xz, t1, t2, t3, dta, dtb, dxz, dz, dz', da2 | row sums, column sums | scalars, per-head partials
-size_t nystrom_pinv_bwd_floats(int heads, int iters) {
-  return (size_t)heads * NM * NM * (iters + 10) + (size_t)heads * NM * 2 + 128;
+// per matrix (b * heads of them): z_0 .. z_{iters-1} | xz, t1, t2, t3, dta, dtb, dxz, dz, dz', da2 | row sums, column sums;
+// then 64 scalars | one partial per matrix, in whole runs of 64 (b = 1: the 64 + 64 of the single-sequence carve)
+size_t nystrom_pinv_bwd_floats(int heads, int iters, int b) {
+  const size_t nmat = (size_t)b * heads;
+  return nmat * NM * NM * (iters + 10) + nmat * NM * 2 + 64 + (nmat + 63) / 64 * 64;
 }
 
 hipError_t launch_nystrom_output_backward(const float* qkv, const float* kl, const float* wz, const float* conv_w,
                                           const float* d_o, float* d_qkv, float* d_kl, float* d_wz, float* d_conv_w, float* ws,
-                                          long np, int heads, int ks, hipStream_t st) {
+                                          long np, int heads, int ks, hipStream_t st, int b) {
   int nsub, spc, nch;
   nystrom_chunks(np, &nsub, &spc, &nch);
+  const int hb = b * heads;
   float* pW = ws;
-  float* pK = pW + (size_t)heads * nch * NM * ND;
-  float* pC = pK + (size_t)heads * nch * NM * ND;
-  nysb_output_kernel<<<dim3(nch, heads), 256, 0, st>>>(qkv, kl, wz, conv_w, d_o, d_qkv, pW, pK, pC, (int)np, heads, ks, nsub, spc);
+  float* pK = pW + (size_t)hb * nch * NM * ND;
+  float* pC = pK + (size_t)hb * nch * NM * ND;
+  nysb_output_kernel<<<dim3(nch, heads, b), 256, 0, st>>>(qkv, kl, wz, conv_w, d_o, d_qkv, pW, pK, pC, (int)np, heads, ks, nsub, spc);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  nysb_merge_kernel<<<dim3(NM * ND / 256, heads), 256, 0, st>>>(pW, d_wz, nch, NM * ND, NM * ND, 0);
-  nysb_merge_kernel<<<dim3(NM * ND / 256, heads), 256, 0, st>>>(pK, d_kl, nch, NM * ND, NM * ND, 0);
-  if (conv_w) nysb_merge_kernel<<<dim3(1, heads), 256, 0, st>>>(pC, d_conv_w, nch, 64, ks, 0);
+  nysb_merge_kernel<<<dim3(NM * ND / 256, hb), 256, 0, st>>>(pW, d_wz, nch, NM * ND, NM * ND, 0, 1);
+  nysb_merge_kernel<<<dim3(NM * ND / 256, hb), 256, 0, st>>>(pK, d_kl, nch, NM * ND, NM * ND, 0, 1);
+  if (conv_w) nysb_merge_kernel<<<dim3(1, heads), 256, 0, st>>>(pC, d_conv_w, nch, 64, ks, 0, b);   // summed over the items
   return hipGetLastError();
 }
 
 hipError_t launch_nystrom_zav_backward(const float* z, const float* av, const float* d_wz, float* d_z, float* d_av, int heads,
-                                       hipStream_t st) {
-  hipError_t e = gemm(false, true, d_wz, av, d_z, nullptr, NM, NM, ND, heads, 1.f, 0.f, 0.f, 0.f, 0, st);   // dW AV^T
+                                       hipStream_t st, int b) {
+  hipError_t e = gemm(false, true, d_wz, av, d_z, nullptr, NM, NM, ND, b * heads, 1.f, 0.f, 0.f, 0.f, 0, st);   // dW AV^T
   if (e != hipSuccess) return e;
-  return gemm(true, false, z, d_wz, d_av, nullptr, NM, ND, NM, heads, 1.f, 0.f, 0.f, 0.f, 0, st);          // Z^T dW
+  return gemm(true, false, z, d_wz, d_av, nullptr, NM, ND, NM, b * heads, 1.f, 0.f, 0.f, 0.f, 0, st);          // Z^T dW
 }
 
 hipError_t launch_nystrom_lattn_backward(const float* qkv, const float* ql, const float* av, const float* lse, const float* d_av,
-                                         float* d_qkv, float* d_ql, float* ws, long np, int heads, hipStream_t st) {
+                                         float* d_qkv, float* d_ql, float* ws, long np, int heads, hipStream_t st, int b) {
   int nsub, spc, nch;
   nystrom_chunks(np, &nsub, &spc, &nch);
+  const int hb = b * heads;
   float* pQ = ws;
-  float* d3 = pQ + (size_t)heads * nch * NM * ND;
-  nysb_rowdot_kernel<<<dim3(heads * NM / 4), 256, 0, st>>>(d_av, av, d3, heads * NM);
+  float* d3 = pQ + (size_t)hb * nch * NM * ND;
+  nysb_rowdot_kernel<<<dim3(hb * NM / 4), 256, 0, st>>>(d_av, av, d3, hb * NM);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  nysb_lattn_kernel<<<dim3(nch, heads), 256, 0, st>>>(qkv, ql, lse, d3, d_av, d_qkv, pQ, heads, nsub, spc);
+  nysb_lattn_kernel<<<dim3(nch, heads, b), 256, 0, st>>>(qkv, ql, lse, d3, d_av, d_qkv, pQ, heads, nsub, spc);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  nysb_merge_kernel<<<dim3(NM * ND / 256, heads), 256, 0, st>>>(pQ, d_ql, nch, NM * ND, NM * ND, 0);
+  nysb_merge_kernel<<<dim3(NM * ND / 256, hb), 256, 0, st>>>(pQ, d_ql, nch, NM * ND, NM * ND, 0, 1);
   return hipGetLastError();
 }
 
-// d_ql, d_kl (+)= the gradient of pinv_iter(a2 = softmax(ql kl^T), iters) under d_z
+// d_ql, d_kl (+)= the gradient of pinv_iter(a2 = softmax(ql kl^T), iters) under d_z.  b items: every matrix of every item is
+// a "head" below -- den, its ties and d den are taken over all of them
 hipError_t launch_nystrom_pinv_sim_backward(const float* ql, const float* kl, const float* a2, const float* d_z, float* d_ql,
-                                            float* d_kl, int accumulate, float* ws, int heads, int iters, hipStream_t st) {
+                                            float* d_kl, int accumulate, float* ws, int heads_per_item, int iters, hipStream_t st,
+                                            int b) {
+  const int heads = b * heads_per_item;
   const size_t all = (size_t)NM * NM * heads;
   float* zs = ws;
   float* xz = zs + all * iters;
@@ -682,6 +720,7 @@ hipError_t launch_nystrom_pinv_sim_backward(const float* ql, const float* kl, co
       NYSB_TRY(gemm(false, false, z, t3, zs + all * (i + 1), nullptr, NM, NM, NM, heads, 0.25f, 0.f, 0.f, 0.f, 0, st));
   }
   nysb_dot_kernel<<<heads, 256, 0, st>>>(d_z, zd, part);
+  nysb_tot_kernel<<<1, 256, 0, st>>>(part, scal, heads);
   NYSB_TRY(hipGetLastError());
   NYSB_TRY(hipMemcpyAsync(dz, d_z, all * sizeof(float), hipMemcpyDeviceToDevice, st));
   for (int i = iters - 1; i >= 0; --i) {
@@ -702,7 +741,7 @@ hipError_t launch_nystrom_pinv_sim_backward(const float* ql, const float* kl, co
     dzn = sw;
   }
   // z0 = a2^T / den
-  nysb_da2_z0_kernel<<<dim3(NM / 16, NM / 16, heads), 256, 0, st>>>(da2, dz, csum, scal, part, heads);
+  nysb_da2_z0_kernel<<<dim3(NM / 16, NM / 16, heads), 256, 0, st>>>(da2, dz, csum, scal);
   nysb_softmax_bwd_kernel<<<dim3(NM, heads), 256, 0, st>>>(a2, da2);
   NYSB_TRY(hipGetLastError());
   NYSB_TRY(gemm(false, false, da2, kl, d_ql, nullptr, NM, ND, NM, heads, 1.f, 0.f, 0.f, 0.f, accumulate, st));   // dS2 kl
@@ -712,8 +751,8 @@ hipError_t launch_nystrom_pinv_sim_backward(const float* ql, const float* kl, co
 }
 
 hipError_t launch_nystrom_landmarks_backward(const float* d_ql, const float* d_kl, float* d_qkv, long np, int heads,
-                                             hipStream_t st) {
-  nysb_landmarks_kernel<<<dim3((unsigned)np, 2), heads * ND, 0, st>>>(d_ql, d_kl, d_qkv, (int)(np / NM), heads);
+                                             hipStream_t st, int b) {
+  nysb_landmarks_kernel<<<dim3((unsigned)np, 2, b), heads * ND, 0, st>>>(d_ql, d_kl, d_qkv, (int)(np / NM), heads);
   return hipGetLastError();
 }
 

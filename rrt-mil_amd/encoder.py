@@ -9,6 +9,9 @@ into librrt_hip.so (rrt_encoder_forward_f32, include/rrt_hip.h) per bag on the
 current HIP stream.  With gradients enabled and something to differentiate the call goes
 through a torch.autograd.Function over rrt_encoder_forward_train_f32 /
 rrt_encoder_backward_f32 (train() adds proj dropout and stochastic depth, eval() does not).
+The Nystrom ablations (attn='ntrans' / region_attn='ntrans') are inference by default (ONE rrt_encoder_nystrom_forward_f32
+call); after ``enc.enable_training()`` a call that needs a graph takes a layer path: NystromAttention's HIP forward-with-stash
+and backward per layer (region mode: the batched pair), torch glue, and the encoder's own training kernels behind the layers.
 There is no PyTorch/CPU fallback: CPU tensors and configurations outside the HIP path raise.
 """
 import os
@@ -250,6 +253,65 @@ class _EncoderFunction(torch.autograd.Function):
         return (None, dx) + tuple(grads)      # (the stash lives as long as the graph node: retain_graph works)
 
 
+class _EncoderTailFunction(torch.autograd.Function):
+    """What stands behind the attention layers of a Nystrom-ablation encoder -- CR-MSA, all_shortcut (which adds the encoder's
+    ORIGINAL input x0) and the final LayerNorm -- on the encoder's own training kernels: rrt_encoder_tail_forward_train_f32 /
+    rrt_encoder_tail_backward_f32 with a copy of the descriptor that has no R-MSA layer and no PEG stage.  ``params`` are
+    enc._tail_parameters(); the conventions are _EncoderFunction's."""
+
+    @staticmethod
+    def forward(ctx, enc, x1, x0, *params):
+        lib = _lib.load()
+        x1 = x1.detach().float().contiguous()
+        x0 = x0.detach().float().contiguous() if x0 is not None else None
+        n, dev = x1.shape[0], x1.device
+        desc = enc._tail_desc()
+        stash_b, ws_b = C.c_size_t(), C.c_size_t()
+        _lib.check(lib.rrt_encoder_train_sizes(C.byref(desc), n, C.byref(stash_b), C.byref(ws_b)), "rrt_encoder_train_sizes")
+        stash = torch.empty(stash_b.value, dtype=torch.uint8, device=dev)
+        y = torch.empty_like(x1)
+        w = enc._weights()
+        drop_p = float(enc.drop_out) if enc.training else 0.0
+        seed = enc._next_drop_seed() if drop_p > 0 else 0
+        branch = enc._tail_branch_scales()
+        with torch.cuda.device(dev):
+            rc = lib.rrt_encoder_tail_forward_train_f32(C.byref(desc), C.byref(w), x1.data_ptr(),
+                                                        x0.data_ptr() if x0 is not None else None, y.data_ptr(), n,
+                                                        stash.data_ptr(), stash.numel(), drop_p, seed, branch,
+                                                        torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, "rrt_encoder_tail_forward_train_f32")
+        ctx.enc, ctx.desc, ctx.stash, ctx.ws_bytes, ctx.drop = enc, desc, stash, ws_b.value, (drop_p, seed, branch)
+        ctx.versions = [(p_.data_ptr(), p_._version) for p_ in params]
+        ctx.has_x0 = x0 is not None
+        ctx.save_for_backward(x1)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        enc = ctx.enc
+        (x1,) = ctx.saved_tensors
+        if ctx.versions != [(p_.data_ptr(), p_._version) for p_ in enc._tail_parameters()]:
+            raise RuntimeError("RRTEncoder: a parameter was modified in place (or replaced) between this forward and "
+                               "its backward; the backward kernels read the live weights, so the gradients would be "
+                               "wrong -- run the forward again")
+        n, dev = x1.shape[0], x1.device
+        dy = dy.contiguous().float()
+        grads, gstruct = enc._grad_buffers(dev, tail=True)
+        d_x1 = torch.empty_like(x1)
+        d_x0 = torch.empty_like(x1) if ctx.has_x0 else None
+        ws = torch.empty(ctx.ws_bytes, dtype=torch.uint8, device=dev)
+        w = enc._weights()
+        with torch.cuda.device(dev):
+            rc = lib.rrt_encoder_tail_backward_f32(C.byref(ctx.desc), C.byref(w), x1.data_ptr(), dy.data_ptr(),
+                                                   ctx.stash.data_ptr(), ctx.stash.numel(), C.byref(gstruct), d_x1.data_ptr(),
+                                                   d_x0.data_ptr() if d_x0 is not None else None, n, ws.data_ptr(), ws.numel(),
+                                                   ctx.drop[0], ctx.drop[1], ctx.drop[2],
+                                                   torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, "rrt_encoder_tail_backward_f32")
+        return (None, d_x1, d_x0) + tuple(grads)
+
+
 _HWQ_WARNED = False
 
 
@@ -345,6 +407,7 @@ class RRTEncoder(nn.Module):
         # projections emulated in fp32 on the bf16 matrix cores, ~1e-6 from the exact path, include/rrt_hip.h)
         self.compute_dtype = None
         self._ws = None           # cached workspace tensor (grown on demand, per device)
+        self._train_enabled = False   # the Nystrom ablations' opt-in training path (enable_training)
         if need_init:
             self.apply(initialize_weights)
 
@@ -362,6 +425,21 @@ class RRTEncoder(nn.Module):
         self.__dict__.update(st)
         self.__dict__.setdefault("_ws", None)
         self.__dict__.setdefault("_nys_mode", 0)
+        self.__dict__.setdefault("_train_enabled", False)
+
+    def enable_training(self, mode=True):
+        """The Nystrom ablations (attn='ntrans' / region_attn='ntrans') are inference by default.  With this on, a call on
+        one bag that needs a graph -- or ``train()`` with dropout / drop-path -- takes a layer path instead of raising: the
+        attention layers through NystromAttention's HIP forward-with-stash and backward (region mode: the batched pair, ONE
+        pseudo-inverse scale over all regions), the rest of the encoder on its own training kernels.  Switches the held
+        NystromAttention modules too.  A plain attribute: not part of ``state_dict``, kept by pickle and deepcopy.  The R-MSA
+        encoder trains without it.  Returns self."""
+        self._train_enabled = bool(mode)
+        for layer in self.layers.children():
+            na = self._nystrom_of(layer)
+            if na is not None:
+                na.enable_training(mode)
+        return self
 
     # ------------------------------------------------------------------ C-ABI plumbing
     @staticmethod
@@ -461,10 +539,11 @@ class RRTEncoder(nn.Module):
         self.__dict__["_w_struct"] = w
         return w
 
-    def _grad_buffers(self, device):
+    def _grad_buffers(self, device, tail=False):
         """Fresh gradient tensors in the order of self.parameters() and the C struct pointing into them.
         LayerNorm pairs share one [2, dim] buffer (d gamma, d beta); pe.bias gets zeros (its gradient is
-        exactly zero: a per-head constant added to every score cancels in the softmax)."""
+        exactly zero: a per-head constant added to every score cancels in the softmax).  tail: those of
+        _tail_parameters() alone (CR-MSA and the final LayerNorm)."""
         D = self.final_dim
         gs = _lib.EncoderGrads()
         by_name = {}
@@ -506,7 +585,7 @@ class RRTEncoder(nn.Module):
                     setattr(ag, nm + "_b", gb.data_ptr())
 
         gs.norm = ln("norm")
-        for i, layer in enumerate(self.layers.children()):
+        for i, layer in enumerate(self.layers.children() if not tail else ()):
             attn(f"layers.{i}.", layer, gs.rmsa[i])
         if self._desc.cr_msa:
             attn("cr_msa.", self.cr_msa, gs.crmsa)
@@ -519,6 +598,8 @@ class RRTEncoder(nn.Module):
                 gphi = torch.empty_like(self.cr_msa.attn.phi)
                 by_name["cr_msa.attn.phi"] = gphi
                 gs.phi = gphi.data_ptr()
+        if tail:
+            return [by_name[name] for name, _ in self._tail_named_parameters()], gs
         if self._desc.pos:
             for i, name in enumerate(("proj", "proj1", "proj2")):
                 conv = getattr(self.pos_embedding, name, None)
@@ -586,7 +667,7 @@ class RRTEncoder(nn.Module):
             raise ValueError(f"expected feature dim {self.final_dim}, got {d}")
         y = out if out is not None else torch.empty_like(x2d)
         if self._nys_mode:
-            return self._forward_bag_nystrom(x2d, y)
+            return self._forward_bag_nystrom(x2d, y, out)
         if self._stochastic():
             # train() without a graph (torch.no_grad(): MC dropout, EMA / teacher forwards, frozen models): the
             # reference still applies proj dropout and stochastic depth; same kernels as the training forward, the
@@ -623,8 +704,96 @@ class RRTEncoder(nn.Module):
         d.mode, d.attn = self._nys_mode, self._nystrom_of(first)._desc()
         return d
 
-    def _forward_bag_nystrom(self, x2d, y):
-        """attn='ntrans' / region_attn='ntrans': ONE rrt_encoder_nystrom_forward_f32 call.  Inference only."""
+    # ------------------------------------------------------------------ the Nystrom ablations' opt-in training path
+    def _tail_named_parameters(self):
+        return [(n, p) for n, p in self.named_parameters() if n.startswith("cr_msa.") or n.startswith("norm.")]
+
+    def _tail_parameters(self):
+        return [p for _, p in self._tail_named_parameters()]
+
+    def _tail_desc(self):
+        d = _lib.EncoderDesc.from_buffer_copy(self._desc)
+        d.n_rmsa_layers, d.pos, d.compute, d.weights16_valid = 0, _lib.POS_NONE, _lib.COMPUTE_F32, 0
+        return d
+
+    def _tail_branch_scales(self):
+        """this call's stochastic-depth multipliers of CR-MSA's two branches, where the tail's descriptor (no R-MSA layer)
+        looks for them: index 0"""
+        full = self.__dict__.get("_branch_now")
+        if full is None:
+            return None
+        n, L = _lib.RRT_MAX_RMSA_LAYERS + 1, self._desc.n_rmsa_layers
+        arr = (C.c_float * (2 * n))(*([1.0] * (2 * n)))
+        arr[0], arr[n] = full[L], full[n + L]
+        return arr
+
+    def _pos_torch(self, x):
+        """PEG / PPEG as torch ops on the holders' convs (modules/emb_position.py:24-82): the tokens wrapped to an H x H image
+        (PPEG: zero rows up to 7 x 7), depth-wise convs + identity, the first N tokens kept"""
+        N, D = x.shape
+        H = math.isqrt(N - 1) + 1 if N > 1 else 1
+        xh = torch.cat([x, x[:H * H - N]])
+        if self._desc.pos == _lib.POS_PPEG and H < 7:
+            xh, H = torch.cat([xh, x.new_zeros(49 - H * H, D)]), 7
+        img = xh.t().reshape(1, D, H, H)
+        out = img
+        for name in ("proj", "proj1", "proj2"):
+            conv = getattr(self.pos_embedding, name, None)
+            if conv is not None:
+                out = out + conv(img)
+        return out.reshape(D, H * H).t()[:N]
+
+    def _forward_bag_nystrom_train(self, x2d):
+        """The layer path (enable_training): each attention layer is x + NystromAttention(LN(x)) -- whole-bag mode through the
+        single-sequence autograd Function, region mode through the batched one with b = R, n = P -- with LayerNorm, the
+        partition, the FFN and PEG / PPEG as torch ops under autograd on the holders' parameters; CR-MSA, all_shortcut and the
+        final LayerNorm run on the encoder's training kernels (_EncoderTailFunction)."""
+        from .geometry import region_grid
+        F = torch.nn.functional
+        d, (N, D) = self._desc, x2d.shape
+        full = self.__dict__["_branch_now"] = self._branch_scales()
+        nb = _lib.RRT_MAX_RMSA_LAYERS + 1
+        use_pos = d.pos != _lib.POS_NONE
+        try:
+            with torch.autocast("cuda", enabled=False):      # exact fp32 in every context, as the one-call path
+                x = x2d
+                if use_pos and d.pos_pos == -1:
+                    x = self._pos_torch(x)
+                for li, layer in enumerate(self.layers.children()):
+                    if use_pos and li == 1 and d.pos_pos == 0:
+                        x = self._pos_torch(x)
+                    na = self._nystrom_of(layer)
+                    u = F.layer_norm(x, (D,), layer.norm.weight, layer.norm.bias)
+                    if self._nys_mode == _lib.NYSTROM_BAG:
+                        z = na(u.unsqueeze(0))[0]
+                    else:
+                        g = region_grid(N, d.region_num, d.region_size, d.min_region_num, d.min_region_ratio)
+                        rs, s = g.regions_side, g.region_size
+                        up = torch.cat([u, u.new_zeros(g.add_length, D)]) if g.add_length else u
+                        U = up.reshape(rs, s, rs, s, D).permute(0, 2, 1, 3, 4).reshape(g.R, g.P, D)
+                        z = na.forward_batch(U)
+                        z = z.reshape(rs, rs, s, s, D).permute(0, 2, 1, 3, 4).reshape(g.Np, D)[:N]
+                    x = x + (z if full is None else z * float(full[li]))
+                    if layer.ffn:
+                        h = layer.mlp.drop(layer.mlp.act(layer.mlp.fc1(F.layer_norm(x, (D,), layer.norm2.weight, layer.norm2.bias))))
+                        h = layer.mlp.drop(layer.mlp.fc2(h))
+                        x = x + (h if full is None else h * float(full[nb + li]))
+                return _EncoderTailFunction.apply(self, x, x2d if d.all_shortcut else None, *self._tail_parameters())
+        finally:
+            self.__dict__["_branch_now"] = None
+
+    def _forward_bag_nystrom(self, x2d, y, out=None):
+        """attn='ntrans' / region_attn='ntrans': ONE rrt_encoder_nystrom_forward_f32 call.  Inference by default; after
+        enable_training() a call that needs a graph (or train() with dropout / drop-path) takes the layer path."""
+        needs = self._stochastic() or (torch.is_grad_enabled() and
+                                       (x2d.requires_grad or any(p.requires_grad for p in self.parameters())))
+        if needs and getattr(self, "_train_enabled", False):
+            graph = torch.is_grad_enabled() and (x2d.requires_grad or any(p.requires_grad for p in self.parameters()))
+            if out is not None and graph:
+                raise NotImplementedError("rrt_mil_amd.RRTEncoder with NystromAttention layers: out= cannot take a result that "
+                                          "carries a graph; call without out=, or under torch.no_grad()")
+            res = self._forward_bag_nystrom_train(x2d)
+            return res if out is None else out.copy_(res)
         if self._stochastic():
             raise NotImplementedError("rrt_mil_amd.RRTEncoder with NystromAttention layers (attn='ntrans' / region_attn="
                                       "'ntrans') in train() with dropout: inference only, call eval() under torch.no_grad()")
@@ -916,8 +1085,8 @@ class RRTEncoder(nn.Module):
         return False
 
     def forward(self, x):
-        if self._nys_mode:              # inference only: _forward_bag_nystrom raises on a graph or dropout
-            return self._forward_impl(x, False)
+        if self._nys_mode:              # inference by default: _forward_bag_nystrom raises on a graph or dropout, or, after
+            return self._forward_impl(x, False)     # enable_training(), takes the layer path
         if self._wants_grad(x):
             return self._forward_impl(x, True)
         with torch.no_grad():
@@ -927,12 +1096,14 @@ class RRTEncoder(nn.Module):
         """One bag with an autograd graph (rrt_encoder_forward_train_f32 / rrt_encoder_backward_f32)."""
         if not x2d.is_cuda:
             raise _lib.RRTHipError("rrt_mil_amd.RRTEncoder runs on MI355X only; there is no CPU fallback")
-        if self._nys_mode:
+        if self._nys_mode and not getattr(self, "_train_enabled", False):
             raise NotImplementedError("rrt_mil_amd.RRTEncoder with NystromAttention layers (attn='ntrans' / region_attn="
                                       "'ntrans') has no backward: call it in eval() under torch.no_grad()")
         x2d = x2d.float().contiguous()
         if x2d.shape[1] != self.final_dim:
             raise ValueError(f"expected feature dim {self.final_dim}, got {x2d.shape[1]}")
+        if self._nys_mode:
+            return self._forward_bag_nystrom_train(x2d)
         return _EncoderFunction.apply(self, x2d, *self.parameters())
 
     def _forward_impl(self, x, train):

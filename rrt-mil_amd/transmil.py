@@ -115,6 +115,56 @@ class _NystromFn(torch.autograd.Function):
         return (None, dx) + tuple(gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[2:]))
 
 
+class _NystromBatchedFn(torch.autograd.Function):
+    """y [b, n, dim] = NystromAttention on a batch without its Dropout, fp32 -- ONE pseudo-inverse scale over all b * heads
+    matrices, in the forward and in the gradient through it: rrt_nystrom_attention_batched_forward_train_f32 (the bits of
+    rrt_nystrom_attention_batched_f32; the stash is owned by the graph node) and rrt_nystrom_attention_batched_backward_f32.
+    As _NystromFn, the parameters are saved tensors: an in-place update between forward and backward raises."""
+
+    @staticmethod
+    def forward(ctx, desc, x3d, wq, wo, bo, wc):
+        lib = _lib.load()
+        ts = [t.detach().float().contiguous() if t is not None else None for t in (x3d, wq, wo, bo, wc)]
+        x, dev = ts[0], ts[0].device
+        b, n = x.shape[0], x.shape[1]
+        w = _lib.NystromWeights()
+        w.qkv_w, w.out_w, w.out_b, w.conv_w = (_ptr(t) for t in ts[1:])
+        stash_bytes, bwd_bytes = C.c_size_t(), C.c_size_t()
+        _lib.check(lib.rrt_nystrom_batched_train_sizes(C.byref(desc), b, n, C.byref(stash_bytes), C.byref(bwd_bytes)),
+                   "rrt_nystrom_batched_train_sizes")
+        stash = torch.empty(stash_bytes.value, dtype=torch.uint8, device=dev)
+        y = torch.empty((b, n, desc.dim), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.rrt_nystrom_attention_batched_forward_train_f32(C.byref(desc), C.byref(w), x.data_ptr(), y.data_ptr(),
+                                                                           b, n, stash.data_ptr(), stash.numel(), st),
+                       "rrt_nystrom_attention_batched_forward_train_f32")
+        ctx.save_for_backward(stash, *[t for t in ts if t is not None])
+        ctx.desc, ctx.bwd_bytes, ctx.has_conv = desc, bwd_bytes.value, ts[4] is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        stash, x, wq, wo, bo = ctx.saved_tensors[:5]
+        wc = ctx.saved_tensors[5] if ctx.has_conv else None
+        desc, dev, b, n = ctx.desc, x.device, x.shape[0], x.shape[1]
+        dy = dy.float().contiguous()
+        w, g = _lib.NystromWeights(), _lib.NystromGrads()
+        w.qkv_w, w.out_w, w.out_b, w.conv_w = (_ptr(t) for t in (wq, wo, bo, wc))
+        grads = [torch.empty_like(t) if t is not None else None for t in (wq, wo, bo, wc)]
+        g.qkv_w, g.out_w, g.out_b, g.conv_w = (_ptr(t) for t in grads)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        ws = torch.empty(ctx.bwd_bytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.rrt_nystrom_attention_batched_backward_f32(C.byref(desc), C.byref(w), x.data_ptr(), dy.data_ptr(),
+                                                                      stash.data_ptr(), stash.numel(), C.byref(g), _ptr(dx), b, n,
+                                                                      ws.data_ptr(), ws.numel(), st),
+                       "rrt_nystrom_attention_batched_backward_f32")
+        return (None, dx) + tuple(gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[2:]))
+
+
 class _TransmilStepFn(torch.autograd.Function):
     """logits (1, n_classes) = the whole of TransMIL for one bag through rrt_transmil_forward_train_f32, and every parameter
     gradient (and d x, when x needs one) through ONE rrt_transmil_backward_f32.  The parameters are passed as inputs so that
@@ -178,8 +228,9 @@ class _TransmilStepFn(torch.autograd.Function):
 class NystromAttention(HeadState, nn.Module):
     """modules/nystrom_attention.py:32-149.  ``forward(x)`` with x (1, n, dim) -> (1, n, dim); ``forward_batch(x)`` with x
     (b, n, dim), 1 <= b <= 4096 -> (b, n, dim): one launch per stage for all b sequences and ONE pseudo-inverse scale over the
-    whole batch, as the reference's forward on a batch (rrt_nystrom_attention_batched_f32; inference -- ``forward``, the training
-    path and ``attention_row`` keep b = 1); ``mask=`` and
+    whole batch, as the reference's forward on a batch (rrt_nystrom_attention_batched_f32; inference by default, and after
+    ``enable_training()`` with a graph through the batched backward, b <= 2048 -- ``forward`` and ``attention_row`` keep b = 1);
+    ``mask=`` and
     ``return_attn=True`` are not implemented (the reference's mask branch names undefined variables, and TransMIL passes
     neither); ``attention_row(x, row)`` gives one row of the approximated attention matrix.  The HIP path supports dim_head = 64, num_landmarks = 256, heads <= 16, pinv_iterations <= 16, an odd
     residual_conv_kernel <= 63 and dim a multiple of 32 up to 1024; anything else raises NotImplementedError at the call."""
@@ -257,16 +308,23 @@ class NystromAttention(HeadState, nn.Module):
     def forward_batch(self, x):
         """x (b, n, dim), 1 <= b <= 4096 -> (b, n, dim): what the reference's forward computes on a batch -- every sequence
         padded in front on its own, ONE pseudo-inverse scale over all b * heads matrices -- in one launch per stage
-        (rrt_nystrom_attention_batched_f32).  With b = 1 the bits of ``forward``.  Inference only: ``eval()`` under
-        ``torch.no_grad()``; the training path keeps b = 1."""
+        (rrt_nystrom_attention_batched_f32).  With b = 1 the bits of ``forward``.  Inference by default: ``eval()`` under
+        ``torch.no_grad()``.  After ``enable_training()`` a call that needs a graph (or ``train()`` with dropout) runs the
+        batched forward-with-stash and backward under autograd (b <= 2048; fp32 under autocast; ``to_out``'s Dropout is
+        torch's own, on the result); ``forward`` and ``attention_row`` keep b = 1."""
         _no_cpu(x, "NystromAttention")
         if x.dim() != 3 or x.shape[0] < 1:
             raise ValueError(f"NystromAttention.forward_batch expects (b, n, dim), got {tuple(x.shape)}")
         if x.shape[2] != self.dim:
             raise ValueError(f"expected feature dim {self.dim}, got {x.shape[2]}")
         if (self.training and self._dropout > 0.) or _needs_graph(self, x):
-            raise NotImplementedError("rrt_mil_amd.NystromAttention.forward_batch is an inference entry (the training path keeps "
-                                      "b = 1: the backward kernels take one sequence): call it in eval() under torch.no_grad()")
+            if not getattr(self, "_train_enabled", False):
+                raise NotImplementedError("rrt_mil_amd.NystromAttention.forward_batch is an inference entry (the training path keeps "
+                                          "b = 1: the backward kernels take one sequence): call it in eval() under torch.no_grad()")
+            with torch.autocast("cuda", enabled=False):      # fp32 in every context, as the one-call path
+                y = _NystromBatchedFn.apply(self._desc(), x.float(), self.to_qkv.weight, self.to_out[0].weight,
+                                            self.to_out[0].bias, self.res_conv.weight if self.residual else None)
+                return self.to_out[1](y)
         return self._forward_batched(x)
 
     def _forward_batched(self, x):
